@@ -1,10 +1,16 @@
 #!/usr/bin/env python
 """bench.py -- BASELINE.json's metric on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5] [--no-cpu] [--share-gpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5] [--dump-outputs DIR] [--full [--no-cpu]] [--share-gpu]
 
 One *step* = one complete solve of the hot path (dual-decomposition routing, projected L-BFGS on
 log-prices, on device) from a cold start to the 1e-6 certificates on one batch of synthetic input.
+
+A plain run sets up, warms up, times the K steps and prints one JSON line: `value`, `ms_per_step` and what the
+timed steps themselves tell (evaluations, device time, blocks, certificates).  --full adds everything else the line
+can carry (below), each measured in passes of its own behind the timed region.  --dump-outputs DIR writes what the
+last timed solve hands its caller (objective, prices, net trade, every bucket's trades; float64 .npy files, at most
+~48 MB: larger trade sets are cut to a fixed, seeded sample of pools); the inputs depend on the arguments alone.
 
   --config C3 (default; the configuration the metric is quoted on): BASELINE config 3 -- 1e6 mixed Uniswap-v2 +
       Balancer pools / 1000 tokens, linear-utility arbitrage -- PER GPU.  With N > 1 every rank holds its own
@@ -28,13 +34,14 @@ is not already running under a launcher; `python -m torch.distributed.run --npro
 works as well.  value = pool-subproblems solved by all ranks / wall time of the K timed solves (barrier +
 synchronize on both sides, max over ranks; inputs resident in HBM, upload excluded).
 
-Also on the same JSON line:
+With --full, also on the same JSON line:
   roofline     -- the dominant evaluation kernel timed live with HIP events on the library's stream:
                   algorithmic bytes per launch / average launch duration vs the 8 TB/s HBM peak; next to it the
                   rocprofv3 average and PMC traffic of the newest summary committed under profiles/
   per_iteration_us -- evaluation launch / accumulator fold / RCCL all-reduce / nu update + launch boundaries
   cpu_baseline -- oracle/cfmm_oracle.c (the CPU restatement, OpenMP on the host cores) running the
                   same solve on the same instance, timed in this run (rank 0, N = 1 only)
+  and the shader clock live, the batched and PCIe-inclusive figures, the kernel-time budget, the device state
 """
 import argparse
 import csv
@@ -240,6 +247,30 @@ def kernel_table(prob, reps):
     return rows
 
 
+DUMP_TRADE_BYTES = 48 << 20      # --dump-outputs: the trade arrays' share (nu, psi and the objective are a few kB beside it)
+
+
+def dump_outputs(prob, out_dir, budget=DUMP_TRADE_BYTES):
+    """--dump-outputs DIR: what the last solve hands its caller, as DIR/<name>.npy in float64 -- objective [primal, dual value],
+    the prices nu, the net trade psi and every bucket's tenders / receipts (Problem.bucket_trades, [legs][pools]).  When the trades
+    pass `budget` bytes, every bucket keeps the same fraction of its pools: a sample drawn with a fixed seed, sorted, so that two
+    runs with the same arguments write the same pools.  Returns the names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"objective": np.array([prob.value, prob.dual_value]), "nu": prob.nu, "psi": prob.psi}
+    trades = prob._trades()
+    frac = min(1.0, budget / max(1, sum(d.nbytes + l.nbytes for d, l in trades.values())))
+    for key, (d, l) in sorted(trades.items(), key=lambda kv: str(kv[0])):
+        name = key if isinstance(key, str) else (f"gn{key}" if isinstance(key, int) else f"gk_{key[0]}{key[1]}")
+        m = d.shape[1]
+        if frac < 1.0 and m:
+            idx = np.sort(np.random.default_rng(0).choice(m, max(1, int(frac * m)), replace=False))
+            d, l = d[:, idx], l[:, idx]
+        arrays[f"trades_{name}_delta"], arrays[f"trades_{name}_lambda"] = d, l
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` (N > 1) outside any launcher: become the launcher.  One rank per GPU of this node,
     rendezvous on 127.0.0.1 (the container hostname may not resolve)."""
@@ -261,6 +292,11 @@ def main():
     ap.add_argument("--zipf", type=float, default=None, help="SURVEY 8(d)'s stress variant: token pairs drawn Zipf(s) hub-weighted instead of uniform (s = 1.1)")
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--tol", type=float, default=1e-6)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: per-kernel roofline, shader clock, per-iteration split, batched and "
+                         "PCIe-inclusive figures, kernel-time budget, device state, CPU baselines (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed solve computed (objective, nu, psi, trades) as DIR/<name>.npy, float64")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-numpy", action="store_true", help="skip the one-thread NumPy evaluation beside the C baseline")
     ap.add_argument("--no-batch", action="store_true", help="skip the batched-solve figure")
@@ -275,6 +311,8 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="run the pool-sharded code path (process group, RCCL communicator, all-reduce per evaluation) even with one rank")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     launched = "WORLD_SIZE" in os.environ
     if args.gpus > 1 and not launched:
@@ -348,15 +386,16 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # The per-kernel table of the line (the evaluation launch alone, HIP events on the library's stream, at prices ~1 % off the
+    # The per-kernel table of the --full line (the evaluation launch alone, HIP events on the library's stream, at prices ~1 % off the
     # market: about 88 % of the pools trade, as in the first iterations of a solve and in tools/profile_eval.py, whose rocprofv3
     # trace is committed under profiles/) is measured HERE, in front of the warm-up steps, not behind the timed ones: a few
     # hundred launches that leave the device at its working clock.  With W = 5 cold solves (2.5 ms) alone the first timed steps
     # still ran on a ramping clock -- 20.7 us per iteration where the same binary settles at 20.0 (W = 20).  Nothing of it is
-    # inside the timed region, which is K complete cold solves either way.
+    # inside the timed region, which is K complete cold solves either way.  The discarded launches in front of it are part of
+    # every run's warm-up.
     prob._send_utility()
     idle_ghz = None
-    if rank == 0 and not args.no_clock_probe:                       # the clock of the idle chip, read well in front of everything timed
+    if args.full and rank == 0 and not args.no_clock_probe:        # the clock of the idle chip, read well in front of everything timed
         try:
             prob.ctx.clock_probe_start(100.0, 50.0)
             time.sleep(0.004)
@@ -370,7 +409,7 @@ def main():
         prob.ctx.time_eval_kernel(_l.TIME_ALL, 300)       #  are 2 ms, and its table read 6.5 us where the settled kernel takes 5.8)
         if time.perf_counter() - t_ramp >= 0.025:
             break
-    rows = kernel_table(prob, args.kernel_reps)
+    rows = kernel_table(prob, args.kernel_reps) if args.full else None
     for _ in range(args.warmup):
         prob.solve(tol=args.tol, **solve_kw)
     # ... and, single process only, further UNTIMED solves until the host has settled too (reported as `extra_warmup_steps`): the
@@ -418,6 +457,8 @@ def main():
         tb = te
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:                            # (before anything below solves again)
+        dump_outputs(prob, args.dump_outputs)
     # The shader-clock probe (include/cfmm.h: cfmm_clock_probe_*): one sleeping wave on a stream of its own that samples {shader cycles,
     # 100 MHz ticks} every 100 us while solves run -- the clock the line's launch durations were measured at.  It runs in a pass of its
     # OWN, the same solves again right behind the timed region, not beside it: the first version sampled during the timed steps, and the
@@ -426,7 +467,7 @@ def main():
     live_ghz = None
     chain = None
     clock_pass = None
-    if not args.no_clock_probe:                                     # (every rank: the solves of a sharded run are collective; the probe is rank 0's)
+    if args.full and not args.no_clock_probe:                       # (every rank: the solves of a sharded run are collective; the probe is rank 0's)
         n_pass = int(min(max(args.steps // 2, 20), 100))
         probing = False
         if rank == 0:
@@ -461,7 +502,7 @@ def main():
     # steps again with that memo dropped before every solve = what a FIRST solve of a new basket costs; and, separately, the
     # one-off per-network fit (part of setting a network up, like the upload and the token-block ordering of its pools).
     cold_start_ms = potentials_ms = None
-    if args.config == "C5" and not sharded:
+    if args.full and args.config == "C5" and not sharded:
         t0 = time.perf_counter()
         for _ in range(args.steps):
             utility._start_memo = None
@@ -472,22 +513,18 @@ def main():
         t0 = time.perf_counter(); _pm._potentials(prob.net); potentials_ms = 1e3 * (time.perf_counter() - t0)
 
     # per-iteration split (all ranks: the all-reduce timing is a collective)
-    fold_s, ar_s = prob.ctx.time_collective(args.kernel_reps) if sharded else (0.0, 0.0)
+    fold_s, ar_s = prob.ctx.time_collective(args.kernel_reps) if (args.full and sharded) else (0.0, 0.0)
     # the evaluation launch at prices ~1 % off the market (about 88 % of the pools trade, as in the first iterations
     # of a solve and in tools/profile_eval.py, whose rocprofv3 trace is committed under profiles/)
     second_order = prob.stats.get("method") == 2
     newton_kernels = None
-    if second_order and not sharded:
+    if args.full and second_order and not sharded:
         newton_kernels = prob.ctx.time_newton_kernels(max(prob.stats.get("barrier_mu", 0.0), 1e-12), 5)      # at the solution just found
     out = None
     if rank == 0:
-        dom = rows[0]
         mix = ", ".join(f"{k}={len(prob.net[k]['Ra'])}" for k in ("cp2", "w2", "curve2", "sum2") if k in prob.net)
         if "gn" in prob.net:
             mix += ", gn3-8=" + str(sum(b["R"].shape[1] for b in prob.net["gn"].values()))
-        prof = profile_record(args.config, "zipf" if args.zipf else "")
-        pk = "iter" if prob.stats.get("method") == 1 and prof["iter"]["rocprof_avg_us"] else "eval"
-        us_iter = 1e6 * dev_s / max(evals, 1)
         if strong:
             workload = (f"{args.config}: {total_pools} constant-product pools / {net['n_tokens']} tokens split over {world} GPU(s) "
                         f"({prob.m} per GPU: {mix}), linear-utility arbitrage, cold-start solve to gap,infeas <= {args.tol:g}")
@@ -501,44 +538,6 @@ def main():
             workload += f"; token pairs Zipf({args.zipf:g}) hub-weighted (SURVEY 8(d) stress variant)"
         if args.share_gpu:
             workload += f"; --share-gpu: the {world} ranks are processes on ONE device (functional run of the multi-rank path, not a scaling number)"
-        # the binding roofline of the dominant kernel: the algorithmic bytes against the HBM peak, and the cycles its
-        # vector ALUs were issuing (PMC, newest profile) against all SIMD-cycles of the launch; `bound` names the larger
-        # `frac` prices the ALGORITHMIC bytes (the contract's definition); `hbm_frac` the bytes the launch loads AS STORED -- the same
-        # number unless a bucket carries its compact mirror (>= 1e6 two-asset pools: 21 B instead of 32), where the algorithmic
-        # figure can pass what the memory system delivers and only `hbm_frac` is a statement about bandwidth
-        stored_bytes = prob.ctx.eval_bytes()
-        alg_frac = dom["bytes"] / (us_iter * 1e-6) / 1e9 / HBM_PEAK_GBS
-        hbm_frac = stored_bytes / (us_iter * 1e-6) / 1e9 / HBM_PEAK_GBS
-        ev_stored_frac = stored_bytes / dom["seconds"] / 1e9 / HBM_PEAK_GBS
-
-        def valu_fraction(pr, live_seconds):
-            """vector-issue fraction of a profiled launch.  With GRBM_GUI_ACTIVE in the same PMC summary: VALU-issue cycles /
-            (SIMDs x shader-clock cycles of the SAME dispatches) -- profile-only, no clock assumed; otherwise (older
-            summaries) the old estimate against 2.4 GHz x the live duration, flagged as such."""
-            if not pr["valu_busy"]:
-                return None, None
-            if pr["sq_busy"] and pr["pmc_ns"]:
-                # (NOT against the profiled dispatch's own cycles: a counter pass stretches the dispatch -- 21.8 us on one box, 35.6
-                #  on another for the same 20.5 us launch -- and the fraction of a stretched launch says nothing about the live one)
-                clk = pr["sq_busy"] / 32.0 / (pr["pmc_ns"] * 1e-9)
-                return pr["valu_busy"] / (SIMDS * clk * live_seconds), ("4 x SQ_ACTIVE_INST_VALU / (1024 SIMDs x effective clock x the LIVE launch duration); clock = "
-                                                                         "SQ_BUSY_CYCLES / 32 shader engines / the dispatch's duration under the same PMC pass = %.2f GHz (%s)" % (clk / 1e9, pr["traffic_file"]))
-            return pr["valu_busy"] / (SIMDS * CLOCK_HZ * live_seconds), "estimate: 4 x SQ_ACTIVE_INST_VALU (" + str(pr["traffic_file"]) + ") / (1024 SIMDs x 2.4 GHz x the LIVE launch duration)"
-        valu_frac, valu_src = valu_fraction(prof[pk], us_iter * 1e-6)
-        ev_valu, _ = valu_fraction(prof["eval"], dom["seconds"])
-        eff_clock = (prof[pk]["sq_busy"] / 32.0 / prof[pk]["pmc_ns"]) if (prof[pk]["sq_busy"] and prof[pk]["pmc_ns"]) else None
-        # ... and with the clock measured LIVE beside the timed solves (the probe above): the issue cycles are a property of the binary
-        # (SQ_ACTIVE_INST_VALU of the committed PMC pass), the SIMD-cycles available are 1024 x the live clock x the live launch duration --
-        # no profiler clock in it.  `clock_accounts_for` = how much of the live / profiled launch-time ratio the clock ratio explains.
-        valu_frac_live = (prof[pk]["valu_busy"] / (SIMDS * live_ghz * 1e9 * us_iter * 1e-6)) if (prof[pk]["valu_busy"] and live_ghz) else None
-        launch_cycles_live = us_iter * 1e-6 * live_ghz * 1e9 if live_ghz else None
-        rp_us = prof[pk]["rocprof_avg_us"]
-        launch_cycles_profiled = rp_us * 1e-6 * eff_clock * 1e9 if (rp_us and eff_clock) else None
-        clock_note = None
-        if launch_cycles_live and launch_cycles_profiled:
-            clock_note = {"launch_shader_cycles_live": launch_cycles_live, "launch_shader_cycles_profiled": launch_cycles_profiled,
-                          "time_ratio_live_over_profiled": us_iter / rp_us, "cycle_ratio_live_over_profiled": launch_cycles_live / launch_cycles_profiled,
-                          "note": "launch duration x clock on both sides: a cycle ratio near 1 with a time ratio above it = the same binary on a slower clock"}
         out = {
             "metric": METRIC,
             "value": value, "unit": "pool-subproblems/s", "n_gpus": world, "steps": args.steps,
@@ -553,209 +552,252 @@ def main():
             "evals_per_solve": evals / args.steps,
             "device_ms_per_step": 1e3 * dev_s / args.steps,
             "us_per_eval": 1e6 * dt / max(evals, 1),
-            "per_iteration_us": {"total_device": us_iter, "evaluation": dom["us"], "fold": 1e6 * fold_s, "allreduce": 1e6 * ar_s,
-                                 "update_in_launch": us_iter - dom["us"] - 1e6 * (fold_s + ar_s),
-                                 "note": "evaluation = the evaluation launch alone (eval_kernel), fold / all-reduce as back-to-back launches, all with "
-                                         "HIP events on the library's stream; the remainder of the device time per iteration is the in-launch nu "
-                                         "update (and, per solve, the start kernel / first evaluation / idle run-ahead launches, amortised)"},
             "gap": prob.gap, "infeas": prob.infeas, "objective": prob.value,
-            # The dominant kernel of the timed region is iter_kernel: ONE launch per outer iteration = the in-launch nu update
-            # (latency-bound, L2 traffic only) + the evaluation of every pool (the streaming part).  Its average duration over
-            # the timed region is the device time per iteration (HIP events around the outer loop, one launch per iteration,
-            # back to back); the algorithmic bytes are those of the evaluation.  `evaluation_only` is the same tile code
-            # launched without the update (eval_kernel, what cfmm_eval_dual runs), timed as back-to-back launches.
-            "roofline": {"bound": "valu" if (valu_frac is not None and valu_frac > hbm_frac) else "hbm",
-                         "kernel": "iter_kernel (nu update + evaluation, one launch per iteration)" if prob.stats.get("method") == 1 else dom["kernel"],
-                         "achieved": dom["bytes"] / (us_iter * 1e-6) / 1e9, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": alg_frac, "hbm_frac": hbm_frac, "valu_frac": valu_frac,
-                         "bytes_as_stored_per_launch": stored_bytes,
-                         "frac_note": "frac = algorithmic bytes (SURVEY 8(d): 32 B per constant-product pool, ...) / launch duration / 8 TB/s; hbm_frac = the bytes "
-                                      "the launch loads as stored (compact mirror of ids and fee where built) / the same -- equal unless a mirror exists",
-                         "valu_frac_note": valu_src, "effective_clock_ghz_under_profiler": eff_clock,
-                         "effective_clock_ghz_live": live_ghz, "clock_pass": clock_pass, "clock_ghz_idle": idle_ghz,
-                         "valu_frac_live_clock": valu_frac_live, "clock_check": clock_note, "clock_probe_fma_chain": chain,
-                         "effective_clock_note": "live = shader cycles / wall time sampled every 100 us by one sleeping wave beside the solves of `clock_pass`, right behind the timed region (cfmm_clock_probe_*); "
-                                                 "valu_frac_live_clock = 4 x SQ_ACTIVE_INST_VALU (committed PMC pass) / (1024 SIMDs x live clock x live launch duration)",
-                         "l2_hit_rate": prof[pk]["l2_hit_rate"],
-                         "traffic": prof[pk]["traffic"],
-                         "traffic_source": prof[pk]["traffic_file"],
-                         "algorithmic_bytes_per_launch": dom["bytes"], "avg_launch_us": us_iter,
-                         "rocprof_avg_launch_us": prof[pk]["rocprof_avg_us"], "rocprof_source": prof[pk]["rocprof_file"],
-                         "evaluation_only": {"kernel": "eval_kernel", "avg_launch_us": dom["seconds"] * 1e6, "achieved": dom["GBps"],
-                                             "frac": dom["GBps"] / HBM_PEAK_GBS, "hbm_frac": ev_stored_frac, "valu_frac": ev_valu,
-                                             "bound": "valu" if (ev_valu is not None and ev_valu > ev_stored_frac) else "hbm",
-                                             "traffic": prof["eval"]["traffic"],
-                                             "rocprof_avg_launch_us": prof["eval"]["rocprof_avg_us"], "rocprof_source": prof["eval"]["rocprof_file"]},
-                         "note": TRAFFIC_NOTE[args.config],
-                         "all_kernels": [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items()} for r in rows]},
         }
         if second_order:
-            # the second-order path: `value` counts its dual evaluations (smoothed and exact) like any other; the time goes
-            # into the dense solve of each Newton step, so THAT is the dominant kernel group and its ceiling is the fp64
-            # vector rate (no MFMA in it).  The smoothed evaluation is priced against both ceilings beside it.
             out["newton_steps_per_solve"] = newton_steps / args.steps
-            if cold_start_ms is not None:
-                out["start_prices"] = {"ms_per_step_memoised": 1e3 * dt / args.steps, "ms_per_step_recomputed": cold_start_ms,
-                                       "network_potentials_ms_once_per_network": potentials_ms,
-                                       "note": "`ms_per_step` / `value` are measured behind the warm-up, with this utility's start prices memoised "
-                                               "(cfmm/problem.py: start_prices); `ms_per_step_recomputed` repeats the timed steps with the memo dropped "
-                                               "before every solve (a new basket on the same pools: O(n) from the network's potentials); the least-squares "
-                                               "fit of those potentials is a one-off per network, timed separately"}
-            if newton_kernels:
-                nk = newton_kernels
-                nr = (net["n_tokens"] + 31) // 32 * 32
-                # n^3 / 3 for the factorisation + 2 n^3 / 3 for the inverse factor that rides its launches (chol.hpp, round 4: two
-                # 32^3 products per tile, ~n^3 / (6 x 32^3) tiles) -- the price of a back substitution that is one matrix-vector product
-                inverse_factor = os.environ.get("CFMM_BACKSUB", "") != "classic"
-                useful_flops = nr ** 3 / 3.0                       # the factorisation proper: what a Newton step NEEDS
-                flops = useful_flops * (3.0 if inverse_factor else 1.0)
-                # which kernel, how many launches: as cfmm_hip.hip: launch_factor chooses them (chol2.hpp takes the block columns in
-                # pairs -- CH_NB = 32, rows rounded up to a pair of blocks -- plus one launch that only finishes the inverse factor)
-                pairs = os.environ.get("CFMM_CHOL", "") != "single"
-                nr2 = (net["n_tokens"] + 63) // 64 * 64
-                nlaunch = (nr2 // 64 + (1 if inverse_factor and nr2 // 32 >= 2 else 0)) if pairs else nr2 // 32
-                kname = ("chol_step2_kernel (csrc/chol2.hpp: two block columns per launch, fp64 MFMA side products" if pairs else
-                         "chol_step_kernel (csrc/chol.hpp: one block column per launch")
-                sm_bytes = dom["bytes"] + 16 * sum(len(prob.net[k]["Ra"]) for k in ("cp2", "w2", "curve2") if k in prob.net)     # + the warm starts: 8 B per direction
-                tf = flops / nk["factor"] / 1e12
-                rp_us, _, rp_file = newton_profile_record("chol_step2_kernel" if pairs else "chol_step_kernel")
-                out["roofline"].update({
-                    "bound": "valu", "kernel": kname + f"; the dense Cholesky of one Newton step with its inverse factor: {nlaunch} dependent launches)",
-                    "launches_per_factorisation": nlaunch,
-                    "achieved": tf, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / FP64_VECTOR_PEAK_TFLOPS,
-                    "flop_frac": tf / FP64_VECTOR_PEAK_TFLOPS, "useful_flop_frac": useful_flops / nk["factor"] / 1e12 / FP64_VECTOR_PEAK_TFLOPS,
-                    "valu_frac": None, "hbm_frac": None, "traffic": None, "traffic_source": None,
-                    "flop_frac_note": f"flop_frac (= frac): the flops the launches EXECUTE -- n^3/3 of the {nr} x {nr} factorisation + 2n^3/3 of the inverse factor riding along "
-                                      "(work added to turn the back substitution into one matrix-vector product) -- / their measured time, against the fp64 vector peak; "
-                                      "useful_flop_frac: the n^3/3 a Newton step needs alone / the same time (a flop rate, not the PMC issue fraction the other configs report as valu_frac)",
-                    "valu_frac_note": None,
-                    "avg_launch_us": nk["factor"] * 1e6, "algorithmic_bytes_per_launch": None,
-                    "avg_launch_us_note": "the whole factorisation (the chain of dependent launches), HIP events on the library's stream; "
-                                          "rocprof_avg_launch_us = the kernel-trace average of ONE launch of the chain x launches_per_factorisation",
-                    "rocprof_avg_per_launch_us": rp_us, "rocprof_avg_launch_us": (rp_us * nlaunch if rp_us else None), "rocprof_source": rp_file,
-                    "newton_step_us": {"smoothed_evaluation_with_hessian": nk["smooth_hess"] * 1e6, "smoothed_evaluation": nk["smooth"] * 1e6,
-                                       "factorisation": nk["factor"] * 1e6, "back_substitution": nk["backsolve"] * 1e6},
-                    "smoothed_evaluation": {"kernel": "smooth_kernel<false>", "avg_launch_us": nk["smooth"] * 1e6,
-                                            "algorithmic_bytes_per_launch": sm_bytes, "hbm_frac": sm_bytes / nk["smooth"] / 1e9 / HBM_PEAK_GBS},
-                })
-        if not sharded and not strong and not args.no_batch and not second_order and "curve2" not in prob.net and "sum2" not in prob.net:
-            # B price vectors per pool read (cfmm_solve_batch; the parametric-sweep use of two-asset.py:34-100): B solves
-            # of the same pools under B utilities in lock-step.  Not `value` (the metric is quoted on ONE solve of this
-            # config): an extra figure in the same unit.
-            B = prob.ctx.batch_capacity()
-            rng = np.random.default_rng(1)
-            us = [cfmm.Arbitrage(net["c"] * np.exp(rng.normal(0, 0.01, net["n_tokens"]))) for _ in range(B)]
-            prob.solve_many(us, tol=args.tol, batch=B)
-            t0 = time.perf_counter(); bev = 0; bit = 0; bdev = 0.0
-            for _ in range(args.steps):
-                res = prob.solve_many(us, tol=args.tol, batch=B)
-                if any(r["status"] != "optimal" for r in res):
-                    raise SystemExit("batched solve: " + ", ".join(r["status"] for r in res))
-                bev += sum(r["stats"]["evals"] for r in res); bit += max(r["stats"]["evals"] for r in res)
-                bdev += res[0]["stats"]["device_seconds"]
-            bdt = time.perf_counter() - t0
-            out["batched"] = {"solves_per_batch": B, "value": bev * prob.m / bdt, "unit": "pool-subproblems/s",
-                              "ms_per_batch": 1e3 * bdt / args.steps, "ms_per_solve": 1e3 * bdt / args.steps / B,
-                              "device_us_per_lockstep_iteration": 1e6 * bdev / max(bit, 1),
-                              "device_us_per_solve_iteration": 1e6 * bdev / max(bev, 1),
-                              "note": f"{B} cold solves of the same pools under {B} market-value vectors (1 % apart) in lock-step: every "
-                                      "outer iteration reads every pool column once and solves each pool at all price vectors "
-                                      "(eval_batch_kernel + one update workgroup per solve); wall time includes the host-side start "
-                                      "prices and certificate checks of every solve"}
-            prob.set_utility(cfmm.Arbitrage(net["c"]))
-        # the line's own kernel figures against the committed budget (profiles/budget.json), and what the driver exposes about the device
-        bkey = "C4" if args.config == "C4" and world == 1 else args.config
-        if not sharded and args.scale == 1.0 and not args.zipf:
-            measured = {"eval_kernel_us": dom["us"]}
+        if args.full:
+            dom = rows[0]
+            prof = profile_record(args.config, "zipf" if args.zipf else "")
+            pk = "iter" if prob.stats.get("method") == 1 and prof["iter"]["rocprof_avg_us"] else "eval"
+            us_iter = 1e6 * dev_s / max(evals, 1)
+            # the binding roofline of the dominant kernel: the algorithmic bytes against the HBM peak, and the cycles its
+            # vector ALUs were issuing (PMC, newest profile) against all SIMD-cycles of the launch; `bound` names the larger
+            # `frac` prices the ALGORITHMIC bytes (the contract's definition); `hbm_frac` the bytes the launch loads AS STORED -- the same
+            # number unless a bucket carries its compact mirror (>= 1e6 two-asset pools: 21 B instead of 32), where the algorithmic
+            # figure can pass what the memory system delivers and only `hbm_frac` is a statement about bandwidth
+            stored_bytes = prob.ctx.eval_bytes()
+            alg_frac = dom["bytes"] / (us_iter * 1e-6) / 1e9 / HBM_PEAK_GBS
+            hbm_frac = stored_bytes / (us_iter * 1e-6) / 1e9 / HBM_PEAK_GBS
+            ev_stored_frac = stored_bytes / dom["seconds"] / 1e9 / HBM_PEAK_GBS
+
+            def valu_fraction(pr, live_seconds):
+                """vector-issue fraction of a profiled launch.  With GRBM_GUI_ACTIVE in the same PMC summary: VALU-issue cycles /
+                (SIMDs x shader-clock cycles of the SAME dispatches) -- profile-only, no clock assumed; otherwise (older
+                summaries) the old estimate against 2.4 GHz x the live duration, flagged as such."""
+                if not pr["valu_busy"]:
+                    return None, None
+                if pr["sq_busy"] and pr["pmc_ns"]:
+                    # (NOT against the profiled dispatch's own cycles: a counter pass stretches the dispatch -- 21.8 us on one box, 35.6
+                    #  on another for the same 20.5 us launch -- and the fraction of a stretched launch says nothing about the live one)
+                    clk = pr["sq_busy"] / 32.0 / (pr["pmc_ns"] * 1e-9)
+                    return pr["valu_busy"] / (SIMDS * clk * live_seconds), ("4 x SQ_ACTIVE_INST_VALU / (1024 SIMDs x effective clock x the LIVE launch duration); clock = "
+                                                                             "SQ_BUSY_CYCLES / 32 shader engines / the dispatch's duration under the same PMC pass = %.2f GHz (%s)" % (clk / 1e9, pr["traffic_file"]))
+                return pr["valu_busy"] / (SIMDS * CLOCK_HZ * live_seconds), "estimate: 4 x SQ_ACTIVE_INST_VALU (" + str(pr["traffic_file"]) + ") / (1024 SIMDs x 2.4 GHz x the LIVE launch duration)"
+            valu_frac, valu_src = valu_fraction(prof[pk], us_iter * 1e-6)
+            ev_valu, _ = valu_fraction(prof["eval"], dom["seconds"])
+            eff_clock = (prof[pk]["sq_busy"] / 32.0 / prof[pk]["pmc_ns"]) if (prof[pk]["sq_busy"] and prof[pk]["pmc_ns"]) else None
+            # ... and with the clock measured LIVE beside the timed solves (the probe above): the issue cycles are a property of the binary
+            # (SQ_ACTIVE_INST_VALU of the committed PMC pass), the SIMD-cycles available are 1024 x the live clock x the live launch duration --
+            # no profiler clock in it.  `clock_accounts_for` = how much of the live / profiled launch-time ratio the clock ratio explains.
+            valu_frac_live = (prof[pk]["valu_busy"] / (SIMDS * live_ghz * 1e9 * us_iter * 1e-6)) if (prof[pk]["valu_busy"] and live_ghz) else None
+            launch_cycles_live = us_iter * 1e-6 * live_ghz * 1e9 if live_ghz else None
+            rp_us = prof[pk]["rocprof_avg_us"]
+            launch_cycles_profiled = rp_us * 1e-6 * eff_clock * 1e9 if (rp_us and eff_clock) else None
+            clock_note = None
+            if launch_cycles_live and launch_cycles_profiled:
+                clock_note = {"launch_shader_cycles_live": launch_cycles_live, "launch_shader_cycles_profiled": launch_cycles_profiled,
+                              "time_ratio_live_over_profiled": us_iter / rp_us, "cycle_ratio_live_over_profiled": launch_cycles_live / launch_cycles_profiled,
+                              "note": "launch duration x clock on both sides: a cycle ratio near 1 with a time ratio above it = the same binary on a slower clock"}
+            out.update({
+                "per_iteration_us": {"total_device": us_iter, "evaluation": dom["us"], "fold": 1e6 * fold_s, "allreduce": 1e6 * ar_s,
+                                     "update_in_launch": us_iter - dom["us"] - 1e6 * (fold_s + ar_s),
+                                     "note": "evaluation = the evaluation launch alone (eval_kernel), fold / all-reduce as back-to-back launches, all with "
+                                             "HIP events on the library's stream; the remainder of the device time per iteration is the in-launch nu "
+                                             "update (and, per solve, the start kernel / first evaluation / idle run-ahead launches, amortised)"},
+                # The dominant kernel of the timed region is iter_kernel: ONE launch per outer iteration = the in-launch nu update
+                # (latency-bound, L2 traffic only) + the evaluation of every pool (the streaming part).  Its average duration over
+                # the timed region is the device time per iteration (HIP events around the outer loop, one launch per iteration,
+                # back to back); the algorithmic bytes are those of the evaluation.  `evaluation_only` is the same tile code
+                # launched without the update (eval_kernel, what cfmm_eval_dual runs), timed as back-to-back launches.
+                "roofline": {"bound": "valu" if (valu_frac is not None and valu_frac > hbm_frac) else "hbm",
+                             "kernel": "iter_kernel (nu update + evaluation, one launch per iteration)" if prob.stats.get("method") == 1 else dom["kernel"],
+                             "achieved": dom["bytes"] / (us_iter * 1e-6) / 1e9, "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": alg_frac, "hbm_frac": hbm_frac, "valu_frac": valu_frac,
+                             "bytes_as_stored_per_launch": stored_bytes,
+                             "frac_note": "frac = algorithmic bytes (SURVEY 8(d): 32 B per constant-product pool, ...) / launch duration / 8 TB/s; hbm_frac = the bytes "
+                                          "the launch loads as stored (compact mirror of ids and fee where built) / the same -- equal unless a mirror exists",
+                             "valu_frac_note": valu_src, "effective_clock_ghz_under_profiler": eff_clock,
+                             "effective_clock_ghz_live": live_ghz, "clock_pass": clock_pass, "clock_ghz_idle": idle_ghz,
+                             "valu_frac_live_clock": valu_frac_live, "clock_check": clock_note, "clock_probe_fma_chain": chain,
+                             "effective_clock_note": "live = shader cycles / wall time sampled every 100 us by one sleeping wave beside the solves of `clock_pass`, right behind the timed region (cfmm_clock_probe_*); "
+                                                     "valu_frac_live_clock = 4 x SQ_ACTIVE_INST_VALU (committed PMC pass) / (1024 SIMDs x live clock x live launch duration)",
+                             "l2_hit_rate": prof[pk]["l2_hit_rate"],
+                             "traffic": prof[pk]["traffic"],
+                             "traffic_source": prof[pk]["traffic_file"],
+                             "algorithmic_bytes_per_launch": dom["bytes"], "avg_launch_us": us_iter,
+                             "rocprof_avg_launch_us": prof[pk]["rocprof_avg_us"], "rocprof_source": prof[pk]["rocprof_file"],
+                             "evaluation_only": {"kernel": "eval_kernel", "avg_launch_us": dom["seconds"] * 1e6, "achieved": dom["GBps"],
+                                                 "frac": dom["GBps"] / HBM_PEAK_GBS, "hbm_frac": ev_stored_frac, "valu_frac": ev_valu,
+                                                 "bound": "valu" if (ev_valu is not None and ev_valu > ev_stored_frac) else "hbm",
+                                                 "traffic": prof["eval"]["traffic"],
+                                                 "rocprof_avg_launch_us": prof["eval"]["rocprof_avg_us"], "rocprof_source": prof["eval"]["rocprof_file"]},
+                             "note": TRAFFIC_NOTE[args.config],
+                             "all_kernels": [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items()} for r in rows]},
+            })
             if second_order:
+                # the second-order path: `value` counts its dual evaluations (smoothed and exact) like any other; the time goes
+                # into the dense solve of each Newton step, so THAT is the dominant kernel group and its ceiling is the fp64
+                # vector rate (no MFMA in it).  The smoothed evaluation is priced against both ceilings beside it.
+                if cold_start_ms is not None:
+                    out["start_prices"] = {"ms_per_step_memoised": 1e3 * dt / args.steps, "ms_per_step_recomputed": cold_start_ms,
+                                           "network_potentials_ms_once_per_network": potentials_ms,
+                                           "note": "`ms_per_step` / `value` are measured behind the warm-up, with this utility's start prices memoised "
+                                                   "(cfmm/problem.py: start_prices); `ms_per_step_recomputed` repeats the timed steps with the memo dropped "
+                                                   "before every solve (a new basket on the same pools: O(n) from the network's potentials); the least-squares "
+                                                   "fit of those potentials is a one-off per network, timed separately"}
                 if newton_kernels:
-                    measured.update({"smooth_hess_us": newton_kernels["smooth_hess"] * 1e6, "smooth_us": newton_kernels["smooth"] * 1e6,
-                                     "factor_plus_backsolve_us": (newton_kernels["factor"] + newton_kernels["backsolve"]) * 1e6})
-            else:
-                measured["iter_kernel_us_per_iteration"] = us_iter
-                if "batched" in out:
-                    measured[f"batch{out['batched']['solves_per_batch']}_us_per_lockstep_iteration"] = out["batched"]["device_us_per_lockstep_iteration"]
-            out["budget"] = budget_check(bkey, measured)
-            out["budget_ok"] = out["budget"]["ok"] if out["budget"] else None
-        out["device_state"] = device_state()
-        if not sharded and not strong and not second_order:
-            # the same solve with the host-buffer hand-over inside the clock (never `value`): a fresh context, the pool columns
-            # uploaded from pageable NumPy buffers, utility, one cold solve, prices and psi read back -- through the raw
-            # C-ABI calls INTEGRATION.md's stub makes
-            from cfmm.problem import KIND2
-            u = cfmm.Arbitrage(net["c"])
-            rows = []
-            for _ in range(5):
-                t0 = time.perf_counter()
-                c2 = _lib.Context(net["n_tokens"], 0)
-                for key, kind in KIND2.items():
-                    if key in net:
-                        b = net[key]
-                        c2.upload_pools2(kind, b["Ra"], b["Rb"], b["fee"], b["ia"], b["ib"], b.get("wa") if key == "w2" else b.get("alpha"))
-                for k, b in net.get("gn", {}).items():
-                    c2.upload_poolsN(b["idx"], b["R"], b["w"], b["fee"])
-                t1 = time.perf_counter()
-                c2.set_utility(u.c, u.h, u.ctype); st2 = c2.solve(net["c"], tol=args.tol); c2.get_solution()
-                t2 = time.perf_counter()
-                rows.append((t2 - t0, t1 - t0, st2["evals"]))
-                c2.close()
-            rows.sort()
-            tot, up, ev2 = rows[len(rows) // 2]
-            out["pcie_inclusive"] = {"value": ev2 * prob.m / tot, "unit": "pool-subproblems/s", "ms_total": 1e3 * tot, "ms_create_and_upload": 1e3 * up,
-                                     "upload_GBps": dom["bytes"] / up / 1e9, "evals": ev2,
-                                     "note": "median of 5: cfmm_create + cfmm_upload_* of the pool columns from pageable host buffers + "
-                                             "cfmm_set_utility + one cold cfmm_solve + cfmm_get_solution"}
-        if not sharded and not args.no_cpu:
-            from oracle.c_oracle import Oracle
-            avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-            # calibrate the thread count on single dual evaluations (a cgroup quota can make "all logical
-            # CPUs" the slowest choice), then time full solves with the best one
-            best = None
-            for th in sorted({avail, max(1, avail // 2), max(1, avail // 4), min(avail, 64), min(avail, 32), min(avail, 16)}, reverse=True):
-                o = Oracle(net["n_tokens"], threads=th)
-                o.add_network(net); o.set_utility(net["c"])
-                o.eval(net["c"])
-                t0 = time.perf_counter()
-                for _ in range(3):
+                    nk = newton_kernels
+                    nr = (net["n_tokens"] + 31) // 32 * 32
+                    # n^3 / 3 for the factorisation + 2 n^3 / 3 for the inverse factor that rides its launches (chol.hpp, round 4: two
+                    # 32^3 products per tile, ~n^3 / (6 x 32^3) tiles) -- the price of a back substitution that is one matrix-vector product
+                    inverse_factor = os.environ.get("CFMM_BACKSUB", "") != "classic"
+                    useful_flops = nr ** 3 / 3.0                       # the factorisation proper: what a Newton step NEEDS
+                    flops = useful_flops * (3.0 if inverse_factor else 1.0)
+                    # which kernel, how many launches: as cfmm_hip.hip: launch_factor chooses them (chol2.hpp takes the block columns in
+                    # pairs -- CH_NB = 32, rows rounded up to a pair of blocks -- plus one launch that only finishes the inverse factor)
+                    pairs = os.environ.get("CFMM_CHOL", "") != "single"
+                    nr2 = (net["n_tokens"] + 63) // 64 * 64
+                    nlaunch = (nr2 // 64 + (1 if inverse_factor and nr2 // 32 >= 2 else 0)) if pairs else nr2 // 32
+                    kname = ("chol_step2_kernel (csrc/chol2.hpp: two block columns per launch, fp64 MFMA side products" if pairs else
+                             "chol_step_kernel (csrc/chol.hpp: one block column per launch")
+                    sm_bytes = dom["bytes"] + 16 * sum(len(prob.net[k]["Ra"]) for k in ("cp2", "w2", "curve2") if k in prob.net)     # + the warm starts: 8 B per direction
+                    tf = flops / nk["factor"] / 1e12
+                    rp_us, _, rp_file = newton_profile_record("chol_step2_kernel" if pairs else "chol_step_kernel")
+                    out["roofline"].update({
+                        "bound": "valu", "kernel": kname + f"; the dense Cholesky of one Newton step with its inverse factor: {nlaunch} dependent launches)",
+                        "launches_per_factorisation": nlaunch,
+                        "achieved": tf, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / FP64_VECTOR_PEAK_TFLOPS,
+                        "flop_frac": tf / FP64_VECTOR_PEAK_TFLOPS, "useful_flop_frac": useful_flops / nk["factor"] / 1e12 / FP64_VECTOR_PEAK_TFLOPS,
+                        "valu_frac": None, "hbm_frac": None, "traffic": None, "traffic_source": None,
+                        "flop_frac_note": f"flop_frac (= frac): the flops the launches EXECUTE -- n^3/3 of the {nr} x {nr} factorisation + 2n^3/3 of the inverse factor riding along "
+                                          "(work added to turn the back substitution into one matrix-vector product) -- / their measured time, against the fp64 vector peak; "
+                                          "useful_flop_frac: the n^3/3 a Newton step needs alone / the same time (a flop rate, not the PMC issue fraction the other configs report as valu_frac)",
+                        "valu_frac_note": None,
+                        "avg_launch_us": nk["factor"] * 1e6, "algorithmic_bytes_per_launch": None,
+                        "avg_launch_us_note": "the whole factorisation (the chain of dependent launches), HIP events on the library's stream; "
+                                              "rocprof_avg_launch_us = the kernel-trace average of ONE launch of the chain x launches_per_factorisation",
+                        "rocprof_avg_per_launch_us": rp_us, "rocprof_avg_launch_us": (rp_us * nlaunch if rp_us else None), "rocprof_source": rp_file,
+                        "newton_step_us": {"smoothed_evaluation_with_hessian": nk["smooth_hess"] * 1e6, "smoothed_evaluation": nk["smooth"] * 1e6,
+                                           "factorisation": nk["factor"] * 1e6, "back_substitution": nk["backsolve"] * 1e6},
+                        "smoothed_evaluation": {"kernel": "smooth_kernel<false>", "avg_launch_us": nk["smooth"] * 1e6,
+                                                "algorithmic_bytes_per_launch": sm_bytes, "hbm_frac": sm_bytes / nk["smooth"] / 1e9 / HBM_PEAK_GBS},
+                    })
+            if not sharded and not strong and not args.no_batch and not second_order and "curve2" not in prob.net and "sum2" not in prob.net:
+                # B price vectors per pool read (cfmm_solve_batch; the parametric-sweep use of two-asset.py:34-100): B solves
+                # of the same pools under B utilities in lock-step.  Not `value` (the metric is quoted on ONE solve of this
+                # config): an extra figure in the same unit.
+                B = prob.ctx.batch_capacity()
+                rng = np.random.default_rng(1)
+                us = [cfmm.Arbitrage(net["c"] * np.exp(rng.normal(0, 0.01, net["n_tokens"]))) for _ in range(B)]
+                prob.solve_many(us, tol=args.tol, batch=B)
+                t0 = time.perf_counter(); bev = 0; bit = 0; bdev = 0.0
+                for _ in range(args.steps):
+                    res = prob.solve_many(us, tol=args.tol, batch=B)
+                    if any(r["status"] != "optimal" for r in res):
+                        raise SystemExit("batched solve: " + ", ".join(r["status"] for r in res))
+                    bev += sum(r["stats"]["evals"] for r in res); bit += max(r["stats"]["evals"] for r in res)
+                    bdev += res[0]["stats"]["device_seconds"]
+                bdt = time.perf_counter() - t0
+                out["batched"] = {"solves_per_batch": B, "value": bev * prob.m / bdt, "unit": "pool-subproblems/s",
+                                  "ms_per_batch": 1e3 * bdt / args.steps, "ms_per_solve": 1e3 * bdt / args.steps / B,
+                                  "device_us_per_lockstep_iteration": 1e6 * bdev / max(bit, 1),
+                                  "device_us_per_solve_iteration": 1e6 * bdev / max(bev, 1),
+                                  "note": f"{B} cold solves of the same pools under {B} market-value vectors (1 % apart) in lock-step: every "
+                                          "outer iteration reads every pool column once and solves each pool at all price vectors "
+                                          "(eval_batch_kernel + one update workgroup per solve); wall time includes the host-side start "
+                                          "prices and certificate checks of every solve"}
+                prob.set_utility(cfmm.Arbitrage(net["c"]))
+            # the line's own kernel figures against the committed budget (profiles/budget.json), and what the driver exposes about the device
+            bkey = "C4" if args.config == "C4" and world == 1 else args.config
+            if not sharded and args.scale == 1.0 and not args.zipf:
+                measured = {"eval_kernel_us": dom["us"]}
+                if second_order:
+                    if newton_kernels:
+                        measured.update({"smooth_hess_us": newton_kernels["smooth_hess"] * 1e6, "smooth_us": newton_kernels["smooth"] * 1e6,
+                                         "factor_plus_backsolve_us": (newton_kernels["factor"] + newton_kernels["backsolve"]) * 1e6})
+                else:
+                    measured["iter_kernel_us_per_iteration"] = us_iter
+                    if "batched" in out:
+                        measured[f"batch{out['batched']['solves_per_batch']}_us_per_lockstep_iteration"] = out["batched"]["device_us_per_lockstep_iteration"]
+                out["budget"] = budget_check(bkey, measured)
+                out["budget_ok"] = out["budget"]["ok"] if out["budget"] else None
+            out["device_state"] = device_state()
+            if not sharded and not strong and not second_order:
+                # the same solve with the host-buffer hand-over inside the clock (never `value`): a fresh context, the pool columns
+                # uploaded from pageable NumPy buffers, utility, one cold solve, prices and psi read back -- through the raw
+                # C-ABI calls INTEGRATION.md's stub makes
+                from cfmm.problem import KIND2
+                u = cfmm.Arbitrage(net["c"])
+                rows = []
+                for _ in range(5):
+                    t0 = time.perf_counter()
+                    c2 = _lib.Context(net["n_tokens"], 0)
+                    for key, kind in KIND2.items():
+                        if key in net:
+                            b = net[key]
+                            c2.upload_pools2(kind, b["Ra"], b["Rb"], b["fee"], b["ia"], b["ib"], b.get("wa") if key == "w2" else b.get("alpha"))
+                    for k, b in net.get("gn", {}).items():
+                        c2.upload_poolsN(b["idx"], b["R"], b["w"], b["fee"])
+                    t1 = time.perf_counter()
+                    c2.set_utility(u.c, u.h, u.ctype); st2 = c2.solve(net["c"], tol=args.tol); c2.get_solution()
+                    t2 = time.perf_counter()
+                    rows.append((t2 - t0, t1 - t0, st2["evals"]))
+                    c2.close()
+                rows.sort()
+                tot, up, ev2 = rows[len(rows) // 2]
+                out["pcie_inclusive"] = {"value": ev2 * prob.m / tot, "unit": "pool-subproblems/s", "ms_total": 1e3 * tot, "ms_create_and_upload": 1e3 * up,
+                                         "upload_GBps": dom["bytes"] / up / 1e9, "evals": ev2,
+                                         "note": "median of 5: cfmm_create + cfmm_upload_* of the pool columns from pageable host buffers + "
+                                                 "cfmm_set_utility + one cold cfmm_solve + cfmm_get_solution"}
+            if not sharded and not args.no_cpu:
+                from oracle.c_oracle import Oracle
+                avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+                # calibrate the thread count on single dual evaluations (a cgroup quota can make "all logical
+                # CPUs" the slowest choice), then time full solves with the best one
+                best = None
+                for th in sorted({avail, max(1, avail // 2), max(1, avail // 4), min(avail, 64), min(avail, 32), min(avail, 16)}, reverse=True):
+                    o = Oracle(net["n_tokens"], threads=th)
+                    o.add_network(net); o.set_utility(net["c"])
                     o.eval(net["c"])
-                dt1 = (time.perf_counter() - t0) / 3
-                if best is None or dt1 < best[1]:
-                    best = (th, dt1, o)
-            cores, eval_s, o = best
-            if second_order:
-                # the CPU twin of this path is the first-order iteration (the oracle has no second-order method): dual
-                # evaluations of the same network at the same prices are what is comparable, timed for the same duration
-                t0 = time.perf_counter(); ce = 0
-                while time.perf_counter() - t0 < args.cpu_seconds:
-                    o.eval(net["prices"]); ce += 1
-                cdt = time.perf_counter() - t0
-                out["cpu_baseline"] = {"value": ce * prob.m / cdt, "unit": "pool-subproblems/s", "cores": cores, "kind": "port",
-                                       "measures": "dual EVALUATIONS only -- not solves to 1e-6 (the only CPU solve of this instance is the "
-                                                   "half-hour NumPy barrier-Newton run behind tests/golden/c5_liquidation.json)",
-                                       "sample": f"{ce} exact dual evaluations of the same {prob.m}-pool network by oracle/cfmm_oracle.c (OpenMP, {cores} "
-                                                 f"threads), {cdt:.1f} s: the oracle has no second-order method, and its first-order iteration needs "
-                                                 "thousands of evaluations on this instance (DESIGN.md); cvxpy is not installed in this image",
-                                       "single_evaluation_ms": eval_s * 1e3}
-                print(json.dumps(out))
-                if sharded:
-                    dist.barrier(); dist.destroy_process_group()
-                return
-            o.solve(net["c"], tol=args.tol)          # warm the OpenMP pool
-            t0 = time.perf_counter(); ce = 0; ns = 0
-            while ns < args.cpu_solves or time.perf_counter() - t0 < args.cpu_seconds:     # >= 10 s: past any cgroup burst allowance
-                r = o.solve(net["c"], tol=args.tol); ce += r["evals"]; ns += 1
-                if time.perf_counter() - t0 > 3 * args.cpu_seconds:
-                    break
-            cdt = time.perf_counter() - t0
-            out["cpu_baseline"] = {"value": ce * prob.m / cdt, "unit": "pool-subproblems/s", "cores": cores, "kind": "port",
-                                   "sample": f"{ns} full solves of the same {prob.m}-pool instance to the same tolerance by "
-                                             f"oracle/cfmm_oracle.c (OpenMP, {cores} threads: the fastest of the thread counts tried on "
-                                             f"the {avail} CPUs this process may use), {cdt:.1f} s; cvxpy (the reference's solver stack) "
-                                             "is not installed in this image",
-                                   "evals_per_solve": ce / ns, "objective": r["primal_value"],
-                                   "single_evaluation_ms": eval_s * 1e3}
-            if not getattr(args, "no_numpy", False) and not set(net) & {"curve2", "pow2", "gk", "sum2"} and prob.m <= 20_000_000:      # (~25 temporaries of 8 B per pool)
-                out["cpu_baseline"]["numpy_one_thread"] = numpy_one_thread(net)      # (baseline B of BASELINE.md section 4, beside baseline A above)
+                    t0 = time.perf_counter()
+                    for _ in range(3):
+                        o.eval(net["c"])
+                    dt1 = (time.perf_counter() - t0) / 3
+                    if best is None or dt1 < best[1]:
+                        best = (th, dt1, o)
+                cores, eval_s, o = best
+                if second_order:
+                    # the CPU twin of this path is the first-order iteration (the oracle has no second-order method): dual
+                    # evaluations of the same network at the same prices are what is comparable, timed for the same duration
+                    t0 = time.perf_counter(); ce = 0
+                    while time.perf_counter() - t0 < args.cpu_seconds:
+                        o.eval(net["prices"]); ce += 1
+                    cdt = time.perf_counter() - t0
+                    out["cpu_baseline"] = {"value": ce * prob.m / cdt, "unit": "pool-subproblems/s", "cores": cores, "kind": "port",
+                                           "measures": "dual EVALUATIONS only -- not solves to 1e-6 (the only CPU solve of this instance is the "
+                                                       "half-hour NumPy barrier-Newton run behind tests/golden/c5_liquidation.json)",
+                                           "sample": f"{ce} exact dual evaluations of the same {prob.m}-pool network by oracle/cfmm_oracle.c (OpenMP, {cores} "
+                                                     f"threads), {cdt:.1f} s: the oracle has no second-order method, and its first-order iteration needs "
+                                                     "thousands of evaluations on this instance (DESIGN.md); cvxpy is not installed in this image",
+                                           "single_evaluation_ms": eval_s * 1e3}
+                else:
+                    o.solve(net["c"], tol=args.tol)          # warm the OpenMP pool
+                    t0 = time.perf_counter(); ce = 0; ns = 0
+                    while ns < args.cpu_solves or time.perf_counter() - t0 < args.cpu_seconds:     # >= 10 s: past any cgroup burst allowance
+                        r = o.solve(net["c"], tol=args.tol); ce += r["evals"]; ns += 1
+                        if time.perf_counter() - t0 > 3 * args.cpu_seconds:
+                            break
+                    cdt = time.perf_counter() - t0
+                    out["cpu_baseline"] = {"value": ce * prob.m / cdt, "unit": "pool-subproblems/s", "cores": cores, "kind": "port",
+                                           "sample": f"{ns} full solves of the same {prob.m}-pool instance to the same tolerance by "
+                                                     f"oracle/cfmm_oracle.c (OpenMP, {cores} threads: the fastest of the thread counts tried on "
+                                                     f"the {avail} CPUs this process may use), {cdt:.1f} s; cvxpy (the reference's solver stack) "
+                                                     "is not installed in this image",
+                                           "evals_per_solve": ce / ns, "objective": r["primal_value"],
+                                           "single_evaluation_ms": eval_s * 1e3}
+                    if not getattr(args, "no_numpy", False) and not set(net) & {"curve2", "pow2", "gk", "sum2"} and prob.m <= 20_000_000:      # (~25 temporaries of 8 B per pool)
+                        out["cpu_baseline"]["numpy_one_thread"] = numpy_one_thread(net)      # (baseline B of BASELINE.md section 4, beside baseline A above)
         print(json.dumps(out))
     if sharded:
         dist.barrier()

@@ -1189,11 +1189,11 @@ def test_one_shot_all_reduce_against_rccl_on_real_peers(tmp_path):
 
 
 def test_bench_line_keeps_the_contract(tmp_path):
-    """`python bench.py` (N = 1, a short run): ONE JSON line with the contract's keys, BASELINE's metric and unit, the
+    """`python bench.py --full` (N = 1, a short run): ONE JSON line with the contract's keys, BASELINE's metric and unit, the
     roofline and CPU-baseline objects, and the extra figures (batched, PCIe-inclusive) beside -- not instead of -- `value`"""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--cpu-solves", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--cpu-solves", "1"],
                        capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1236,7 +1236,7 @@ def test_bench_line_keeps_the_contract(tmp_path):
     assert d["batched"]["solves_per_batch"] >= 2 and d["batched"]["value"] > 0.7 * d["value"]
     assert d["pcie_inclusive"]["value"] < d["value"]
     # the pool-sharded code path with a one-rank process group (what the driver's --gpus N > 1 runs per rank)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--force-dist", "--no-cpu"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--force-dist", "--no-cpu"],
                        capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
     d1 = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -1260,12 +1260,12 @@ def test_bench_lines_of_the_other_baseline_configs(tmp_path):
     here at a tenth of its size) and C5 (second-order path: the dominant kernel group is the dense factorisation, priced
     against the fp64 vector peak) beside the default C3"""
     base = json_load_baseline()
-    d2 = _bench_line(tmp_path, "--config", "C2", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-batch")
+    d2 = _bench_line(tmp_path, "--full", "--config", "C2", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-batch")
     assert d2["metric"] == base["metric"] and d2["config"]["workload"].startswith("C2:") and d2["config"]["pools_total"] == 10000
     assert d2["value"] > 1e8 and d2["roofline"]["bound"] in ("hbm", "valu") and d2["roofline"]["hbm_frac"] < 0.05
-    d4 = _bench_line(tmp_path, "--config", "C4", "--scale", "0.1", "--steps", "2", "--warmup", "1", "--no-cpu")
+    d4 = _bench_line(tmp_path, "--full", "--config", "C4", "--scale", "0.1", "--steps", "2", "--warmup", "1", "--no-cpu")
     assert d4["scaling"] == "strong" and d4["config"]["workload"].startswith("C4:") and d4["value"] > 2e9
-    d5 = _bench_line(tmp_path, "--config", "C5", "--steps", "1", "--warmup", "1", "--cpu-seconds", "1")
+    d5 = _bench_line(tmp_path, "--full", "--config", "C5", "--steps", "1", "--warmup", "1", "--cpu-seconds", "1")
     assert d5["config"]["workload"].startswith("C5:") and d5["config"]["pools_total"] == 550000 and d5["newton_steps_per_solve"] >= 3
     assert d5["gap"] <= 1e-6 and d5["infeas"] <= 1e-6
     rf = d5["roofline"]
@@ -1279,16 +1279,43 @@ def test_bench_multi_rank_path_end_to_end_on_one_gpu(tmp_path):
     """`bench.py --gpus 2 --share-gpu`: self-launch -> torch.distributed.run -> two ranks (processes on device 0, gloo + the
     hipIpc one-shot exchange, no RCCL) -> pool shards -> barrier-bracketed timing, max over ranks -> per-iteration split ->
     ONE JSON line from rank 0.  Everything the driver's N > 1 command runs except RCCL and the second device."""
-    d = _bench_line(tmp_path, "--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1", "--no-cpu", "--scale", "0.25")
+    d = _bench_line(tmp_path, "--full", "--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1", "--no-cpu", "--scale", "0.25")
     assert d["n_gpus"] == 2 and d["config"]["rccl_ranks"] == 2 and d["config"]["allreduce"] == "oneshot" and d["scaling"] == "weak"
     assert d["config"]["pools_total"] == 2 * d["config"]["pools_per_gpu"] and "--share-gpu" in d["config"]["workload"]
     assert d["per_iteration_us"]["allreduce"] > 0.0 and d["gap"] <= 1e-6 and d["infeas"] <= 1e-6
-    ds = _bench_line(tmp_path, "--gpus", "2", "--share-gpu", "--config", "C4", "--scale", "0.05", "--steps", "2", "--warmup", "1", "--no-cpu")
+    ds = _bench_line(tmp_path, "--full", "--gpus", "2", "--share-gpu", "--config", "C4", "--scale", "0.05", "--steps", "2", "--warmup", "1", "--no-cpu")
     assert ds["n_gpus"] == 2 and ds["scaling"] == "strong" and ds["config"]["pools_total"] == 500000 and ds["config"]["pools_per_gpu"] == 250000
     # four ranks (the one-shot exchange with four mailboxes per rank, rank-ordered sums): what the driver's --gpus 4 runs per rank
-    d4 = _bench_line(tmp_path, "--gpus", "4", "--share-gpu", "--steps", "2", "--warmup", "1", "--no-cpu", "--scale", "0.1")
+    d4 = _bench_line(tmp_path, "--full", "--gpus", "4", "--share-gpu", "--steps", "2", "--warmup", "1", "--no-cpu", "--scale", "0.1")
     assert d4["n_gpus"] == 4 and d4["config"]["rccl_ranks"] == 4 and d4["config"]["allreduce"] == "oneshot"
     assert d4["config"]["pools_total"] == 4 * d4["config"]["pools_per_gpu"] and d4["gap"] <= 1e-6 and d4["infeas"] <= 1e-6
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """`bench.py` without --full: the headline figures alone (nothing that takes a pass of its own), `--steps` timed steps, and
+    --dump-outputs: the last timed solve's objective, prices, net trade and trades as float64 arrays, consistent with each other
+    and with the line; a second run with the same arguments solves the same instance"""
+    lines = [_bench_line(tmp_path, "--config", "C2", "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path / d)) for d in ("a", "b")]
+    d = lines[0]
+    assert d["metric"] == json_load_baseline()["metric"] and d["unit"] == "pool-subproblems/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 4 and len(d["ms_per_step_blocks"]) == 4 and d["ms_per_step"] > 0.0 and d["gap"] <= 1e-6 and d["infeas"] <= 1e-6
+    work = d["evals_per_solve"] * d["config"]["pools_total"]
+    assert abs(d["ms_per_step"] * 1e-3 * d["value"] - work) <= 1e-6 * work
+    assert not set(d) & {"roofline", "per_iteration_us", "cpu_baseline", "batched", "pcie_inclusive", "budget", "device_state"}, sorted(d)
+    names = {"objective", "nu", "psi", "trades_cp2_delta", "trades_cp2_lambda"}
+    out = [{f[:-4]: np.load(tmp_path / r / f) for f in os.listdir(tmp_path / r)} for r in ("a", "b")]
+    assert set(out[0]) == set(out[1]) == names
+    assert all(a.dtype == np.float64 for a in out[0].values()) and sum(a.nbytes for a in out[0].values()) <= 64 << 20
+    net = synthetic.config("C2", seed=0)
+    n, b = net["n_tokens"], net["cp2"]
+    o = out[0]
+    assert o["objective"][0] == d["objective"] and o["nu"].shape == o["psi"].shape == (n,)
+    assert o["trades_cp2_delta"].shape == o["trades_cp2_lambda"].shape == (2, len(b["Ra"]))
+    y = o["trades_cp2_lambda"] - o["trades_cp2_delta"]
+    psi = np.bincount(b["ia"], weights=y[0], minlength=n) + np.bincount(b["ib"], weights=y[1], minlength=n)
+    assert np.abs(psi - o["psi"]).max() <= 1e-9 * max(1.0, np.abs(psi).max())
+    assert abs(net["c"] @ o["psi"] - o["objective"][0]) <= 1e-9 * abs(o["objective"][0])
+    assert abs(out[1]["objective"][0] - o["objective"][0]) <= 2e-6 * abs(o["objective"][0])
 
 
 def json_load_baseline():

@@ -149,6 +149,38 @@ def test_product_fails_loudly_without_gpu():
         p.solve()
 
 
+def test_bench_dump_outputs_samples_large_trade_sets(tmp_path):
+    """bench.py --dump-outputs: float64 files; trade sets past the budget keep the same fraction of every bucket's pools, a seeded
+    sample in pool order that two dumps share; trade sets inside the budget are written whole"""
+    import types
+    import bench
+    rng = np.random.default_rng(5)
+    trades = {"cp2": (rng.random((2, 300_000)), rng.random((2, 300_000))), 3: (rng.random((3, 50_000)), rng.random((3, 50_000))),
+              ("sum", 4): (rng.random((4, 20_000)), rng.random((4, 20_000)))}
+    prob = types.SimpleNamespace(value=2.5, dual_value=2.5000001, nu=rng.random(7), psi=rng.random(7).astype(np.float32), _trades=lambda: trades)
+    budget = 4 << 20
+    got = []
+    for run in ("a", "b"):
+        names = bench.dump_outputs(prob, str(tmp_path / run), budget=budget)
+        got.append({k: np.load(tmp_path / run / (k + ".npy")) for k in names})
+    assert set(got[0]) == {"objective", "nu", "psi"} | {f"trades_{b}_{w}" for b in ("cp2", "gn3", "gk_sum4") for w in ("delta", "lambda")}
+    assert all(a.dtype == np.float64 for a in got[0].values())
+    assert all(np.array_equal(got[0][k], got[1][k]) for k in got[0])
+    assert got[0]["objective"].tolist() == [2.5, 2.5000001] and np.array_equal(got[0]["psi"], prob.psi.astype(np.float64))
+    assert sum(a.nbytes for k, a in got[0].items() if k.startswith("trades_")) <= budget
+    frac = budget / sum(d.nbytes + l.nbytes for d, l in trades.values())
+    for key, name in (("cp2", "cp2"), (3, "gn3"), (("sum", 4), "gk_sum4")):
+        d, l = trades[key]
+        sd, sl = got[0][f"trades_{name}_delta"], got[0][f"trades_{name}_lambda"]
+        assert sd.shape == sl.shape == (d.shape[0], int(frac * d.shape[1]))
+        pos = np.searchsorted(d[0], sd[0], sorter=np.argsort(d[0]))
+        idx = np.argsort(d[0])[pos]                     # (random columns: row 0 identifies a pool)
+        assert np.all(np.diff(idx) > 0) and np.array_equal(d[:, idx], sd) and np.array_equal(l[:, idx], sl)
+    whole = bench.dump_outputs(prob, str(tmp_path / "c"))
+    assert all(np.array_equal(np.load(tmp_path / "c" / f"trades_cp2_{w}.npy"), a) for w, a in zip(("delta", "lambda"), trades["cp2"]))
+    assert len(whole) == len(got[0])
+
+
 def test_bench_self_launches_one_rank_per_gpu(tmp_path):
     """`python bench.py --gpus N` (the driver's command, no launcher around it) must start N ranks itself; without
     GPUs every rank then refuses loudly instead of falling back to anything"""

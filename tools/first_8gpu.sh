@@ -38,7 +38,7 @@ for cfg in C3 C4; do
       extra="--no-cpu --no-batch --steps 10 --warmup 3"
       [ "$n" -gt 1 ] && extra="$extra --allreduce $ar $SHARE"
       [ -n "$SHARE" ] && [ "$cfg" = C4 ] && extra="$extra --scale 0.25"       # (two ranks time-share one device: a quarter of the pools)
-      timeout 1500 python bench.py --gpus $n --config $cfg $extra > $f 2> ${f%.json}.err
+      timeout 1500 python bench.py --full --gpus $n --config $cfg $extra > $f 2> ${f%.json}.err
       echo "bench $cfg --gpus $n --allreduce $ar: rc=$?"
     done
   done

@@ -10,13 +10,13 @@ if [ "$1" != quick ]; then
 echo "== gpu tests"; timeout 1500 python -m pytest tests -m gpu -q > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -4 $O/pytest.log
 fi
 for c in C3 C2 C4 C5 C4x4; do
-  echo "== bench $c"; timeout 1200 python bench.py --config $c --cpu-seconds 8 > $O/bench_$c.json 2> $O/bench_$c.err; echo "bench rc=$?"; cut -c1-400 $O/bench_$c.json
+  echo "== bench $c"; timeout 1200 python bench.py --full --config $c --cpu-seconds 8 > $O/bench_$c.json 2> $O/bench_$c.err; echo "bench rc=$?"; cut -c1-400 $O/bench_$c.json
 done
-echo "== bench C3, Zipf(1.1) token pairs"; timeout 900 python bench.py --config C3 --zipf 1.1 --no-cpu --no-batch > $O/bench_C3zipf.json 2> $O/bench_C3zipf.err; echo "rc=$?"; cut -c1-300 $O/bench_C3zipf.json
+echo "== bench C3, Zipf(1.1) token pairs"; timeout 900 python bench.py --full --config C3 --zipf 1.1 --no-cpu --no-batch > $O/bench_C3zipf.json 2> $O/bench_C3zipf.err; echo "rc=$?"; cut -c1-300 $O/bench_C3zipf.json
 cp $O/bench_C3.json $O/bench.json
 if [ "$1" != quick ]; then
-echo "== bench (pool-sharded path, one rank)"; timeout 900 python bench.py --force-dist --no-cpu > $O/bench_dist1.json 2> $O/bench_dist1.err; echo "rc=$?"
-echo "== bench (two ranks sharing the GPU, one-shot exchange)"; timeout 900 python bench.py --gpus 2 --share-gpu --no-cpu > $O/bench_share2.json 2> $O/bench_share2.err; echo "rc=$?"; cut -c1-300 $O/bench_share2.json
+echo "== bench (pool-sharded path, one rank)"; timeout 900 python bench.py --full --force-dist --no-cpu > $O/bench_dist1.json 2> $O/bench_dist1.err; echo "rc=$?"
+echo "== bench (two ranks sharing the GPU, one-shot exchange)"; timeout 900 python bench.py --full --gpus 2 --share-gpu --no-cpu > $O/bench_share2.json 2> $O/bench_share2.err; echo "rc=$?"; cut -c1-300 $O/bench_share2.json
 echo "== upload"; timeout 300 python tools/upload_timing.py > $O/upload.json 2> $O/upload.err; cat $O/upload.json
 echo "== small networks"; timeout 300 python tools/small_timing.py > $O/small.json 2> $O/small.err; cut -c1-600 $O/small.json
 echo "== batched solves"; for c in C3 C4shard; do timeout 600 python tools/batch_timing.py --config $c > $O/batch_$c.jsonl 2> $O/batch_$c.err; cut -c1-300 $O/batch_$c.jsonl; done
@@ -26,7 +26,7 @@ echo "== host share of a solve"; timeout 300 python tools/host_overhead.py 2> $O
 fi
 cd /tmp
 echo "== kernel trace of bench.py"
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_bench -o t -- python $R/bench.py --steps 5 --warmup 2 --no-cpu > $O/trace_bench.log 2>&1; echo "rc=$?"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_bench -o t -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu > $O/trace_bench.log 2>&1; echo "rc=$?"
 echo "== kernel trace of the K-asset table's launch and of the utility-table solve"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_table -o t -- python $R/tools/profile_table.py > $O/trace_table.log 2>&1; echo "rc=$?"; tail -1 $O/trace_table.log | cut -c1-300
 CFMM_TABLE_WARM=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_tablecold -o t -- python $R/tools/profile_table.py > $O/trace_tablecold.log 2>&1; echo "rc=$?"; tail -1 $O/trace_tablecold.log | cut -c1-300
