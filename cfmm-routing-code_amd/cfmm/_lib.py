@@ -61,7 +61,7 @@ assert _STATS_STRUCT.size == C.sizeof(Stats)
 
 def build(force=False):
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp")]
+    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp", "update.hpp")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "cfmm.h"))
     if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _CSRC, "-s"])
@@ -71,7 +71,7 @@ def build(force=False):
 _lib = None
 
 SYMBOLS = ["cfmm_create", "cfmm_clone", "cfmm_destroy", "cfmm_last_error", "cfmm_backend", "cfmm_default_opts",
-           "cfmm_upload_pools2", "cfmm_upload_poolsN", "cfmm_upload_poolsG", "cfmm_set_pool_flags", "cfmm_set_pool_flagsG", "cfmm_set_utility",
+           "cfmm_upload_pools2", "cfmm_upload_poolsN", "cfmm_upload_poolsG", "cfmm_update_pools2", "cfmm_update_poolsN", "cfmm_update_poolsG", "cfmm_set_pool_flags", "cfmm_set_pool_flagsG", "cfmm_set_utility",
            "cfmm_set_ties", "cfmm_set_deterministic", "cfmm_debug_eval_limbs", "cfmm_eval_dual", "cfmm_eval_smooth", "cfmm_debug_cholesky", "cfmm_debug_cholesky_apply", "cfmm_time_xcd_handoff", "cfmm_solve", "cfmm_solve_batch", "cfmm_batch_capacity", "cfmm_solve_sweep", "cfmm_get_nu", "cfmm_set_nu", "cfmm_get_psi",
            "cfmm_get_solution", "cfmm_get_trades2", "cfmm_get_tradesN", "cfmm_get_tradesG", "cfmm_comm_unique_id", "cfmm_comm_init",
            "cfmm_oneshot_export", "cfmm_oneshot_import", "cfmm_oneshot_attach", "cfmm_oneshot_mailbox", "cfmm_oneshot_enable",
@@ -97,6 +97,9 @@ def lib():
     L.cfmm_upload_pools2.argtypes = [vp, C.c_int, C.c_int64, dp, dp, dp, dp, ip, ip]
     L.cfmm_upload_poolsN.argtypes = [vp, C.c_int, C.c_int64, ip, dp, dp, dp]
     L.cfmm_upload_poolsG.argtypes = [vp, C.c_int, C.c_int, C.c_int64, ip, dp, dp, dp]
+    L.cfmm_update_pools2.argtypes = [vp, C.c_int, C.c_int64, ip, dp, dp, dp]
+    L.cfmm_update_poolsN.argtypes = [vp, C.c_int, C.c_int64, ip, dp]
+    L.cfmm_update_poolsG.argtypes = [vp, C.c_int, C.c_int, C.c_int64, ip, dp, dp]
     L.cfmm_set_pool_flags.argtypes = [vp, C.c_int, ip]
     L.cfmm_set_pool_flagsG.argtypes = [vp, C.c_int, ip]
     L.cfmm_set_utility.argtypes = [vp, dp, dp, ip]
@@ -224,6 +227,30 @@ class Context:
         param = None if param is None else f64(param)
         k, m = R.shape
         self._chk(self.L.cfmm_upload_poolsG(self.h, kind, k, m, _i(idx), _d(R), _d(fee), _d(param) if param is not None else None))
+
+    def update_pools2(self, kind, pos, Ra, Rb, param=None):
+        """new reserves (and parameter, None = unchanged) of the pools `pos` (upload order) of a two-asset bucket, in place"""
+        pos, Ra, Rb, param = i32(pos), f64(Ra), f64(Rb), f64(param)
+        if len(Ra) != len(pos) or len(Rb) != len(pos) or (param is not None and len(param) != len(pos)):
+            raise CfmmError(f"update_pools2: {len(pos)} positions but columns of {len(Ra)}, {len(Rb)}"
+                            + ("" if param is None else f", {len(param)}") + " entries")
+        self._chk(self.L.cfmm_update_pools2(self.h, kind, len(pos), _i(pos), _d(Ra), _d(Rb), _d(param)))
+
+    def update_poolsN(self, pos, R):
+        """new reserves R [k][count] of the pools `pos` of the geo-mean bucket of k assets, in place"""
+        pos, R = i32(pos), f64(R)
+        k, cnt = R.shape
+        if cnt != len(pos):
+            raise CfmmError(f"update_poolsN: {len(pos)} positions but {cnt} reserve columns")
+        self._chk(self.L.cfmm_update_poolsN(self.h, k, cnt, _i(pos), _d(R)))
+
+    def update_poolsG(self, kind, pos, R, param=None):
+        """new reserves R [k][count] (and alpha of stableswap pools, None = unchanged) of the pools `pos` of a K-asset table bucket, in place"""
+        pos, R, param = i32(pos), f64(R), f64(param)
+        k, cnt = R.shape
+        if cnt != len(pos) or (param is not None and len(param) != cnt):
+            raise CfmmError(f"update_poolsG: {len(pos)} positions but {cnt} reserve columns" + ("" if param is None else f", {len(param)} parameters"))
+        self._chk(self.L.cfmm_update_poolsG(self.h, kind, k, cnt, _i(pos), _d(R), _d(param)))
 
     def set_pool_flags(self, kind, flags):
         flags = i32(flags)

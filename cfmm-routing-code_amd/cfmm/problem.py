@@ -188,11 +188,105 @@ def pack(n_tokens, local_indices, reserves, fees, kinds=None, weights=None, para
     return net, where
 
 
+def _param_rule(kind_key, i, x):
+    """the parameter rule of pack() for a bucket whose pools carry one (None: fine), with pack's message"""
+    if kind_key in ("curve2", "stable"):
+        if x is None or not (float(x) > 0):
+            return f"pool {i}: curve pools need params[i] = alpha > 0"
+    elif kind_key == "pow2":
+        if x is None or not (1e-3 <= float(x) <= 0.999):
+            return f"pool {i}: power-sum pools are two-asset and need params[i] = t in [0.001, 0.999]"
+    elif x is not None:
+        return f"pool {i}: this kind of pool has no parameter to update"
+    return None
+
+
+def route_updates(net, where, pools, reserves, params=None):
+    """New reserves of some pools of a packed network, routed to their buckets: `pools` are indices into the reference's pool
+    list (arbitrage.py:6-28 order, `where` as pack() returned it), reserves[i] the new reserve vector of pools[i], params[i] (or
+    params None) the new alpha / t of a curve / power-sum pool (None: unchanged).  Checks lengths, positivity, parameters (with
+    pack's messages), range and duplicates; raises ValueError.  Returns {bucket key: (positions int32[count], R [k][count],
+    param [count] or None)} with slot-major R, positions ascending, the key as bucket_trades takes it ('cp2'..'pow2', a size k,
+    ('stable' | 'sum', k)).  An entry without a new parameter in a bucket where another entry has one keeps its current value."""
+    pools = [int(i) for i in pools]
+    if len(reserves) != len(pools):
+        raise ValueError(f"{len(pools)} pools but {len(reserves)} reserve vectors")
+    if params is not None and len(params) != len(pools):
+        raise ValueError(f"{len(pools)} pools but {len(params)} parameters")
+    if len(set(pools)) != len(pools):
+        raise ValueError("a pool is named twice")
+    rows = {}
+    for e, i in enumerate(pools):
+        if not 0 <= i < len(where):
+            raise ValueError(f"pool {i}: outside [0, {len(where)})")
+        key, pos = where[i]
+        R = np.asarray(reserves[e], dtype=np.float64).ravel()
+        k = key if isinstance(key, int) else (key[1] if isinstance(key, tuple) else 2)
+        if len(R) != k:
+            raise ValueError(f"pool {i}: {k} indices but {len(R)} reserves")
+        if not np.all(np.isfinite(R)) or not np.all(R > 0):
+            raise ValueError(f"pool {i}: reserves must be > 0 and finite")
+        x = None if params is None else params[e]
+        msg = _param_rule(key[0] if isinstance(key, tuple) else key, i, x) if x is not None else None
+        if msg:
+            raise ValueError(msg)
+        rows.setdefault(key, []).append((pos, R, None if x is None else float(x)))
+    out = {}
+    for key, rr in rows.items():
+        rr.sort(key=lambda r: r[0])
+        pos = np.array([r[0] for r in rr], dtype=np.int32)
+        R = np.array([r[1] for r in rr], dtype=np.float64).T.copy()
+        param = None
+        if any(r[2] is not None for r in rr):
+            cur = _bucket_param(net, key)
+            param = np.array([cur[r[0]] if r[2] is None else r[2] for r in rr], dtype=np.float64)
+        out[key] = (pos, R, param)
+    return out
+
+
+def _bucket_of(net, key):
+    """(bucket dict, 'two' | 'gn' | 'gk') of a bucket key as bucket_trades takes it"""
+    if isinstance(key, str):
+        if key not in KIND2 or key not in net:
+            raise ValueError(f"no bucket {key!r} in this network")
+        return net[key], "two"
+    if isinstance(key, tuple):
+        if key not in net.get("gk", {}):
+            raise ValueError(f"no bucket {key!r} in this network")
+        return net["gk"][key], "gk"
+    if int(key) not in net.get("gn", {}):
+        raise ValueError(f"no bucket {key!r} in this network")
+    return net["gn"][int(key)], "gn"
+
+
+def _bucket_param(net, key):
+    b, fam = _bucket_of(net, key)
+    if fam == "two":
+        return b[PARAM2[key]] if PARAM2[key] else None
+    return b["param"] if fam == "gk" and key[0] == "stable" else None
+
+
 def network_pool_count(net):
     m = sum(len(net[k]["Ra"]) for k in KIND2 if k in net)
     m += sum(b["R"].shape[1] for b in net.get("gn", {}).values())
     m += sum(b["R"].shape[1] for b in net.get("gk", {}).values())
     return m
+
+
+def shard_range(m, rank, world):
+    """the contiguous slice [lo, hi) of a bucket of m pools that rank `rank` of `world` holds (shard_network)"""
+    return (m * rank) // world, (m * (rank + 1)) // world
+
+
+def shard_updates(m, rank, world, positions, R, param=None):
+    """The entries of a bucket update given in GLOBAL positions (over all m pools of the bucket) that fall in this rank's slice,
+    with positions local to it: what a pool-sharded Problem's update_bucket takes on each rank.  Every rank calls update_bucket
+    with its part, an empty one included.  Returns (positions, R [k][count], param or None)."""
+    lo, hi = shard_range(m, rank, world)
+    pos = np.asarray(positions, dtype=np.int64).ravel()
+    sel = (pos >= lo) & (pos < hi)
+    R = np.asarray(R, dtype=np.float64)
+    return pos[sel] - lo, R[:, sel], (None if param is None else np.asarray(param, dtype=np.float64)[sel])
 
 
 def shard_network(net, rank, world):
@@ -201,9 +295,7 @@ def shard_network(net, rank, world):
     out = {k: v for k, v in net.items() if k not in KIND2 and k not in ("gn", "gk") and not str(k).startswith("_")}      # (not the per-network caches: _price_relations, _potentials)
 
     def sl(m):
-        lo = (m * rank) // world
-        hi = (m * (rank + 1)) // world
-        return slice(lo, hi)
+        return slice(*shard_range(m, rank, world))
     for key in KIND2:
         if key in net:
             b = net[key]; s = sl(len(b["Ra"]))
@@ -260,11 +352,12 @@ def start_prices(net, util):
     if known is None:
         known = c > 0
     memo = getattr(util, "_start_memo", None)
-    if memo is not None and memo[0] is net and np.array_equal(memo[1], c):
+    gen = net.get("_generation", 0)              # (Problem.update_bucket: the reserves the guess was propagated through changed)
+    if memo is not None and memo[0] is net and memo[3] == gen and np.array_equal(memo[1], c):
         return memo[2].copy()
     out = _propagate_prices(net, c, known)
     try:
-        util._start_memo = (net, c.copy(), out.copy())
+        util._start_memo = (net, c.copy(), out.copy(), gen)
     except AttributeError:
         pass
     return out
@@ -794,6 +887,86 @@ class Problem:
     def eval_dual(self, nu, want_diag=False):
         return self._ensure_ctx().eval_dual(nu, want_diag)
 
+    # -- in-place updates (include/cfmm.h: cfmm_update_pools*) ---------------------------------
+    def update_reserves(self, pools, reserves, params=None):
+        """New reserves of some pools, written into the resident columns in place (nothing else is uploaded again): `pools` index the
+        pool list the Problem was built from, reserves[i] is the new reserve vector of pools[i], params[i] the new alpha / t of a
+        curve / power-sum pool (None: unchanged).  Fees, weights and token ids stay (changing them is a new Problem).  The per-block loop
+        of a router:
+
+            p.solve()
+            for block in blocks:
+                p.update_reserves(block.pools, block.reserves)
+                p.solve(warm_start=True)          # from the prices of the previous block
+        """
+        if self.where is None:
+            raise CfmmError("update_reserves needs a Problem built from pool lists; use update_bucket()")
+        for key, (pos, R, param) in route_updates(self.net, self.where, pools, reserves, params).items():
+            self.update_bucket(key, pos, R, param)
+
+    def update_bucket(self, key, positions, R, param=None):
+        """New reserves R ([k][count], slot-major; k = 2 for the two-asset buckets) of the pools `positions` of one bucket (`key` as
+        bucket_trades takes it: 'cp2' .. 'pow2', a size k, ('stable' | 'sum', k)), and of its parameter where it has one (None:
+        unchanged), in place on the device and in self.net (shared with this Problem's clones, which notice the change too).  A
+        pool-sharded Problem takes positions local to its rank's shard, and every rank makes the call for every bucket any rank updates
+        (empty `positions` where its slice is untouched): shard_updates(m, rank, world, global_positions, R, param) picks a rank's part
+        of an update given over the whole bucket of m pools."""
+        b, fam = _bucket_of(self.net, key)
+        pos = np.ascontiguousarray(positions, dtype=np.int64).ravel()
+        m = len(b["Ra"]) if fam == "two" else b["R"].shape[1]
+        k = 2 if fam == "two" else b["R"].shape[0]
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        if R.ndim == 1 and len(pos) == 0:
+            R = R.reshape(k, 0)
+        if R.shape != (k, len(pos)):
+            raise ValueError(f"bucket {key!r}: reserves of shape {R.shape}, expected ({k}, {len(pos)})")
+        if len(pos) and (pos.min() < 0 or pos.max() >= m):
+            raise ValueError(f"bucket {key!r}: a position outside [0, {m})")
+        if len(np.unique(pos)) != len(pos):
+            raise ValueError(f"bucket {key!r}: a position is named twice")
+        if not np.all(np.isfinite(R)) or not np.all(R > 0):
+            raise ValueError(f"bucket {key!r}: reserves must be > 0 and finite")
+        cur = _bucket_param(self.net, key)
+        if param is not None:
+            param = np.ascontiguousarray(param, dtype=np.float64).ravel()
+            if cur is None or (fam == "two" and key == "w2"):
+                raise ValueError(f"bucket {key!r}: no parameter to update")
+            if len(param) != len(pos):
+                raise ValueError(f"bucket {key!r}: {len(pos)} positions but {len(param)} parameters")
+            for i, x in zip(pos, param):
+                msg = _param_rule(key[0] if isinstance(key, tuple) else key, int(i), x)
+                if msg:
+                    raise ValueError(msg)
+        if self.ctx is not None and self._uploaded:
+            p32 = pos.astype(np.int32)
+            if fam == "two":
+                self.ctx.update_pools2(KIND2[key], p32, R[0], R[1], param)
+            elif fam == "gn":
+                self.ctx.update_poolsN(p32, R)
+            else:
+                self.ctx.update_poolsG(_lib.POOLK[key[0]], p32, R, param)
+        if fam == "two":
+            b["Ra"][pos] = R[0]; b["Rb"][pos] = R[1]
+        else:
+            b["R"][:, pos] = R
+        if param is not None:
+            cur[pos] = param
+        # what was derived from the old reserves: start-price relations (and the start prices memoised on them), the largest reserve,
+        # the read-back caches -- of this Problem and of its clones, through the generation stamp on the network they share
+        for kk in ("_price_relations", "_potentials"):
+            self.net.pop(kk, None)
+        self.net["_generation"] = self.net.get("_generation", 0) + 1
+        self._pools_seen()
+
+    def _pools_seen(self):
+        """drop what was derived from reserves that an update through this Problem or a clone (they share self.net) has replaced"""
+        g = self.net.get("_generation", 0)
+        if getattr(self, "_net_generation", 0) != g:
+            self._net_generation = g
+            self._rmax = None
+            self._theta = {}
+            self._trade_cache = None
+
     # -- solve -------------------------------------------------------------------------------
     def solve(self, tol=1e-6, nu0=None, max_evals=2000, memory=0, iters_per_graph=8, kink_tol=1e-3,
               max_rounds=6, warm_start=False, method="auto"):
@@ -1305,6 +1478,7 @@ class Problem:
 
     def _max_reserve(self):
         """largest reserve of the network (all ranks of a pool-sharded problem: the floor of a relative figure must not differ between them)"""
+        self._pools_seen()
         mr = getattr(self, "_rmax", None)
         if mr is None:
             mr = 0.0
@@ -1493,6 +1667,7 @@ class Problem:
 
     # -- result read-back (arbitrage.py:84, two-asset.py:94-100) --------------------------------
     def _trades(self):
+        self._pools_seen()
         if self._trade_cache is None:
             ctx = self._ensure_ctx()
             tr = {}

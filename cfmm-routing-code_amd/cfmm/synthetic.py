@@ -198,3 +198,48 @@ def config(name, seed=0, scale=1.0, pool_seed=None, zipf_s=None):
     if name == "C5":      # 5e5 Curve pools + basket liquidation
         return make_network(1000, m_cp2=s(50_000), m_curve2=s(500_000), seed=seed)
     raise ValueError(name)
+
+
+def copy_network(net):
+    """a deep copy of a network's arrays (without the per-network caches under private keys)"""
+    out = {}
+    for k, v in net.items():
+        if str(k).startswith("_"):
+            continue
+        if isinstance(v, dict):
+            out[k] = {kk: ({c: np.array(a, copy=True) for c, a in vv.items()} if isinstance(vv, dict) else np.array(vv, copy=True))
+                      for kk, vv in v.items()}
+        else:
+            out[k] = v.copy() if isinstance(v, np.ndarray) else v
+    return out
+
+
+def swap_block(net, frac, seed=0):
+    """One block of swaps over a network of constant-product, weighted and geo-mean pools: `frac` of every bucket's pools each
+    trade a random amount (0.1 .. 5 % of the input reserve) between two of their tokens at their fee, along their own trading
+    function, so phi(R') >= phi(R).  Returns (the network after the block, {bucket key: (positions, R [k][count])}) -- what
+    Problem.update_bucket takes."""
+    rng = np.random.default_rng(seed)
+    after = copy_network(net)
+    changes = {}
+    cols = [(key, net[key]) for key in ("cp2", "w2") if key in net] + list(net.get("gn", {}).items())
+    for key, b in cols:
+        two = isinstance(key, str)
+        R = np.stack([b["Ra"], b["Rb"]]) if two else b["R"]
+        k, m = R.shape
+        pos = np.sort(rng.choice(m, max(1, int(frac * m)), replace=False))
+        w = (np.stack([b["wa"], 1.0 - b["wa"]]) if key == "w2" else np.full((2, m), 0.5)) if two else b["w"]
+        i_in = rng.integers(0, k, len(pos))
+        i_out = (i_in + rng.integers(1, k, len(pos))) % k
+        c = np.arange(len(pos))
+        newR = R[:, pos].copy()
+        x, y = newR[i_in, c], newR[i_out, c]
+        d = x * rng.uniform(1e-3, 0.05, len(pos))
+        newR[i_out, c] = y * (x / (x + b["fee"][pos] * d)) ** (w[i_in, pos] / w[i_out, pos])
+        newR[i_in, c] = x + d
+        changes[key] = (pos, newR)
+        if two:
+            after[key]["Ra"][pos] = newR[0]; after[key]["Rb"][pos] = newR[1]
+        else:
+            after["gn"][key]["R"][:, pos] = newR
+    return after, changes

@@ -37,6 +37,7 @@
 #include "chol.hpp"
 #include "chol2.hpp"
 #include "phik.hpp"
+#include "update.hpp"
 #include "handoff.hpp"
 
 using namespace cfmm;
@@ -103,8 +104,25 @@ struct PoolStore {
     // different host threads (Problem.solve_many): `mu` guards landed and the pending flags ro2 / ron.
     std::vector<std::pair<void *, hipStream_t>> landed;
     std::mutex mu;
+    // in-place updates of the reserves (update.hpp: cfmm_update_pools*).  `gen` counts them; every context remembers the generation it
+    // last saw and drops what it derived from the old reserves when it meets a newer one (pools_seen).  `readers`: contexts inside a
+    // solve / evaluation / batch right now (an update is refused meanwhile); `sharers`: every context on this store (an update orders
+    // its writes behind the work each has enqueued).  Both under `mu`.
+    std::atomic<unsigned long long> gen{0};
+    int readers = 0;
+    std::vector<cfmm_ctx *> sharers;
+    int *inv2[CFMM_POOL_KINDS2] = {};              // inverse of a permuted bucket's perm (caller index -> position), built at its first update
+    int *invn[CFMM_MAX_POOL_SIZE + 1] = {};
+    std::vector<unsigned long long> dup_bits;      // scratch of the updates' duplicate check (one bit per pool of the largest bucket), all zero between calls
+    // host copy of the constant-sum bucket's columns as uploaded and updated (small buckets only): the host half of the library's own
+    // active-set loop over their kinks reads them (cfmm_solve with CFMM_METHOD_AUTO on networks cfmm_solve_sweep serves; round 6).  Only the
+    // context that uploaded the pools uses it (cfmm_ctx::is_clone)
+    std::vector<int32_t> hs_ia, hs_ib;
+    std::vector<double> hs_fee, hs_Ra, hs_Rb;
     ~PoolStore()
     {
+        for (int *q : inv2) if (q) (void)hipFree(q);
+        for (int *q : invn) if (q) (void)hipFree(q);
         for (auto &q : landed) (void)hipFree(q.first);
         for (void *q : b2mem) if (q) (void)hipFree(q);
         for (void *q : c2mem) if (q) (void)hipFree(q);
@@ -123,10 +141,11 @@ struct cfmm_ctx {
     // pools (shared with clones); the tied-pool flags of the constant-sum bucket are per context
     std::shared_ptr<PoolStore> pools = std::make_shared<PoolStore>();
     int *flags2 = nullptr;
-    // host copy of the constant-sum bucket's columns as uploaded (small buckets only): the host half of the library's own active-set loop
-    // over their kinks reads them (cfmm_solve with CFMM_METHOD_AUTO on networks cfmm_solve_sweep serves; round 6)
-    std::vector<int32_t> hs_ia, hs_ib;
-    std::vector<double> hs_fee, hs_Ra, hs_Rb;
+    bool is_clone = false;             // made by cfmm_clone (does not run the library's own kink loop: PoolStore::hs_*)
+    unsigned long long pool_gen = 0;   // PoolStore::gen as this context last saw it (pools_seen)
+    hipEvent_t ev_pool = nullptr;      // recorded on this context's stream by an update made through another context sharing the store
+    char *upd_dev = nullptr; size_t upd_cap = 0;       // grow-only device copy of an update's records (cfmm_update_pools*)
+    unsigned long long *upd_host = nullptr;            // pinned: the update's `lowered` flag and bucket maximum read back
     // tenders as that loop left them (cfmm_solve_sweep's `trades` layout, the tied pools' fills folded in): what cfmm_get_trades2 / N
     // return until the prices change again
     std::vector<double> tr_ovr;
@@ -695,7 +714,33 @@ void pools_changed(cfmm_ctx *ctx)
     local_extrema(ctx);
     ctx->g_valid = false; ctx->g_counts_valid = false; ctx->listed_valid = false;
     ctx->hsol_valid = false; ctx->mu_last = 0.0; ctx->warm_mu = 0.0; ctx->slo_active = false; ctx->tr_ovr_valid = false;
+    ctx->pool_gen = ctx->pools->gen.load(std::memory_order_acquire);
 }
+
+// On entry to every call that reads the pools: has some context sharing them updated reserves in place (cfmm_update_pools*) since this
+// one last looked?  Then what was derived from the old reserves goes -- the largest reserve (the reproducible mode's exponent; re-reduced
+// over the ranks when pool-sharded), the cached solution, the kink loop's tenders, the barrier warm start and the captured launches (they
+// carry the exponent) -- while the prices, the utility, the ties and the tie flags stay: a solve from NULL continues from the accepted
+// prices.  One integer compare when nothing changed.
+void pools_seen(cfmm_ctx *ctx)
+{
+    const unsigned long long g = ctx->pools->gen.load(std::memory_order_acquire);
+    if (g == ctx->pool_gen) return;
+    ctx->pool_gen = g;
+    local_extrema(ctx);
+    ctx->g_valid = false; ctx->g_counts_valid = false;
+    ctx->hsol_valid = false; ctx->tr_ovr_valid = false;
+    ctx->warm_mu = 0.0; ctx->mu_last = 0.0; ctx->slo_active = false;
+    for (int k = 0; k < CFMM_POOL_KINDS2; ++k)
+        if (ctx->sm_ws[k]) (void)hipMemsetAsync(ctx->sm_ws[k], 0, 2 * (size_t)ctx->sm_ws_m[k] * sizeof(double), ctx->stream);
+}
+
+// a solve, evaluation or batch in progress on a context of this store: an update through another context is refused meanwhile
+struct PoolReader {
+    PoolStore &ps;
+    explicit PoolReader(cfmm_ctx *ctx) : ps(*ctx->pools) { std::lock_guard<std::mutex> g(ps.mu); ++ps.readers; }
+    ~PoolReader() { std::lock_guard<std::mutex> g(ps.mu); --ps.readers; }
+};
 
 // dma: the staged tile walk (kernels.hpp) -- one 4 KB slot per wave on top
 size_t eval_lds_bytes(int n, bool with_d, bool det = false, bool dma = false)
@@ -2203,6 +2248,8 @@ int cfmm_create(int device, int n_tokens, cfmm_ctx **out)
     for (int i = 0; i < 2; ++i) TRY_C(hipEventCreateWithFlags(&ctx->ev[i], hipEventDisableTiming));
     TRY_C(hipEventCreate(&ctx->ev_t0));
     TRY_C(hipEventCreate(&ctx->ev_t1));
+    TRY_C(hipEventCreateWithFlags(&ctx->ev_pool, hipEventDisableTiming));
+    ctx->pools->sharers.push_back(ctx);            // (a fresh store: nobody else holds it yet)
     if (ctx->det && eval_lds_bytes(n, true, true) > 160 * 1024) {
         fail(ctx, CFMM_E_LIMIT, "cfmm_create: CFMM_DETERMINISTIC=1 with %d tokens exceeds the LDS tile of the reproducible mode", n);
         return bail(CFMM_E_LIMIT);
@@ -2242,9 +2289,15 @@ int cfmm_clone(cfmm_ctx *src, cfmm_ctx **out)
     cfmm_ctx *c = nullptr;
     int rc = cfmm_create(src->device, src->n, &c);
     if (rc) { src->err = g_create_error; return rc; }
-    c->pools = src->pools;                 // the pool columns are shared: no copy, no second upload
+    {   // the pool columns are shared: no copy, no second upload
+        std::lock_guard<std::mutex> g(src->pools->mu);
+        c->pools = src->pools;
+        c->pools->sharers.push_back(c);
+    }
+    c->is_clone = true;
     c->det = src->det;
     local_extrema(c);
+    c->pool_gen = c->pools->gen.load(std::memory_order_acquire);
     c->nslices = src->nslices <= c->nslices ? src->nslices : c->nslices;
     *out = c;
     return CFMM_OK;
@@ -2259,7 +2312,15 @@ int cfmm_destroy(cfmm_ctx *ctx)
     if (ctx->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(ctx->comm);
     for (void *q : ctx->os_opened) (void)hipIpcCloseMemHandle(q);
     if (ctx->os_mail) (void)hipFree(ctx->os_mail);
+    if (ctx->pools) {
+        std::lock_guard<std::mutex> g(ctx->pools->mu);
+        auto &sh = ctx->pools->sharers;
+        sh.erase(std::remove(sh.begin(), sh.end(), ctx), sh.end());
+    }
     ctx->pools.reset();
+    if (ctx->ev_pool) (void)hipEventDestroy(ctx->ev_pool);
+    if (ctx->upd_dev) (void)hipFree(ctx->upd_dev);
+    if (ctx->upd_host) (void)hipHostFree(ctx->upd_host);
     if (ctx->flags2) (void)hipFree(ctx->flags2);
     for (int *q : ctx->flagsG) if (q) (void)hipFree(q);
     if (ctx->trade_buf) (void)hipFree(ctx->trade_buf);
@@ -2408,6 +2469,7 @@ static void build_compact_mirrors(cfmm_ctx *ctx, PoolStore &ps)
 
 static void pools_ready(cfmm_ctx *ctx)
 {
+    pools_seen(ctx);
     PoolStore &ps = *ctx->pools;
     std::lock_guard<std::mutex> guard(ps.mu);
     struct Mirrors { cfmm_ctx *c; PoolStore &p; ~Mirrors() { build_compact_mirrors(c, p); } } mirrors{ctx, ps};      // (on every way out, behind the orderings)
@@ -2534,13 +2596,14 @@ int cfmm_upload_pools2(cfmm_ctx *ctx, int kind, int64_t m, const double *Ra, con
     if (ctx->pools->b2mem[kind]) (void)hipFree(ctx->pools->b2mem[kind]);
     if (ctx->pools->c2mem[kind]) { (void)hipFree(ctx->pools->c2mem[kind]); ctx->pools->c2mem[kind] = nullptr; }
     ctx->pools->c2tried[kind] = false;
+    if (ctx->pools->inv2[kind]) { (void)hipFree(ctx->pools->inv2[kind]); ctx->pools->inv2[kind] = nullptr; }
     ctx->pools->b2mem[kind] = arena;
     ctx->pools->b2[kind] = b;
     if (kind == CFMM_POOL_SUM2) {
-        ctx->hs_ia.clear(); ctx->hs_ib.clear(); ctx->hs_fee.clear(); ctx->hs_Ra.clear(); ctx->hs_Rb.clear();
+        ctx->pools->hs_ia.clear(); ctx->pools->hs_ib.clear(); ctx->pools->hs_fee.clear(); ctx->pools->hs_Ra.clear(); ctx->pools->hs_Rb.clear();
         if (m > 0 && m <= 65536) {
-            ctx->hs_ia.assign(ia, ia + m); ctx->hs_ib.assign(ib, ib + m); ctx->hs_fee.assign(fee, fee + m);
-            ctx->hs_Ra.assign(Ra, Ra + m); ctx->hs_Rb.assign(Rb, Rb + m);
+            ctx->pools->hs_ia.assign(ia, ia + m); ctx->pools->hs_ib.assign(ib, ib + m); ctx->pools->hs_fee.assign(fee, fee + m);
+            ctx->pools->hs_Ra.assign(Ra, Ra + m); ctx->pools->hs_Rb.assign(Rb, Rb + m);
         }
     }
     ctx->tr_ovr_valid = false;
@@ -2613,6 +2676,7 @@ int cfmm_upload_poolsN(cfmm_ctx *ctx, int k, int64_t m, const int32_t *idx, cons
     }
     const double mxr = scan.mxr, mnf = scan.mnf;
     if (ctx->pools->bnmem[k]) (void)hipFree(ctx->pools->bnmem[k]);
+    if (ctx->pools->invn[k]) { (void)hipFree(ctx->pools->invn[k]); ctx->pools->invn[k] = nullptr; }
     ctx->pools->bnmem[k] = arena;
     ctx->pools->bn[k] = b;
     ctx->pools->ron[k] = ro_total;
@@ -2674,10 +2738,255 @@ int cfmm_upload_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t m, const int32_t 
     return CFMM_OK;
 }
 
+// ---- in-place updates of resident reserves (update.hpp) ---------------------------------------------------------------
+// One bucket per call.  Everything the caller hands in is checked on the host before anything is written; then the records
+// travel as ONE staged H2D copy (positions | new values, slot-major as given), one scatter launch writes them and the derived
+// columns, and the call returns behind its own synchronisation.  The writes are ordered behind the work every context sharing the
+// store has enqueued (one event per context); a context of the store that is inside a solve, evaluation or batch makes the call fail.
+namespace {
+struct UpdPart { const void *src; size_t bytes; };
+constexpr size_t UPD_HDR = 256;        // header of the device copy: int lowered | ... | unsigned long long bucket maximum at +64
+
+// the records -> ctx->upd_dev through the pinned staging ring the uploads use; offs[q] = device offset of part q
+int update_stage(cfmm_ctx *ctx, const std::vector<UpdPart> &parts, std::vector<size_t> &offs)
+{
+    size_t total = UPD_HDR;
+    offs.clear();
+    for (auto &p : parts) { offs.push_back(total); total += (p.bytes + 255) & ~(size_t)255; }
+    if (total > ctx->upd_cap) {
+        if (ctx->upd_dev) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->upd_dev); ctx->upd_dev = nullptr; ctx->upd_cap = 0; }
+        const size_t cap = std::max<size_t>(total, 1u << 20);
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->upd_dev, cap));
+        ctx->upd_cap = cap;
+    }
+    if (!ctx->upd_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->upd_host, 64, hipHostMallocDefault));
+    std::lock_guard<std::mutex> lock(g_stage.mu);
+    if (!g_stage.buf) {
+        HIP_TRY(ctx, hipHostMalloc((void **)&g_stage.buf, STAGE_SLOTS * STAGE_BYTES, hipHostMallocDefault));
+        for (auto &ev : g_stage.ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    int slot = g_stage.next;
+    for (size_t c0 = 0; c0 < total; c0 += STAGE_BYTES) {
+        const size_t clen = std::min(STAGE_BYTES, total - c0);
+        char *st = g_stage.buf + (size_t)slot * STAGE_BYTES;
+        if (g_stage.used[slot]) HIP_TRY(ctx, stage_slot_wait(slot));
+        std::memset(st, 0, std::min(clen, c0 < UPD_HDR ? UPD_HDR - c0 : (size_t)0));       // (the header: flag and maximum start at zero)
+        for (size_t q = 0; q < parts.size(); ++q) {
+            const size_t lo = std::max(offs[q], c0), hi = std::min(offs[q] + parts[q].bytes, c0 + clen);
+            if (lo < hi) std::memcpy(st + (lo - c0), (const char *)parts[q].src + (lo - offs[q]), hi - lo);
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->upd_dev + c0, st, clen, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(g_stage.ev[slot], ctx->stream));
+        g_stage.used[slot] = true; g_stage.last[slot] = ctx->stream; slot = (slot + 1) % STAGE_SLOTS;
+    }
+    g_stage.next = slot;
+    return CFMM_OK;
+}
+
+// positions: in [0, m), no duplicate (one bit per pool in a grow-only scratch of the store, cleared again on the way out)
+int update_check_positions(cfmm_ctx *ctx, const char *who, int64_t m, int64_t count, const int32_t *pos)
+{
+    auto &bits = ctx->pools->dup_bits;
+    if (bits.size() < (size_t)((m + 63) / 64)) bits.resize((size_t)((m + 63) / 64), 0ull);
+    int64_t i = 0;
+    int rc = CFMM_OK;
+    for (; i < count; ++i) {
+        const int32_t q = pos[i];
+        if (q < 0 || q >= m) { rc = fail(ctx, CFMM_E_ARG, "%s: entry %lld names pool %d, outside [0, %lld)", who, (long long)i, q, (long long)m); break; }
+        unsigned long long &w = bits[(size_t)q >> 6];
+        const unsigned long long bit = 1ull << (q & 63);
+        if (w & bit) { rc = fail(ctx, CFMM_E_ARG, "%s: pool %d is named twice", who, q); break; }
+        w |= bit;
+    }
+    for (int64_t j = 0; j < i; ++j) bits[(size_t)pos[j] >> 6] = 0ull;
+    return rc;
+}
+
+// reserves: positive and finite; returns the largest through mx
+int update_check_reserves(cfmm_ctx *ctx, const char *who, const double *R, int64_t cnt, double &mx)
+{
+    for (int64_t i = 0; i < cnt; ++i) {
+        const double x = R[i];
+        if (!(x > 0.0 && x <= std::numeric_limits<double>::max())) return fail(ctx, CFMM_E_ARG, "%s: reserve %lld is %g: not positive and finite", who, (long long)i, x);
+        mx = x > mx ? x : mx;
+    }
+    return CFMM_OK;
+}
+
+// the common frame of the three entry points: after the checks, under the store's lock
+//   launch(dev, offs, lowered)    enqueues the scatter of the staged parts
+//   reduce(out)                   enqueues the bucket's maximum into *out (zeroed)
+//   commit(mx)                    records the new maximum (and the host copies) once the writes are complete
+int update_run(cfmm_ctx *ctx, const char *who, const std::vector<UpdPart> &parts, const int *perm, int **inv, int64_t m, double mx_old, double mx_new,
+               const std::function<void(const char *, const std::vector<size_t> &, const int *, int *)> &launch,
+               const std::function<void(unsigned long long *)> &reduce, const std::function<void(double)> &commit, int64_t count)
+{
+    PoolStore &ps = *ctx->pools;
+    for (cfmm_ctx *s : ps.sharers) {
+        if (s == ctx) continue;
+        HIP_TRY(ctx, hipEventRecord(s->ev_pool, s->stream));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s->ev_pool, 0));
+    }
+    double mx = std::max(mx_old, mx_new);
+    if (count > 0) {
+        if (perm && !*inv) {
+            HIP_TRY(ctx, hipMalloc((void **)inv, (size_t)m * sizeof(int) + 16));
+            hipLaunchKernelGGL(upd_inverse_kernel, dim3((unsigned)std::min<int64_t>((m + UP_THREADS - 1) / UP_THREADS, 4096)), dim3(UP_THREADS), 0, ctx->stream, perm, (long long)m, *inv);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        std::vector<size_t> offs;
+        { int rc = update_stage(ctx, parts, offs); if (rc) return rc; }
+        int *lowered = (int *)ctx->upd_dev;
+        launch(ctx->upd_dev, offs, perm ? *inv : nullptr, lowered);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->upd_host, lowered, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (*(const int *)ctx->upd_host) {                 // a reserve equal to the bucket's maximum went down: reduce the bucket again
+            unsigned long long *out = (unsigned long long *)(ctx->upd_dev + 64);
+            reduce(out);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->upd_host, out, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            double r; std::memcpy(&r, ctx->upd_host, sizeof r);
+            mx = std::max(r, mx_new);
+        }
+    } else {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    (void)who;
+    commit(mx);
+    ps.gen.fetch_add(1, std::memory_order_acq_rel);
+    return CFMM_OK;
+}
+
+unsigned upd_grid(int64_t count) { return (unsigned)((count + UP_THREADS - 1) / UP_THREADS); }
+unsigned max_grid(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + UP_THREADS - 1) / UP_THREADS, 1024)); }
+}  // namespace
+
+int cfmm_update_pools2(cfmm_ctx *ctx, int kind, int64_t count, const int32_t *pos, const double *Ra, const double *Rb, const double *param)
+{
+    const char *who = "update_pools2";
+    if (!ctx) return CFMM_E_ARG;
+    if (kind < 0 || kind >= CFMM_POOL_KINDS2 || count < 0) return fail(ctx, CFMM_E_ARG, "%s: kind %d, count %lld", who, kind, (long long)count);
+    if (count > 0 && (!pos || !Ra || !Rb)) return fail(ctx, CFMM_E_ARG, "%s: NULL column", who);
+    if (param && !kKind2[kind].needs_param) return fail(ctx, CFMM_E_ARG, "%s: kind %d (%s) has no parameter", who, kind, kKind2[kind].name);
+    if (param && kind == CFMM_POOL_W2) return fail(ctx, CFMM_E_ARG, "%s: the weights of weighted pools cannot be updated (a re-upload)", who);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PoolStore &ps = *ctx->pools;
+    const int64_t m = ps.b2[kind].m;
+    if (m == 0 && count > 0) return fail(ctx, CFMM_E_STATE, "%s: no %s pools uploaded", who, kKind2[kind].name);
+    pools_ready(ctx);                                      // (a pending token-block ordering first: the positions go through its permutation)
+    std::unique_lock<std::mutex> guard(ps.mu);
+    if (ps.readers > 0) return fail(ctx, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve or evaluation", who);
+    { int rc = update_check_positions(ctx, who, m, count, pos); if (rc) return rc; }
+    double mx_new = 0.0;
+    { int rc = update_check_reserves(ctx, who, Ra, count, mx_new); if (rc) return rc; }
+    { int rc = update_check_reserves(ctx, who, Rb, count, mx_new); if (rc) return rc; }
+    if (param && kKind2[kind].param_ok)
+        for (int64_t i = 0; i < count; ++i)
+            if (!kKind2[kind].param_ok(param[i])) return fail(ctx, CFMM_E_ARG, "%s: entry %lld (%s) has parameter %g: expected %s", who, (long long)i, kKind2[kind].name, param[i], kKind2[kind].param_rule);
+    const Bucket2 b = ps.b2[kind];
+    const double mx_old = ps.mxr2[kind];
+    std::vector<UpdPart> parts = {{pos, (size_t)count * 4}, {Ra, (size_t)count * 8}, {Rb, (size_t)count * 8}};
+    if (param) parts.push_back({param, (size_t)count * 8});
+    const int cnt = (int)count;
+    const int rc = update_run(ctx, who, parts, b.perm, &ps.inv2[kind], m, mx_old, mx_new,
+        [&](const char *d, const std::vector<size_t> &o, const int *inv, int *low) {
+            hipLaunchKernelGGL(upd_scatter2_kernel, dim3(upd_grid(count)), dim3(UP_THREADS), 0, ctx->stream, b, cnt, (const int *)(d + o[0]),
+                               (const double *)(d + o[1]), (const double *)(d + o[2]), param ? (const double *)(d + o[3]) : nullptr, inv, mx_old, low);
+        },
+        [&](unsigned long long *out) {
+            hipLaunchKernelGGL(upd_max_kernel, dim3(max_grid(2 * m)), dim3(UP_THREADS), 0, ctx->stream, b.Ra, (long long)m, b.Rb, (long long)m, out);
+        },
+        [&](double mx) {
+            ps.mxr2[kind] = mx;
+            if (kind == CFMM_POOL_SUM2 && (int64_t)ps.hs_Ra.size() == m)
+                for (int64_t i = 0; i < count; ++i) { ps.hs_Ra[pos[i]] = Ra[i]; ps.hs_Rb[pos[i]] = Rb[i]; }
+        }, count);
+    guard.unlock();
+    if (rc == CFMM_OK) release_landed(ctx);          // (a reorder pools_ready ran above: its landing arena, behind this call's synchronisation)
+    return rc;
+}
+
+int cfmm_update_poolsN(cfmm_ctx *ctx, int k, int64_t count, const int32_t *pos, const double *R)
+{
+    const char *who = "update_poolsN";
+    if (!ctx) return CFMM_E_ARG;
+    if (k < 3 || k > CFMM_MAX_POOL_SIZE || count < 0) return fail(ctx, CFMM_E_ARG, "%s: pool size %d outside 3..%d, or count %lld", who, k, CFMM_MAX_POOL_SIZE, (long long)count);
+    if (count > 0 && (!pos || !R)) return fail(ctx, CFMM_E_ARG, "%s: NULL column", who);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PoolStore &ps = *ctx->pools;
+    const int64_t m = ps.bn[k].m;
+    if (m == 0 && count > 0) return fail(ctx, CFMM_E_STATE, "%s: no geo-mean pools of %d assets uploaded", who, k);
+    pools_ready(ctx);
+    std::unique_lock<std::mutex> guard(ps.mu);
+    if (ps.readers > 0) return fail(ctx, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve or evaluation", who);
+    { int rc = update_check_positions(ctx, who, m, count, pos); if (rc) return rc; }
+    double mx_new = 0.0;
+    { int rc = update_check_reserves(ctx, who, R, (int64_t)k * count, mx_new); if (rc) return rc; }
+    const BucketN b = ps.bn[k];
+    const double mx_old = ps.mxrn[k];
+    const std::vector<UpdPart> parts = {{pos, (size_t)count * 4}, {R, (size_t)count * k * 8}};
+    const int cnt = (int)count;
+    const int rc = update_run(ctx, who, parts, b.perm, &ps.invn[k], m, mx_old, mx_new,
+        [&](const char *d, const std::vector<size_t> &o, const int *inv, int *low) {
+            hipLaunchKernelGGL(upd_scatterN_kernel, dim3(upd_grid(count)), dim3(UP_THREADS), 0, ctx->stream, b, k, cnt, (const int *)(d + o[0]),
+                               (const double *)(d + o[1]), inv, mx_old, low);
+        },
+        [&](unsigned long long *out) {
+            hipLaunchKernelGGL(upd_max_kernel, dim3(max_grid((int64_t)k * m)), dim3(UP_THREADS), 0, ctx->stream, b.R, (long long)k * m, (const double *)nullptr, 0ll, out);
+        },
+        [&](double mx) { ps.mxrn[k] = mx; }, count);
+    guard.unlock();
+    if (rc == CFMM_OK) release_landed(ctx);          // (a reorder pools_ready ran above: its landing arena, behind this call's synchronisation)
+    return rc;
+}
+
+int cfmm_update_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t count, const int32_t *pos, const double *R, const double *param)
+{
+    const char *who = "update_poolsG";
+    if (!ctx) return CFMM_E_ARG;
+    if (kind < 0 || kind >= CFMM_POOLK_KINDS || k < 2 || k > CFMM_MAX_POOL_SIZE || count < 0)
+        return fail(ctx, CFMM_E_ARG, "%s: kind %d, %d assets, count %lld", who, kind, k, (long long)count);
+    if (count > 0 && (!pos || !R)) return fail(ctx, CFMM_E_ARG, "%s: NULL column", who);
+    if (param && kind != CFMM_POOLK_STABLE) return fail(ctx, CFMM_E_ARG, "%s: constant-sum pools have no parameter", who);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PoolStore &ps = *ctx->pools;
+    const int64_t m = ps.bg[kind][k].m;
+    if (m == 0 && count > 0) return fail(ctx, CFMM_E_STATE, "%s: no pools of kind %d with %d assets uploaded", who, kind, k);
+    pools_ready(ctx);
+    std::unique_lock<std::mutex> guard(ps.mu);
+    if (ps.readers > 0) return fail(ctx, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve or evaluation", who);
+    { int rc = update_check_positions(ctx, who, m, count, pos); if (rc) return rc; }
+    double mx_new = 0.0;
+    { int rc = update_check_reserves(ctx, who, R, (int64_t)k * count, mx_new); if (rc) return rc; }
+    if (param)
+        for (int64_t i = 0; i < count; ++i)
+            if (!(param[i] > 0.0 && param[i] <= std::numeric_limits<double>::max())) return fail(ctx, CFMM_E_ARG, "%s: entry %lld has alpha %g (need > 0)", who, (long long)i, param[i]);
+    const BucketG b = ps.bg[kind][k];
+    const double mx_old = ps.mxrg[kind][k];
+    std::vector<UpdPart> parts = {{pos, (size_t)count * 4}, {R, (size_t)count * k * 8}};
+    if (param) parts.push_back({param, (size_t)count * 8});
+    const int cnt = (int)count;
+    const int rc = update_run(ctx, who, parts, nullptr, nullptr, m, mx_old, mx_new,
+        [&](const char *d, const std::vector<size_t> &o, const int *, int *low) {
+            hipLaunchKernelGGL(upd_scatterG_kernel, dim3(upd_grid(count)), dim3(UP_THREADS), 0, ctx->stream, b, k, cnt, (const int *)(d + o[0]),
+                               (const double *)(d + o[1]), param ? (const double *)(d + o[2]) : nullptr, mx_old, low);
+        },
+        [&](unsigned long long *out) {
+            hipLaunchKernelGGL(upd_max_kernel, dim3(max_grid((int64_t)k * m)), dim3(UP_THREADS), 0, ctx->stream, b.R, (long long)k * m, (const double *)nullptr, 0ll, out);
+        },
+        [&](double mx) { ps.mxrg[kind][k] = mx; }, count);
+    guard.unlock();
+    if (rc == CFMM_OK) release_landed(ctx);          // (a reorder pools_ready ran above: its landing arena, behind this call's synchronisation)
+    return rc;
+}
+
 int cfmm_get_tradesG(cfmm_ctx *ctx, int kind, int k, double *delta, double *lambda)
 {
     if (!ctx || kind < 0 || kind >= CFMM_POOLK_KINDS || k < 2 || k > CFMM_MAX_POOL_SIZE) return CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    pools_seen(ctx);
     const BucketG &b = ctx->pools->bg[kind][k];
     if (b.m == 0) return CFMM_OK;
     const size_t cnt = (size_t)k * b.m;
@@ -2850,6 +3159,7 @@ int cfmm_get_psi(cfmm_ctx *ctx, double *psi)
 {
     if (!ctx || !psi) return CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    pools_seen(ctx);
     HIP_TRY(ctx, hipMemcpyAsync(psi, ctx->psi_acc, ctx->n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CFMM_OK;
@@ -2858,6 +3168,7 @@ int cfmm_get_psi(cfmm_ctx *ctx, double *psi)
 int cfmm_get_solution(cfmm_ctx *ctx, double *nu, double *psi)
 {
     if (!ctx || (!nu && !psi)) return CFMM_E_ARG;
+    pools_seen(ctx);
     if (ctx->hsol_valid) {                 // the last solve left both in pinned host memory
         if (nu) std::memcpy(nu, ctx->hsol, ctx->n * sizeof(double));
         if (psi) std::memcpy(psi, ctx->hsol + ctx->n, ctx->n * sizeof(double));
@@ -2874,6 +3185,7 @@ int cfmm_eval_dual(cfmm_ctx *ctx, const double *nu, double *arb_sum, double *psi
 {
     if (!ctx || !nu) return CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PoolReader reading(ctx);
     pools_ready(ctx);
     const int n = ctx->n;
     for (int j = 0; j < n; ++j) if (!(nu[j] > 0.0) || !std::isfinite(nu[j])) return fail(ctx, CFMM_E_ARG, "eval_dual: nu[%d] = %g is not a positive finite price", j, nu[j]);
@@ -2990,6 +3302,7 @@ int cfmm_eval_smooth(cfmm_ctx *ctx, const double *nu, double mu, double *value, 
 {
     if (!ctx || !nu || !(mu > 0.0)) return ctx ? fail(ctx, CFMM_E_ARG, "eval_smooth: nu is NULL or mu <= 0") : CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PoolReader reading(ctx);
     pools_ready(ctx);
     const char *why = "";
     if (!newton_supported(ctx, &why)) return fail(ctx, CFMM_E_UNSUPPORTED, "eval_smooth: %s", why);
@@ -3021,7 +3334,7 @@ static int solve_tiny_kinks(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out)
 {
     const int n = ctx->n;
     const int64_t msum = ctx->pools->b2[CFMM_POOL_SUM2].m;
-    if (msum == 0 || (int64_t)ctx->hs_ia.size() != msum || ctx->general_utility || ctx->ng != n || ctx->flags2 || sharded(ctx) || ctx->det || o.pg_rule) return 0;
+    if (msum == 0 || ctx->is_clone || (int64_t)ctx->pools->hs_ia.size() != msum || ctx->general_utility || ctx->ng != n || ctx->flags2 || sharded(ctx) || ctx->det || o.pg_rule) return 0;
     {
         const EvalArgs ea = make_eval_args(ctx, false, 0x7fffffff, false);
         if (!(ctx->tiny_path && extra_launch_pools(ctx) == 0 && ea.ntiles >= 1 && ea.ntiles <= TINY_MAX_TILES && n <= TINY_N)) return 0;
@@ -3046,8 +3359,8 @@ static int solve_tiny_kinks(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out)
     cfmm_stats st;
     const bool deferred = ctx->nu0_deferred;
     ctx->nu0_deferred = false;                               // (the sweep takes the prices from the host vector)
-    int rc = cfmm_solve_sweep(ctx, 1, ctx->hc.data(), ctx->hh.data(), ct.data(), nu0.data(), msum, ctx->hs_ia.data(), ctx->hs_ib.data(), ctx->hs_fee.data(),
-                              ctx->hs_Ra.data(), ctx->hs_Rb.data(), &os, 0.0, 0, nu.data(), psi.data(), theta.data(), tsgn.data(), tr.data(), &st, &rounds);
+    int rc = cfmm_solve_sweep(ctx, 1, ctx->hc.data(), ctx->hh.data(), ct.data(), nu0.data(), msum, ctx->pools->hs_ia.data(), ctx->pools->hs_ib.data(), ctx->pools->hs_fee.data(),
+                              ctx->pools->hs_Ra.data(), ctx->pools->hs_Rb.data(), &os, 0.0, 0, nu.data(), psi.data(), theta.data(), tsgn.data(), tr.data(), &st, &rounds);
     if (rc == CFMM_E_NUMERIC || rc == CFMM_E_UNSUPPORTED) { ctx->nu0_deferred = deferred; return 0; }
     if (rc) return rc;
     // psi_total = psi + sum theta d, the tied pools' tenders = theta x their full fill (cfmm.h: cfmm_solve_sweep)
@@ -3056,9 +3369,9 @@ static int solve_tiny_kinks(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out)
     double *dS = tr.data() + off_sum, *lS = dS + 2 * msum;                                  // delta [2][m] | lambda [2][m]
     for (int64_t i = 0; i < msum; ++i) {
         if (!std::isfinite(theta[i])) continue;
-        const double ya = (tsgn[i] > 0 ? -ctx->hs_Rb[i] / ctx->hs_fee[i] : ctx->hs_Ra[i]) * theta[i];
-        const double yb = (tsgn[i] > 0 ? ctx->hs_Rb[i] : -ctx->hs_Ra[i] / ctx->hs_fee[i]) * theta[i];
-        psi[ctx->hs_ia[i]] += ya; psi[ctx->hs_ib[i]] += yb;
+        const double ya = (tsgn[i] > 0 ? -ctx->pools->hs_Rb[i] / ctx->pools->hs_fee[i] : ctx->pools->hs_Ra[i]) * theta[i];
+        const double yb = (tsgn[i] > 0 ? ctx->pools->hs_Rb[i] : -ctx->pools->hs_Ra[i] / ctx->pools->hs_fee[i]) * theta[i];
+        psi[ctx->pools->hs_ia[i]] += ya; psi[ctx->pools->hs_ib[i]] += yb;
         dS[i] = std::max(-ya, 0.0); dS[msum + i] = std::max(-yb, 0.0);
         lS[i] = std::max(ya, 0.0); lS[msum + i] = std::max(yb, 0.0);
     }
@@ -3091,6 +3404,7 @@ int cfmm_solve(cfmm_ctx *ctx, const double *nu0, const cfmm_opts *opts_in, cfmm_
 {
     if (!ctx || !out) return CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PoolReader reading(ctx);
     pools_ready(ctx);
     struct AtExit { cfmm_ctx *c; ~AtExit() { release_landed(c); } } at_exit{ctx};      // (every path out of a solve ends behind a synchronisation)
     ctx->tr_ovr_valid = false;
@@ -3418,7 +3732,9 @@ int cfmm_solve_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu0, co
     if (!ctxs || nb < 1 || !ctxs[0] || !out) return CFMM_E_ARG;
     cfmm_ctx *c0 = ctxs[0];
     HIP_TRY(c0, hipSetDevice(c0->device));
+    PoolReader reading(c0);
     pools_ready(c0);
+    for (int b = 1; b < nb; ++b) if (ctxs[b]) pools_seen(ctxs[b]);
     struct AtExit { cfmm_ctx *c; ~AtExit() { release_landed(c); } } at_exit{c0};      // (as cfmm_solve: every path out ends behind a synchronisation,
                                                                                        //  or before anything read the pools)
     const int n = c0->n;
@@ -3788,6 +4104,7 @@ int cfmm_solve_sweep(cfmm_ctx *ctx, int B, const double *c, const double *h, con
 {
     if (!ctx || B < 1 || !c || !nu0 || !nu_out || !psi_out || !out) return ctx ? fail(ctx, CFMM_E_ARG, "solve_sweep: NULL argument or no points") : CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PoolReader reading(ctx);
     pools_ready(ctx);
     struct AtExit { cfmm_ctx *c; ~AtExit() { release_landed(c); } } at_exit{ctx};
     const int n = ctx->n;
@@ -4173,6 +4490,7 @@ int cfmm_debug_eval_limbs(cfmm_ctx *ctx, const double *nu, double ref_reserve, d
 {
     if (!ctx || !nu || !limbs) return CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PoolReader reading(ctx);
     pools_ready(ctx);
     const int n = ctx->n;
     if (eval_lds_bytes(n, true, true) > 160 * 1024) return fail(ctx, CFMM_E_LIMIT, "debug_eval_limbs: too many tokens for the reproducible mode");

@@ -140,11 +140,13 @@ __global__ void __launch_bounds__(256) compact_build_kernel(Bucket2 b, unsigned 
     }
 }
 
-// the derived column of a K-asset bucket: lrw = log(R / w) per leg (BucketN::lrw), filled behind the upload's copies
+// the derived column of a K-asset bucket: lrw = log(R / w) per leg (BucketN::lrw), filled behind the upload's copies -- and by the
+// in-place update of a pool's reserves (update.hpp), through the same expression, so that an updated leg is bitwise an uploaded one
+__device__ __forceinline__ double lrw_leg(double R, double w) { return log(R / w); }
 __global__ void __launch_bounds__(256) lrw_fill_kernel(const double *__restrict__ R, const double *__restrict__ w, double *__restrict__ lrw, long long legs)
 {
     const long long stride = (long long)gridDim.x * 256;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < legs; i += stride) lrw[i] = log(R[i] / w[i]);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < legs; i += stride) lrw[i] = lrw_leg(R[i], w[i]);
 }
 
 struct EvalArgs {

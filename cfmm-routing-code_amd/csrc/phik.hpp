@@ -41,12 +41,19 @@ struct BucketG {
     const double *ifee, *sR;
     double *ws;
 };
+// s_R = alpha / prod R of one pool whose K reserves sit `stride` apart (shared with the in-place update, update.hpp: bitwise the same)
+__device__ __forceinline__ double gk_coupling(const double *R, long long stride, int K, double alpha)
+{
+    double pr = 1.0;
+    for (int j = 0; j < K; ++j) pr *= R[j * stride];
+    return alpha / pr;
+}
 __global__ void __launch_bounds__(256) gk_derive_kernel(BucketG b, int K, double *ifee, double *sR, double *ws)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= b.m) return;
     ifee[i] = 1.0 / b.fee[i];
-    if (b.param) { double pr = 1.0; for (int j = 0; j < K; ++j) pr *= b.R[i * K + j]; sR[i] = b.param[i] / pr; } else sR[i] = 0.0;
+    sR[i] = b.param ? gk_coupling(b.R + i * K, 1, K, b.param[i]) : 0.0;
     ws[i] = __builtin_nan("");
 }
 

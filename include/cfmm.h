@@ -138,7 +138,7 @@ int cfmm_destroy(cfmm_ctx *ctx);
  * no copy) but has its own stream, utility, prices and solver state: several solves over one pool set --
  * the parameter sweep of two-asset.py:34-100, or independent utilities -- can then be in flight at once
  * (one per host thread), one solve's single-workgroup nu update overlapping another's evaluation kernels.
- * Pools cannot be re-uploaded while clones exist. */
+ * Pools cannot be re-uploaded while clones exist; their reserves can be updated in place through any of them (cfmm_update_pools*). */
 int cfmm_clone(cfmm_ctx *src, cfmm_ctx **out);
 const char *cfmm_last_error(cfmm_ctx *ctx);       /* ctx may be NULL: last error of cfmm_create */
 const char *cfmm_backend(cfmm_ctx *ctx);          /* "hip:gfx950"                               */
@@ -159,6 +159,36 @@ int cfmm_upload_poolsN(cfmm_ctx *ctx, int k, int64_t m, const int32_t *idx, cons
  * tokens (arbitrage.py:63-74 in the reference's style; the reference itself ships the two-token forms) */
 int cfmm_upload_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t m, const int32_t *idx, const double *R,
                        const double *fee, const double *param);
+/* In-place update of resident pools (the per-block loop of a router: between two blocks only the pools that traded change).
+ * Writes new reserves -- and, where the kind has one, the parameter (CFMM_POOL_CURVE2 / CFMM_POOLK_STABLE alpha, CFMM_POOL_POW2 t;
+ * param NULL = unchanged; every other kind, CFMM_POOL_W2 included, takes NULL only) -- of `count` pools of ONE bucket into the columns
+ * already in HBM, and recomputes what the upload derives from them (log(R / w) of the geo-mean legs, alpha / prod R and the root-search
+ * warm start of the table's pools) with the same device code: an updated pool is bitwise the pool a fresh upload would have made.  Moves
+ * count x (4 + 8 k [+ 8]) bytes instead of the whole pool set.
+ *   pos[count]    the pools, by their index in the order the bucket was uploaded (the index cfmm_get_trades* reports in), not by the
+ *                 position the library stores them at (large buckets are reordered on the device: the update maps through the inverse)
+ *   Ra, Rb        [count];  R: slot-major [k][count], like the uploads
+ * Fees, weights (of the two-asset weighted pools too) and token ids can NOT be updated (the ids decide the reordering, the fees the compact
+ * mirror, log fee, 1 / fee and the smallest fee, the weights log(R / w)): changing one of them, or adding / removing pools, is a re-upload.
+ * Rules:
+ *   - everything is checked before anything is written: a position outside [0, m) or named twice, a reserve that is not positive and
+ *     finite, a parameter the bucket's upload refuses (the same rule) -> CFMM_E_ARG and the pools are left bit for bit as they were;
+ *     count > 0 on an empty bucket -> CFMM_E_STATE, a k without a bucket (outside 3..8 / 2..8) -> CFMM_E_ARG; count == 0 is legal;
+ *   - the bucket's largest reserve is kept exact (what a fresh upload would record: the reproducible mode's fixed-point exponent, the
+ *     infeasibility floor);
+ *   - the pools are shared with every cfmm_clone: an update made through any context of the set is seen by all.  Each notices it on its
+ *     next call and drops what it derived from the old reserves (cached solution, the kink loop's tenders, the barrier warm start, the
+ *     largest reserve) but keeps its prices, utility, ties and tie flags: cfmm_solve(ctx, NULL, ...) continues from the accepted prices,
+ *     and cfmm_get_trades* before any re-solve returns the tenders of the NEW reserves at those prices;
+ *   - the writes are ordered behind all work already enqueued on every context of the set, and complete when the call returns; if another
+ *     context of the set is inside a solve, evaluation or batch at that moment the call returns CFMM_E_STATE;
+ *   - pool-sharded contexts (cfmm_comm_init): positions are local to this rank's shard, and EVERY rank makes the call (count = 0 where it
+ *     has nothing to update) so that the global maxima are re-reduced in step at the next solve. */
+int cfmm_update_pools2(cfmm_ctx *ctx, int kind, int64_t count, const int32_t *pos,
+                       const double *Ra, const double *Rb, const double *param /* NULL = unchanged */);
+int cfmm_update_poolsN(cfmm_ctx *ctx, int k, int64_t count, const int32_t *pos, const double *R /* [k][count] */);
+int cfmm_update_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t count, const int32_t *pos,
+                       const double *R /* [k][count] */, const double *param /* NULL = unchanged */);
 /* constant-sum pools sitting on their kink are `tied` (flag 1): they are skipped by the
  * kernels and their fill fraction is assigned by the host's primal recovery */
 int cfmm_set_pool_flags(cfmm_ctx *ctx, int kind, const int32_t *flags /* [m] or NULL */);
@@ -265,6 +295,8 @@ int cfmm_get_tradesG(cfmm_ctx *ctx, int kind, int k, double *delta, double *lamb
  * [psi | sum arb] per dual evaluation.  `uid` is the 128-byte ncclUniqueId made by rank 0. */
 int cfmm_comm_unique_id(void *uid128);
 int cfmm_comm_init(cfmm_ctx *ctx, int n_ranks, int rank, const void *uid128);
+/* (cfmm_update_pools* on a pool-sharded context: positions local to the rank's shard, and every rank makes the call -- count = 0 where
+ *  it has nothing to update -- so that the global maxima are re-reduced in step at the next solve) */
 
 /* One-shot all-reduce over the xGMI mesh for the iteration's 8-50 KB messages (csrc/oneshot.hpp): every rank stores its
  * vector straight into a mailbox in each peer's HBM, one hop instead of a ring's 2 (R - 1); reduced in rank order, so every
