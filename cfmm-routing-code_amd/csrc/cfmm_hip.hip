@@ -106,8 +106,8 @@ struct PoolStore {
     std::mutex mu;
     // in-place updates of the reserves (update.hpp: cfmm_update_pools*).  `gen` counts them; every context remembers the generation it
     // last saw and drops what it derived from the old reserves when it meets a newer one (pools_seen).  `readers`: contexts inside a
-    // solve / evaluation / batch right now (an update is refused meanwhile); `sharers`: every context on this store (an update orders
-    // its writes behind the work each has enqueued).  Both under `mu`.
+    // call that reads the columns right now (PoolEntry: an update is refused meanwhile); `sharers`: every context on this store (an
+    // update orders its writes behind the work each has enqueued).  Both under `mu`.
     std::atomic<unsigned long long> gen{0};
     int readers = 0;
     std::vector<cfmm_ctx *> sharers;
@@ -131,6 +131,16 @@ struct PoolStore {
     }
 };
 
+// Where the context's prices and solution are, and what the read-backs may return: assigned only by the transitions next to pools_changed
+struct Point {
+    bool have_nu = false;              // nu_acc holds prices: the caller's or a solve's
+    bool hsol_valid = false;           // hsol holds nu | psi of the last solve
+    double mu_last = 0.0;              // barrier weight of the last solve (0: first-order, exact tenders)
+    bool slo_active = false;           // sm_slo holds that solve's low-order log-prices (smooth.hpp); read only while mu_last > 0
+    std::vector<double> tr_ovr;        // tenders the library's kink loop left (solve_tiny_kinks; cfmm_solve_sweep's `trades` layout):
+    bool tr_ovr_valid = false;         // what cfmm_get_trades2 returns while set
+};
+
 struct cfmm_ctx {
     int device = 0, n = 0, ng = 0;
     int cus = 256;
@@ -146,10 +156,6 @@ struct cfmm_ctx {
     hipEvent_t ev_pool = nullptr;      // recorded on this context's stream by an update made through another context sharing the store
     char *upd_dev = nullptr; size_t upd_cap = 0;       // grow-only device copy of an update's records (cfmm_update_pools*)
     unsigned long long *upd_host = nullptr;            // pinned: the update's `lowered` flag and bucket maximum read back
-    // tenders as that loop left them (cfmm_solve_sweep's `trades` layout, the tied pools' fills folded in): what cfmm_get_trades2 / N
-    // return until the prices change again
-    std::vector<double> tr_ovr;
-    bool tr_ovr_valid = false;
     int *flagsG[CFMM_MAX_POOL_SIZE + 1] = {};      // per-leg tie flags of the table's constant-sum buckets (cfmm_set_pool_flagsG), pool-major
     double *trade_buf = nullptr;       // grow-only scratch for cfmm_get_trades* (delta | lambda)
     size_t trade_cap = 0;
@@ -182,7 +188,7 @@ struct cfmm_ctx {
     double *hnu0_d = nullptr, *hsol_d = nullptr;
     DevState *hst_d = nullptr;
     bool nu0_deferred = false;        // inside cfmm_solve only: the start prices are in hnu0 and not yet in nu_acc
-    bool hsol_valid = false;
+    Point pt;
     hipEvent_t ev[2] = {nullptr, nullptr}, ev_t0 = nullptr, ev_t1 = nullptr;
     int walk_parity[2] = {0, 0};       // direction of the next evaluation launch's tile walk (launch_eval), per tile space
     int nslices = 2;                   // accumulator slices the workgroups flush into (blockIdx % nslices): flat from 2 upward for the flush, and every slice is one more vector the in-launch update of EVERY workgroup reads (27.4 vs 28.4 us per iteration at 2 vs 4, C3)
@@ -195,7 +201,7 @@ struct cfmm_ctx {
     bool upd_generic = false;          // CFMM_UPDATE_GENERIC=1: force the generic update kernel (A/B testing)
     bool general_utility = false;      // some token carries an entry of the utility table beyond linear-plus-box (lbfgs_rules.hpp):
                                        // the generic two-launch first-order iteration serves it, nothing else
-    bool have_utility = false, have_nu = false;
+    bool have_utility = false;
     // host copies needed to derive bounds
     std::vector<double> hc, hh, hoff;
     std::vector<int> hctype, hgrp;
@@ -252,14 +258,11 @@ struct cfmm_ctx {
     double *sm_ws[CFMM_POOL_KINDS2] = {};   // warm starts of the smoothed per-direction solves
     long long sm_ws_m[CFMM_POOL_KINDS2] = {};
     double *sm_slo = nullptr;               // low-order log-prices of the last second-order solve (smooth.hpp)
-    bool slo_active = false;
     int *sm_mask = nullptr, *sm_info = nullptr;
-    double mu_last = 0.0;              // barrier weight of the last solve (0: first-order, exact tenders)
     // shader-clock probe (cfmm_clock_probe_*): one sleeping wave on a stream of its own, its samples in mapped pinned memory
     hipStream_t probe_stream = nullptr;
     long long *probe_ring = nullptr, *probe_ring_d = nullptr;       // [PROBE_CAP][2] {shader cycles, 100 MHz ticks} | control words behind them
     bool probe_running = false;
-    double warm_mu = 0.0;              // barrier weight to continue from (cfmm_solve with nu0 == NULL after a second-order solve)
 };
 
 namespace {
@@ -708,39 +711,54 @@ void local_extrema(cfmm_ctx *ctx)
     ctx->g_max_reserve = ctx->max_reserve;
 }
 
-// a successful (re-)upload invalidates everything that was derived from the previous pool set
-void pools_changed(cfmm_ctx *ctx)
+// ---- transitions of the context's point (cfmm_ctx::pt) -------------------------------------------------------------------------------
+// prices from the caller (cfmm_set_nu, cfmm_solve with nu0, every context entering cfmm_solve_batch): no earlier result describes them
+void point_from_caller(cfmm_ctx *ctx)
+{
+    Point &p = ctx->pt;
+    p.have_nu = true; p.hsol_valid = false; p.mu_last = 0.0; p.slo_active = false; p.tr_ovr_valid = false;
+}
+// a solve left nu | psi in nu_acc / psi_acc and hsol, at barrier weight mu (0: first order), sm_slo in use or not, and the kink loop its tenders
+void point_published(cfmm_ctx *ctx, double mu, bool slo, std::vector<double> *tenders = nullptr)
+{
+    Point &p = ctx->pt;
+    p.have_nu = true; p.hsol_valid = true; p.mu_last = mu; p.slo_active = slo; p.tr_ovr_valid = tenders != nullptr;
+    if (tenders) p.tr_ovr.swap(*tenders);
+}
+// the tie rules changed (cfmm_set_pool_flags / G, cfmm_set_ties), or a solve is about to move the point: the kink loop's tenders go
+void drop_tenders(cfmm_ctx *ctx) { ctx->pt.tr_ovr_valid = false; }
+// a first-order solve is about to move the point, or the smoothed state of its barrier weight was overwritten (cfmm_time_newton_kernels)
+void drop_barrier(cfmm_ctx *ctx) { ctx->pt.mu_last = 0.0; ctx->pt.slo_active = false; }
+// the reserves moved (a re-upload, or an update through any context of the store): the largest reserve, the captured launches that carry
+// it, the cached solution, the barrier weight and the kink tenders go; prices, utility, ties and tie flags stay (a solve from NULL goes on)
+void reserves_moved(cfmm_ctx *ctx)
 {
     local_extrema(ctx);
-    ctx->g_valid = false; ctx->g_counts_valid = false; ctx->listed_valid = false;
-    ctx->hsol_valid = false; ctx->mu_last = 0.0; ctx->warm_mu = 0.0; ctx->slo_active = false; ctx->tr_ovr_valid = false;
+    ctx->g_valid = false; ctx->g_counts_valid = false;
+    Point &p = ctx->pt;
+    p.hsol_valid = false; p.mu_last = 0.0; p.slo_active = false; p.tr_ovr_valid = false;
+}
+
+// a successful (re-)upload through this context
+void pools_changed(cfmm_ctx *ctx)
+{
+    reserves_moved(ctx);
+    ctx->listed_valid = false;             // (a re-upload only: an update moves reserves, never the token ids the list is made of)
     ctx->pool_gen = ctx->pools->gen.load(std::memory_order_acquire);
 }
 
 // On entry to every call that reads the pools: has some context sharing them updated reserves in place (cfmm_update_pools*) since this
-// one last looked?  Then what was derived from the old reserves goes -- the largest reserve (the reproducible mode's exponent; re-reduced
-// over the ranks when pool-sharded), the cached solution, the kink loop's tenders, the barrier warm start and the captured launches (they
-// carry the exponent) -- while the prices, the utility, the ties and the tie flags stay: a solve from NULL continues from the accepted
-// prices.  One integer compare when nothing changed.
+// one last looked?  One integer compare when nothing changed.
 void pools_seen(cfmm_ctx *ctx)
 {
     const unsigned long long g = ctx->pools->gen.load(std::memory_order_acquire);
     if (g == ctx->pool_gen) return;
     ctx->pool_gen = g;
-    local_extrema(ctx);
-    ctx->g_valid = false; ctx->g_counts_valid = false;
-    ctx->hsol_valid = false; ctx->tr_ovr_valid = false;
-    ctx->warm_mu = 0.0; ctx->mu_last = 0.0; ctx->slo_active = false;
+    reserves_moved(ctx);
+    // (an update only: the per-pool warm starts outlive it at unchanged bucket sizes; a re-upload of another size reallocates them)
     for (int k = 0; k < CFMM_POOL_KINDS2; ++k)
         if (ctx->sm_ws[k]) (void)hipMemsetAsync(ctx->sm_ws[k], 0, 2 * (size_t)ctx->sm_ws_m[k] * sizeof(double), ctx->stream);
 }
-
-// a solve, evaluation or batch in progress on a context of this store: an update through another context is refused meanwhile
-struct PoolReader {
-    PoolStore &ps;
-    explicit PoolReader(cfmm_ctx *ctx) : ps(*ctx->pools) { std::lock_guard<std::mutex> g(ps.mu); ++ps.readers; }
-    ~PoolReader() { std::lock_guard<std::mutex> g(ps.mu); --ps.readers; }
-};
 
 // dma: the staged tile walk (kernels.hpp) -- one 4 KB slot per wave on top
 size_t eval_lds_bytes(int n, bool with_d, bool det = false, bool dma = false)
@@ -1692,7 +1710,8 @@ static HostUtilityTerm host_utility_term(int ctype, double c, double h, double n
     return t;
 }
 
-int solve_newton(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out, int evals_before)
+// warm_mu: the barrier weight to continue from (that of the previous solve, when cfmm_solve continues from it), or 0
+int solve_newton(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out, int evals_before, double warm_mu)
 {
     const char *why = "";
     if (!newton_supported(ctx, &why)) return fail(ctx, CFMM_E_UNSUPPORTED, "solve: the second-order method cannot take this problem: %s", why);
@@ -1797,7 +1816,7 @@ int solve_newton(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out, int evals_b
     static const double mu0_scale = getenv("CFMM_NEWTON_MU0") ? atof(getenv("CFMM_NEWTON_MU0")) : 0.1;                      // tuning knob
     double mu = mu0_scale * std::max(std::fabs(dual), 1e-300) / (double)std::max<long long>(nbar, 1);
     static const double warm_mult = getenv("CFMM_NEWTON_WARM") ? atof(getenv("CFMM_NEWTON_WARM")) : 1e3;                    // tuning knob
-    if (ctx->warm_mu > 0.0) mu = std::min(mu, warm_mult * ctx->warm_mu);
+    if (warm_mu > 0.0) mu = std::min(mu, warm_mult * warm_mu);
     static const double sigma_env = getenv("CFMM_NEWTON_SHRINK") ? atof(getenv("CFMM_NEWTON_SHRINK")) : 0.0;      // tuning knob (A/B)
     const double sigma = (sigma_env > 0.0 && sigma_env < 1.0) ? sigma_env : ((o.barrier_shrink > 0.0 && o.barrier_shrink < 1.0) ? o.barrier_shrink : 0.1);
     const int max_newton = o.max_newton > 0 ? o.max_newton : 200;
@@ -2098,9 +2117,7 @@ int solve_newton(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out, int evals_b
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::memcpy(ctx->hsol, nu.data(), n * sizeof(double));
     if ((int)e.psi.size() == n) std::memcpy(ctx->hsol + n, e.psi.data(), n * sizeof(double));
-    ctx->hsol_valid = true; ctx->have_nu = true;
-    ctx->mu_last = mu;
-    ctx->slo_active = slo_on;
+    point_published(ctx, mu, slo_on);
     if (slo_on && !ctx->lean_io) { HIP_TRY(ctx, hipMemcpyAsync(ctx->sm_slo, slo.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream)); HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); }
     const auto t1 = std::chrono::steady_clock::now();
     float ms = 0.f;
@@ -2500,9 +2517,9 @@ static void pools_ready(cfmm_ctx *ctx)
         ps.ron[k] = 0;
     }
 }
-// at the END of an entry point that has synchronised its stream (the permuted copies are complete): the landing arenas
-// go.  hipFree synchronises the whole device -- at the start of a call that could wait on a kernel of another in-process
-// "rank" that is itself waiting for this rank's next exchange; behind this call's own synchronisation nothing waits for us
+// at the END of an entry point: the landing arenas whose permuted copies this context's stream enqueued go, behind a synchronisation
+// of that stream (only when there are some).  hipFree synchronises the whole device -- at the start of a call that could wait on a
+// kernel of another in-process "rank" that is itself waiting for this rank's next exchange; at the end nothing waits for us
 static void release_landed(cfmm_ctx *ctx)
 {
     PoolStore &ps = *ctx->pools;
@@ -2513,8 +2530,26 @@ static void release_landed(cfmm_ctx *ctx)
         for (auto &q : ps.landed) { if (q.second == ctx->stream) mine.push_back(q.first); else ps.landed[keep++] = q; }
         ps.landed.resize(keep);
     }
+    if (mine.empty()) return;
+    (void)hipStreamSynchronize(ctx->stream);
     for (void *q : mine) (void)hipFree(q);
 }
+
+// The entry of every call that uses pool columns: the device, this context counted as a reader of its store (an in-place update through
+// any context of the store is refused meanwhile), the pending orderings (pools_ready); on every way out, release_landed.  The caller
+// returns a failed hipSetDevice: HIP_TRY(ctx, entry.device).  The updates (cfmm_update_pools*) are no readers: they refuse while there are.
+struct PoolEntry {
+    cfmm_ctx *ctx;
+    PoolStore &ps;
+    const bool reader;
+    hipError_t device;
+    explicit PoolEntry(cfmm_ctx *c, bool rd = true) : ctx(c), ps(*c->pools), reader(rd)
+    {
+        if (reader) { std::lock_guard<std::mutex> g(ps.mu); ++ps.readers; }
+        if ((device = hipSetDevice(c->device)) == hipSuccess) pools_ready(c);
+    }
+    ~PoolEntry() { release_landed(ctx); if (reader) { std::lock_guard<std::mutex> g(ps.mu); --ps.readers; } }
+};
 
 // The two-asset kinds as the upload layer sees them: one generic bucket (columns Ra, Rb, fee, [param], ia, ib), per kind
 // only whether a parameter column is required and which values it may hold.  A new trading function is one row here and
@@ -2606,7 +2641,6 @@ int cfmm_upload_pools2(cfmm_ctx *ctx, int kind, int64_t m, const double *Ra, con
             ctx->pools->hs_Ra.assign(Ra, Ra + m); ctx->pools->hs_Rb.assign(Rb, Rb + m);
         }
     }
-    ctx->tr_ovr_valid = false;
     ctx->pools->ro2[kind] = ro_total;
     ctx->pools->mxr2[kind] = mxr; ctx->pools->mnf2[kind] = mnf;
     if (kind == CFMM_POOL_SUM2 && ctx->flags2) { (void)hipFree(ctx->flags2); ctx->flags2 = nullptr; }
@@ -2871,13 +2905,12 @@ int cfmm_update_pools2(cfmm_ctx *ctx, int kind, int64_t count, const int32_t *po
     if (count > 0 && (!pos || !Ra || !Rb)) return fail(ctx, CFMM_E_ARG, "%s: NULL column", who);
     if (param && !kKind2[kind].needs_param) return fail(ctx, CFMM_E_ARG, "%s: kind %d (%s) has no parameter", who, kind, kKind2[kind].name);
     if (param && kind == CFMM_POOL_W2) return fail(ctx, CFMM_E_ARG, "%s: the weights of weighted pools cannot be updated (a re-upload)", who);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PoolEntry entry(ctx, false); HIP_TRY(ctx, entry.device);     // (a pending token-block ordering first: the positions go through its permutation)
     PoolStore &ps = *ctx->pools;
     const int64_t m = ps.b2[kind].m;
     if (m == 0 && count > 0) return fail(ctx, CFMM_E_STATE, "%s: no %s pools uploaded", who, kKind2[kind].name);
-    pools_ready(ctx);                                      // (a pending token-block ordering first: the positions go through its permutation)
-    std::unique_lock<std::mutex> guard(ps.mu);
-    if (ps.readers > 0) return fail(ctx, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve or evaluation", who);
+    std::lock_guard<std::mutex> guard(ps.mu);
+    if (ps.readers > 0) return fail(ctx, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve, evaluation or read-back", who);
     { int rc = update_check_positions(ctx, who, m, count, pos); if (rc) return rc; }
     double mx_new = 0.0;
     { int rc = update_check_reserves(ctx, who, Ra, count, mx_new); if (rc) return rc; }
@@ -2890,7 +2923,7 @@ int cfmm_update_pools2(cfmm_ctx *ctx, int kind, int64_t count, const int32_t *po
     std::vector<UpdPart> parts = {{pos, (size_t)count * 4}, {Ra, (size_t)count * 8}, {Rb, (size_t)count * 8}};
     if (param) parts.push_back({param, (size_t)count * 8});
     const int cnt = (int)count;
-    const int rc = update_run(ctx, who, parts, b.perm, &ps.inv2[kind], m, mx_old, mx_new,
+    return update_run(ctx, who, parts, b.perm, &ps.inv2[kind], m, mx_old, mx_new,
         [&](const char *d, const std::vector<size_t> &o, const int *inv, int *low) {
             hipLaunchKernelGGL(upd_scatter2_kernel, dim3(upd_grid(count)), dim3(UP_THREADS), 0, ctx->stream, b, cnt, (const int *)(d + o[0]),
                                (const double *)(d + o[1]), (const double *)(d + o[2]), param ? (const double *)(d + o[3]) : nullptr, inv, mx_old, low);
@@ -2903,9 +2936,6 @@ int cfmm_update_pools2(cfmm_ctx *ctx, int kind, int64_t count, const int32_t *po
             if (kind == CFMM_POOL_SUM2 && (int64_t)ps.hs_Ra.size() == m)
                 for (int64_t i = 0; i < count; ++i) { ps.hs_Ra[pos[i]] = Ra[i]; ps.hs_Rb[pos[i]] = Rb[i]; }
         }, count);
-    guard.unlock();
-    if (rc == CFMM_OK) release_landed(ctx);          // (a reorder pools_ready ran above: its landing arena, behind this call's synchronisation)
-    return rc;
 }
 
 int cfmm_update_poolsN(cfmm_ctx *ctx, int k, int64_t count, const int32_t *pos, const double *R)
@@ -2914,13 +2944,12 @@ int cfmm_update_poolsN(cfmm_ctx *ctx, int k, int64_t count, const int32_t *pos, 
     if (!ctx) return CFMM_E_ARG;
     if (k < 3 || k > CFMM_MAX_POOL_SIZE || count < 0) return fail(ctx, CFMM_E_ARG, "%s: pool size %d outside 3..%d, or count %lld", who, k, CFMM_MAX_POOL_SIZE, (long long)count);
     if (count > 0 && (!pos || !R)) return fail(ctx, CFMM_E_ARG, "%s: NULL column", who);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PoolEntry entry(ctx, false); HIP_TRY(ctx, entry.device);
     PoolStore &ps = *ctx->pools;
     const int64_t m = ps.bn[k].m;
     if (m == 0 && count > 0) return fail(ctx, CFMM_E_STATE, "%s: no geo-mean pools of %d assets uploaded", who, k);
-    pools_ready(ctx);
-    std::unique_lock<std::mutex> guard(ps.mu);
-    if (ps.readers > 0) return fail(ctx, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve or evaluation", who);
+    std::lock_guard<std::mutex> guard(ps.mu);
+    if (ps.readers > 0) return fail(ctx, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve, evaluation or read-back", who);
     { int rc = update_check_positions(ctx, who, m, count, pos); if (rc) return rc; }
     double mx_new = 0.0;
     { int rc = update_check_reserves(ctx, who, R, (int64_t)k * count, mx_new); if (rc) return rc; }
@@ -2928,7 +2957,7 @@ int cfmm_update_poolsN(cfmm_ctx *ctx, int k, int64_t count, const int32_t *pos, 
     const double mx_old = ps.mxrn[k];
     const std::vector<UpdPart> parts = {{pos, (size_t)count * 4}, {R, (size_t)count * k * 8}};
     const int cnt = (int)count;
-    const int rc = update_run(ctx, who, parts, b.perm, &ps.invn[k], m, mx_old, mx_new,
+    return update_run(ctx, who, parts, b.perm, &ps.invn[k], m, mx_old, mx_new,
         [&](const char *d, const std::vector<size_t> &o, const int *inv, int *low) {
             hipLaunchKernelGGL(upd_scatterN_kernel, dim3(upd_grid(count)), dim3(UP_THREADS), 0, ctx->stream, b, k, cnt, (const int *)(d + o[0]),
                                (const double *)(d + o[1]), inv, mx_old, low);
@@ -2937,9 +2966,6 @@ int cfmm_update_poolsN(cfmm_ctx *ctx, int k, int64_t count, const int32_t *pos, 
             hipLaunchKernelGGL(upd_max_kernel, dim3(max_grid((int64_t)k * m)), dim3(UP_THREADS), 0, ctx->stream, b.R, (long long)k * m, (const double *)nullptr, 0ll, out);
         },
         [&](double mx) { ps.mxrn[k] = mx; }, count);
-    guard.unlock();
-    if (rc == CFMM_OK) release_landed(ctx);          // (a reorder pools_ready ran above: its landing arena, behind this call's synchronisation)
-    return rc;
 }
 
 int cfmm_update_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t count, const int32_t *pos, const double *R, const double *param)
@@ -2950,13 +2976,12 @@ int cfmm_update_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t count, const int3
         return fail(ctx, CFMM_E_ARG, "%s: kind %d, %d assets, count %lld", who, kind, k, (long long)count);
     if (count > 0 && (!pos || !R)) return fail(ctx, CFMM_E_ARG, "%s: NULL column", who);
     if (param && kind != CFMM_POOLK_STABLE) return fail(ctx, CFMM_E_ARG, "%s: constant-sum pools have no parameter", who);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PoolEntry entry(ctx, false); HIP_TRY(ctx, entry.device);
     PoolStore &ps = *ctx->pools;
     const int64_t m = ps.bg[kind][k].m;
     if (m == 0 && count > 0) return fail(ctx, CFMM_E_STATE, "%s: no pools of kind %d with %d assets uploaded", who, kind, k);
-    pools_ready(ctx);
-    std::unique_lock<std::mutex> guard(ps.mu);
-    if (ps.readers > 0) return fail(ctx, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve or evaluation", who);
+    std::lock_guard<std::mutex> guard(ps.mu);
+    if (ps.readers > 0) return fail(ctx, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve, evaluation or read-back", who);
     { int rc = update_check_positions(ctx, who, m, count, pos); if (rc) return rc; }
     double mx_new = 0.0;
     { int rc = update_check_reserves(ctx, who, R, (int64_t)k * count, mx_new); if (rc) return rc; }
@@ -2968,7 +2993,7 @@ int cfmm_update_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t count, const int3
     std::vector<UpdPart> parts = {{pos, (size_t)count * 4}, {R, (size_t)count * k * 8}};
     if (param) parts.push_back({param, (size_t)count * 8});
     const int cnt = (int)count;
-    const int rc = update_run(ctx, who, parts, nullptr, nullptr, m, mx_old, mx_new,
+    return update_run(ctx, who, parts, nullptr, nullptr, m, mx_old, mx_new,
         [&](const char *d, const std::vector<size_t> &o, const int *, int *low) {
             hipLaunchKernelGGL(upd_scatterG_kernel, dim3(upd_grid(count)), dim3(UP_THREADS), 0, ctx->stream, b, k, cnt, (const int *)(d + o[0]),
                                (const double *)(d + o[1]), param ? (const double *)(d + o[2]) : nullptr, mx_old, low);
@@ -2977,16 +3002,12 @@ int cfmm_update_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t count, const int3
             hipLaunchKernelGGL(upd_max_kernel, dim3(max_grid((int64_t)k * m)), dim3(UP_THREADS), 0, ctx->stream, b.R, (long long)k * m, (const double *)nullptr, 0ll, out);
         },
         [&](double mx) { ps.mxrg[kind][k] = mx; }, count);
-    guard.unlock();
-    if (rc == CFMM_OK) release_landed(ctx);          // (a reorder pools_ready ran above: its landing arena, behind this call's synchronisation)
-    return rc;
 }
 
 int cfmm_get_tradesG(cfmm_ctx *ctx, int kind, int k, double *delta, double *lambda)
 {
     if (!ctx || kind < 0 || kind >= CFMM_POOLK_KINDS || k < 2 || k > CFMM_MAX_POOL_SIZE) return CFMM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    pools_seen(ctx);
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
     const BucketG &b = ctx->pools->bg[kind][k];
     if (b.m == 0) return CFMM_OK;
     const size_t cnt = (size_t)k * b.m;
@@ -2995,8 +3016,8 @@ int cfmm_get_tradesG(cfmm_ctx *ctx, int kind, int k, double *delta, double *lamb
     const dim3 grid((unsigned)((b.m + GK_THREADS - 1) / GK_THREADS)), blk(GK_THREADS);
     const double *nu = ctx->nu_acc;
     const int *fl = kind == CFMM_POOLK_SUM ? ctx->flagsG[k] : nullptr;
-    const double *slo = (ctx->mu_last > 0.0 && ctx->slo_active) ? ctx->sm_slo : nullptr;       // (as cfmm_get_tradesN)
-    const double mu = ctx->mu_last > 0.0 ? ctx->mu_last : 0.0;     // (behind a second-order solve: the constant-sum entry's smoothed tenders)
+    const double *slo = (ctx->pt.mu_last > 0.0 && ctx->pt.slo_active) ? ctx->sm_slo : nullptr;       // (as cfmm_get_tradesN)
+    const double mu = ctx->pt.mu_last > 0.0 ? ctx->pt.mu_last : 0.0;     // (behind a second-order solve: the constant-sum entry's smoothed tenders)
 #define GK_T1(KIND_, KK) case KK: hipLaunchKernelGGL((tradesg_kernel<KIND_, KK>), grid, blk, 0, ctx->stream, b, fl, nu, slo, mu, dd, dl); break;
 #define GK_T(KIND_) switch (k) { GK_T1(KIND_, 2) GK_T1(KIND_, 3) GK_T1(KIND_, 4) GK_T1(KIND_, 5) GK_T1(KIND_, 6) GK_T1(KIND_, 7) default: hipLaunchKernelGGL((tradesg_kernel<KIND_, 8>), grid, blk, 0, ctx->stream, b, fl, nu, slo, mu, dd, dl); break; }
     if (kind == CFMM_POOLK_STABLE) { GK_T(CFMM_POOLK_STABLE) } else { GK_T(CFMM_POOLK_SUM) }
@@ -3019,6 +3040,7 @@ int cfmm_set_pool_flags(cfmm_ctx *ctx, int kind, const int32_t *flags)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->flags2) { (void)hipFree(ctx->flags2); ctx->flags2 = nullptr; }
     ctx->g_valid = false;
+    drop_tenders(ctx);
     if (!flags || b.m == 0) return CFMM_OK;
     int rc = dev_upload<int>(ctx, &ctx->flags2, flags, b.m, nullptr);
     if (rc) return rc;
@@ -3037,6 +3059,7 @@ int cfmm_set_pool_flagsG(cfmm_ctx *ctx, int k, const int32_t *flags)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->flagsG[k]) { (void)hipFree(ctx->flagsG[k]); ctx->flagsG[k] = nullptr; }
     ctx->g_valid = false;
+    drop_tenders(ctx);
     if (!flags || b.m == 0) return CFMM_OK;
     std::vector<int> pm((size_t)k * b.m);
     for (int64_t i = 0; i < b.m; ++i) for (int j = 0; j < k; ++j) pm[(size_t)i * k + j] = flags[(size_t)j * b.m + i];
@@ -3101,6 +3124,7 @@ int cfmm_set_ties(cfmm_ctx *ctx, int n_groups, const int32_t *grp, const double 
         ctx->ng = n_groups;
         ctx->hgrp.assign(grp, grp + n); ctx->hoff.assign(off, off + n);
     }
+    drop_tenders(ctx);
     HIP_TRY(ctx, hipMemcpyAsync(ctx->grp, ctx->hgrp.data(), n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->off, ctx->hoff.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (ctx->ng != n) {
@@ -3142,7 +3166,7 @@ int cfmm_set_nu(cfmm_ctx *ctx, const double *nu)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::memcpy(ctx->hnu0, nu, ctx->n * sizeof(double));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->nu_acc, ctx->hnu0, ctx->n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ctx->have_nu = true; ctx->hsol_valid = false; ctx->mu_last = 0.0; ctx->slo_active = false; ctx->tr_ovr_valid = false;
+    point_from_caller(ctx);
     return CFMM_OK;
 }
 
@@ -3169,7 +3193,7 @@ int cfmm_get_solution(cfmm_ctx *ctx, double *nu, double *psi)
 {
     if (!ctx || (!nu && !psi)) return CFMM_E_ARG;
     pools_seen(ctx);
-    if (ctx->hsol_valid) {                 // the last solve left both in pinned host memory
+    if (ctx->pt.hsol_valid) {              // the last solve left both in pinned host memory
         if (nu) std::memcpy(nu, ctx->hsol, ctx->n * sizeof(double));
         if (psi) std::memcpy(psi, ctx->hsol + ctx->n, ctx->n * sizeof(double));
         return CFMM_OK;
@@ -3184,9 +3208,7 @@ int cfmm_get_solution(cfmm_ctx *ctx, double *nu, double *psi)
 int cfmm_eval_dual(cfmm_ctx *ctx, const double *nu, double *arb_sum, double *psi, double *diag)
 {
     if (!ctx || !nu) return CFMM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    PoolReader reading(ctx);
-    pools_ready(ctx);
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
     const int n = ctx->n;
     for (int j = 0; j < n; ++j) if (!(nu[j] > 0.0) || !std::isfinite(nu[j])) return fail(ctx, CFMM_E_ARG, "eval_dual: nu[%d] = %g is not a positive finite price", j, nu[j]);
     const int len = acc_stride(n);
@@ -3232,7 +3254,6 @@ int cfmm_eval_dual(cfmm_ctx *ctx, const double *nu, double *arb_sum, double *psi
     if (psi) std::memcpy(psi, pin_acc, n * sizeof(double));
     if (arb_sum) *arb_sum = pin_acc[acc_arb(n)];
     if (diag) std::memcpy(diag, pin_acc + acc_diag(n), n * sizeof(double));
-    release_landed(ctx);
     return CFMM_OK;
 }
 
@@ -3301,9 +3322,7 @@ int cfmm_debug_cholesky_apply(cfmm_ctx *ctx, int n, const double *b, double *x)
 int cfmm_eval_smooth(cfmm_ctx *ctx, const double *nu, double mu, double *value, double *trade, double *psi, double *H)
 {
     if (!ctx || !nu || !(mu > 0.0)) return ctx ? fail(ctx, CFMM_E_ARG, "eval_smooth: nu is NULL or mu <= 0") : CFMM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    PoolReader reading(ctx);
-    pools_ready(ctx);
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
     const char *why = "";
     if (!newton_supported(ctx, &why)) return fail(ctx, CFMM_E_UNSUPPORTED, "eval_smooth: %s", why);
     const int n = ctx->n;
@@ -3343,7 +3362,7 @@ static int solve_tiny_kinks(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out)
     // start prices on the host: the caller's (deferred), or the context's own
     std::vector<double> nu0(n);
     if (ctx->nu0_deferred) std::memcpy(nu0.data(), ctx->hnu0, n * sizeof(double));
-    else if (ctx->hsol_valid) std::memcpy(nu0.data(), ctx->hsol, n * sizeof(double));
+    else if (ctx->pt.hsol_valid) std::memcpy(nu0.data(), ctx->hsol, n * sizeof(double));
     else {
         HIP_TRY(ctx, hipMemcpyAsync(nu0.data(), ctx->nu_acc, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -3392,8 +3411,7 @@ static int solve_tiny_kinks(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out)
     HIP_TRY(ctx, hipMemcpyAsync(ctx->nu_acc, ctx->hsol, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->psi_acc, ctx->hsol + n, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->hsol_valid = true; ctx->have_nu = true; ctx->mu_last = 0.0; ctx->slo_active = false;
-    ctx->tr_ovr.swap(tr); ctx->tr_ovr_valid = true;
+    point_published(ctx, 0.0, false, &tr);
     *out = st;
     out->status = 1; out->primal_value = value; out->dual_value = dual; out->gap = gap; out->infeas = infeas;
     out->iters = st.iters; out->method = CFMM_METHOD_LBFGS;
@@ -3403,11 +3421,8 @@ static int solve_tiny_kinks(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out)
 int cfmm_solve(cfmm_ctx *ctx, const double *nu0, const cfmm_opts *opts_in, cfmm_stats *out)
 {
     if (!ctx || !out) return CFMM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    PoolReader reading(ctx);
-    pools_ready(ctx);
-    struct AtExit { cfmm_ctx *c; ~AtExit() { release_landed(c); } } at_exit{ctx};      // (every path out of a solve ends behind a synchronisation)
-    ctx->tr_ovr_valid = false;
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
+    drop_tenders(ctx);
     cfmm_opts o;
     if (opts_in) o = *opts_in; else cfmm_default_opts(&o);
     // auto: tiny problems afford (nearly) full quasi-Newton memory; else 3 (iterate.hpp: ITER_MM) -- and 8 for the utility table's
@@ -3421,14 +3436,14 @@ int cfmm_solve(cfmm_ctx *ctx, const double *nu0, const cfmm_opts *opts_in, cfmm_
     if (ctx->g_total == 0) return fail(ctx, CFMM_E_STATE, "solve: no pools uploaded");      // (an empty SHARD is fine: it joins the collectives)
     // nu0 == NULL continues from the previous solution: its prices and, for the second-order method, (a multiple of) its
     // final barrier weight -- the warm start of a parametric sweep (two-asset.py:34-100)
-    ctx->warm_mu = nu0 ? 0.0 : ctx->mu_last;
+    const double warm_mu = nu0 ? 0.0 : ctx->pt.mu_last;
     if (nu0) {
         // as cfmm_set_nu, minus the copy to the device: the first-order solve's start kernel reads the prices where they are
         // (mapped pinned memory) and writes nu_acc itself; a solve that goes straight to the second-order method sends them first
         { int rc = check_prices(ctx, "solve: nu0", nu0); if (rc) return rc; }
         std::memcpy(ctx->hnu0, nu0, ctx->n * sizeof(double));     // (every entry point leaves the stream synchronised: nothing still reads hnu0)
         ctx->nu0_deferred = true;
-        ctx->have_nu = true; ctx->hsol_valid = false; ctx->mu_last = 0.0; ctx->slo_active = false;
+        point_from_caller(ctx);
     }
     // (the flag never outlives this call -- and neither are the prices lost: if a path leaves before anything has consumed
     //  them (an error in front of the start kernel), they are sent now, so that nu_acc holds what have_nu promises)
@@ -3446,7 +3461,7 @@ int cfmm_solve(cfmm_ctx *ctx, const double *nu0, const cfmm_opts *opts_in, cfmm_
         HIP_TRY(ctx, hipMemcpyAsync(ctx->nu_acc, ctx->hnu0, ctx->n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         return CFMM_OK;
     };
-    if (!ctx->have_nu) return fail(ctx, CFMM_E_STATE, "solve: no start prices (pass nu0 or call cfmm_set_nu)");
+    if (!ctx->pt.have_nu) return fail(ctx, CFMM_E_STATE, "solve: no start prices (pass nu0 or call cfmm_set_nu)");
     if (o.method == CFMM_METHOD_AUTO) {         // constant-sum kinks of a small network: the library's own active-set loop
         const int r = solve_tiny_kinks(ctx, o, out);
         if (r < 0) return r;
@@ -3463,7 +3478,7 @@ int cfmm_solve(cfmm_ctx *ctx, const double *nu0, const cfmm_opts *opts_in, cfmm_
         static const int prelude = getenv("CFMM_NEWTON_PRELUDE") ? atoi(getenv("CFMM_NEWTON_PRELUDE")) : 12;     // tuning knob
         int used = 0;
         double w0 = 0.0, d0 = 0.0;
-        if (prelude > 0 && can_newton && ctx->warm_mu == 0.0 && ctx->g_total >= 50000 && !o.pg_rule) {
+        if (prelude > 0 && can_newton && warm_mu == 0.0 && ctx->g_total >= 50000 && !o.pg_rule) {
             cfmm_opts op = o;
             op.method = 0; op.max_newton = 0; op.barrier_shrink = 0.0; op.max_evals = prelude;
             int rc = solve_lbfgs(ctx, op, out);
@@ -3472,7 +3487,7 @@ int cfmm_solve(cfmm_ctx *ctx, const double *nu0, const cfmm_opts *opts_in, cfmm_
             used = out->evals; w0 = out->wall_seconds; d0 = out->device_seconds;
         }
         { int rc = send_nu0(); if (rc) return rc; }
-        int rc = solve_newton(ctx, o, out, used);
+        int rc = solve_newton(ctx, o, out, used, warm_mu);
         out->wall_seconds += w0; out->device_seconds += d0;
         // The barrier path asked for by name and ended without its certificates (round 6; tools/fuzz_small.py seeds 1387, 1501,
         // fuzz_table.py seed 12): optima where nothing trades -- or hardly anything -- leave its Newton system singular in directions
@@ -3484,11 +3499,9 @@ int cfmm_solve(cfmm_ctx *ctx, const double *nu0, const cfmm_opts *opts_in, cfmm_
             const cfmm_stats second = *out;
             const int n = ctx->n;
             const std::vector<double> keep(ctx->hsol, ctx->hsol + 2 * (size_t)n);      // (the path's point: prices | smoothed psi)
-            const double keep_mu = ctx->mu_last;
-            const bool keep_slo = ctx->slo_active;
+            const double keep_mu = ctx->pt.mu_last; const bool keep_slo = ctx->pt.slo_active;
             cfmm_opts ol = o;
             ol.method = 0; ol.max_newton = 0; ol.barrier_shrink = 0.0;
-            ctx->slo_active = false;
             rc = solve_lbfgs(ctx, ol, out);
             if (rc) return rc;
             const cfmm_stats fin = *out;
@@ -3501,7 +3514,7 @@ int cfmm_solve(cfmm_ctx *ctx, const double *nu0, const cfmm_opts *opts_in, cfmm_
                 HIP_TRY(ctx, hipMemcpyAsync(ctx->nu_acc, ctx->hsol, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
                 HIP_TRY(ctx, hipMemcpyAsync(ctx->psi_acc, ctx->hsol + n, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
                 HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                ctx->hsol_valid = true; ctx->have_nu = true; ctx->mu_last = keep_mu; ctx->slo_active = keep_slo;
+                point_published(ctx, keep_mu, keep_slo);
             } else {
                 out->newton_steps = second.newton_steps;
             }
@@ -3518,7 +3531,7 @@ int cfmm_solve(cfmm_ctx *ctx, const double *nu0, const cfmm_opts *opts_in, cfmm_
     const cfmm_stats first = *out;
     cfmm_opts o2 = o;
     o2.max_evals = std::max(o.max_evals, 500);      // the second-order method gets its own budget (it is also capped by max_newton)
-    rc = solve_newton(ctx, o2, out, first.evals);
+    rc = solve_newton(ctx, o2, out, first.evals, warm_mu);
     out->wall_seconds += first.wall_seconds; out->device_seconds += first.device_seconds;
     return rc;
 }
@@ -3526,7 +3539,7 @@ int cfmm_solve(cfmm_ctx *ctx, const double *nu0, const cfmm_opts *opts_in, cfmm_
 static int solve_lbfgs(cfmm_ctx *ctx, const cfmm_opts &o_in, cfmm_stats *out)
 {
     const int n = ctx->n;
-    ctx->mu_last = 0.0;
+    drop_barrier(ctx);
     cfmm_opts o = o_in;
     // One launch per iteration (iterate.hpp) whenever the update fits the evaluation launch; otherwise the
     // two-launch iteration (evaluation kernel, single-workgroup update kernel).
@@ -3700,7 +3713,7 @@ static int solve_lbfgs(cfmm_ctx *ctx, const cfmm_opts &o_in, cfmm_stats *out)
     HIP_TRY(ctx, hipMemcpyAsync(ctx->hsol + n, ctx->psi_acc, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
-    ctx->hsol_valid = true;
+    point_published(ctx, 0.0, false);
     { double mx = 0.0; for (int j = 0; j < n; ++j) mx = std::max(mx, ctx->hsol[j]); if (mx > 0.0 && std::isfinite(mx)) ctx->nu_max = mx; }
     const auto t1 = std::chrono::steady_clock::now();
     float ms = 0.f;
@@ -3731,12 +3744,8 @@ int cfmm_solve_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu0, co
 {
     if (!ctxs || nb < 1 || !ctxs[0] || !out) return CFMM_E_ARG;
     cfmm_ctx *c0 = ctxs[0];
-    HIP_TRY(c0, hipSetDevice(c0->device));
-    PoolReader reading(c0);
-    pools_ready(c0);
+    PoolEntry entry(c0); HIP_TRY(c0, entry.device);
     for (int b = 1; b < nb; ++b) if (ctxs[b]) pools_seen(ctxs[b]);
-    struct AtExit { cfmm_ctx *c; ~AtExit() { release_landed(c); } } at_exit{c0};      // (as cfmm_solve: every path out ends behind a synchronisation,
-                                                                                       //  or before anything read the pools)
     const int n = c0->n;
     if (nb > batch_capacity(n)) return fail(c0, CFMM_E_LIMIT, "solve_batch: %d solves, at most %d fit the LDS tile at %d tokens", nb, batch_capacity(n), n);
     cfmm_opts o;
@@ -3755,8 +3764,8 @@ int cfmm_solve_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu0, co
         if (!c->have_utility) return fail(c0, CFMM_E_STATE, "solve_batch: context %d has no utility", b);
         if (c->general_utility) return fail(c0, CFMM_E_UNSUPPORTED, "solve_batch: context %d has a utility beyond linear-plus-box (CFMM_ULOG / CFMM_UQUAD): solved one at a time", b);
         if (nu0 && nu0[b]) { int rc = cfmm_set_nu(c, nu0[b]); if (rc) { c0->err = c->err; return rc; } }
-        if (!c->have_nu) return fail(c0, CFMM_E_STATE, "solve_batch: context %d has no start prices", b);
-        c->warm_mu = 0.0; c->mu_last = 0.0;
+        if (!c->pt.have_nu) return fail(c0, CFMM_E_STATE, "solve_batch: context %d has no start prices", b);
+        point_from_caller(c);
         HIP_TRY(c0, hipStreamSynchronize(c->stream));
     }
     if (cfmm_pool_count(c0) == 0) return fail(c0, CFMM_E_STATE, "solve_batch: no pools uploaded");
@@ -3846,7 +3855,7 @@ int cfmm_solve_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu0, co
     int rc_all = CFMM_OK;
     for (int b = 0; b < nb; ++b) {
         cfmm_ctx *c = ctxs[b];
-        c->hsol_valid = true;
+        point_published(c, 0.0, false);
         { double mx = 0.0; for (int j = 0; j < n; ++j) mx = std::max(mx, c->hsol[j]); if (mx > 0.0 && std::isfinite(mx)) c->nu_max = mx; }
         const DevState st = c->hst[0];
         cfmm_stats *s = out + b;
@@ -4103,10 +4112,7 @@ int cfmm_solve_sweep(cfmm_ctx *ctx, int B, const double *c, const double *h, con
                      double *nu_out, double *psi_out, double *theta_out, int32_t *tsgn_out, double *trades_out, cfmm_stats *out, int32_t *rounds_out)
 {
     if (!ctx || B < 1 || !c || !nu0 || !nu_out || !psi_out || !out) return ctx ? fail(ctx, CFMM_E_ARG, "solve_sweep: NULL argument or no points") : CFMM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    PoolReader reading(ctx);
-    pools_ready(ctx);
-    struct AtExit { cfmm_ctx *c; ~AtExit() { release_landed(c); } } at_exit{ctx};
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
     const int n = ctx->n;
     cfmm_opts o;
     if (opts_in) o = *opts_in; else cfmm_default_opts(&o);
@@ -4372,24 +4378,23 @@ int cfmm_solve_sweep(cfmm_ctx *ctx, int B, const double *c, const double *h, con
 int cfmm_get_trades2(cfmm_ctx *ctx, int kind, double *delta, double *lambda)
 {
     if (!ctx || kind < 0 || kind >= CFMM_POOL_KINDS2) return CFMM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    pools_ready(ctx);
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
     Bucket2 b = ctx->pools->b2[kind];
     if (kind == CFMM_POOL_SUM2) b.flags = ctx->flags2;
     if (b.m == 0) return CFMM_OK;
-    if (ctx->tr_ovr_valid) {                    // the library's own kink loop left the tenders (solve_tiny_kinks)
+    if (ctx->pt.tr_ovr_valid) {                 // the library's own kink loop left the tenders (solve_tiny_kinks)
         size_t off = 0;
         for (int k = 0; k < kind; ++k) off += 4 * (size_t)ctx->pools->b2[k].m;
-        if (delta) std::memcpy(delta, ctx->tr_ovr.data() + off, 2 * (size_t)b.m * sizeof(double));
-        if (lambda) std::memcpy(lambda, ctx->tr_ovr.data() + off + 2 * (size_t)b.m, 2 * (size_t)b.m * sizeof(double));
+        if (delta) std::memcpy(delta, ctx->pt.tr_ovr.data() + off, 2 * (size_t)b.m * sizeof(double));
+        if (lambda) std::memcpy(lambda, ctx->pt.tr_ovr.data() + off + 2 * (size_t)b.m, 2 * (size_t)b.m * sizeof(double));
         return CFMM_OK;
     }
     double *dd = nullptr, *dl = nullptr;
     { int rc = trade_scratch(ctx, 2 * (size_t)b.m, &dd, &dl); if (rc) return rc; }
     const dim3 grid((unsigned)((b.m + 255) / 256)), blk(256);
-    if (ctx->mu_last > 0.0) {              // after a second-order solve: the smoothed primal point
-        const double mu = ctx->mu_last;
-        const double *slo = ctx->slo_active ? ctx->sm_slo : nullptr;
+    if (ctx->pt.mu_last > 0.0) {           // after a second-order solve: the smoothed primal point
+        const double mu = ctx->pt.mu_last;
+        const double *slo = ctx->pt.slo_active ? ctx->sm_slo : nullptr;
         switch (kind) {
         case 0: hipLaunchKernelGGL(smooth_trades_kernel<0>, grid, blk, 0, ctx->stream, b, (const double *)ctx->nu_acc, slo, mu, dd, dl); break;
         case 1: hipLaunchKernelGGL(smooth_trades_kernel<1>, grid, blk, 0, ctx->stream, b, (const double *)ctx->nu_acc, slo, mu, dd, dl); break;
@@ -4416,8 +4421,7 @@ int cfmm_get_trades2(cfmm_ctx *ctx, int kind, double *delta, double *lambda)
 int cfmm_get_tradesN(cfmm_ctx *ctx, int k, double *delta, double *lambda)
 {
     if (!ctx || k < 3 || k > CFMM_MAX_POOL_SIZE) return CFMM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    pools_ready(ctx);
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
     const BucketN &b = ctx->pools->bn[k];
     if (b.m == 0) return CFMM_OK;
     const size_t cnt = (size_t)k * b.m;
@@ -4427,7 +4431,7 @@ int cfmm_get_tradesN(cfmm_ctx *ctx, int k, double *delta, double *lambda)
     const double *nu = ctx->nu_acc;
     // after a second-order solve that ended with low-order log-prices the k-asset pools were evaluated with them
     // (gn_newton_kernel): the tenders handed out must be those of the same point, or they would not sum to psi
-    const double *slo = (ctx->mu_last > 0.0 && ctx->slo_active) ? ctx->sm_slo : nullptr;
+    const double *slo = (ctx->pt.mu_last > 0.0 && ctx->pt.slo_active) ? ctx->sm_slo : nullptr;
     switch (k) {
     case 3: hipLaunchKernelGGL(tradesn_kernel<3>, grid, blk, 0, ctx->stream, b, nu, slo, dd, dl); break;
     case 4: hipLaunchKernelGGL(tradesn_kernel<4>, grid, blk, 0, ctx->stream, b, nu, slo, dd, dl); break;
@@ -4489,9 +4493,7 @@ int cfmm_set_deterministic(cfmm_ctx *ctx, int on)
 int cfmm_debug_eval_limbs(cfmm_ctx *ctx, const double *nu, double ref_reserve, double ref_fee, uint64_t *limbs)
 {
     if (!ctx || !nu || !limbs) return CFMM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    PoolReader reading(ctx);
-    pools_ready(ctx);
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
     const int n = ctx->n;
     if (eval_lds_bytes(n, true, true) > 160 * 1024) return fail(ctx, CFMM_E_LIMIT, "debug_eval_limbs: too many tokens for the reproducible mode");
     for (int j = 0; j < n; ++j) if (!(nu[j] > 0.0) || !std::isfinite(nu[j])) return fail(ctx, CFMM_E_ARG, "debug_eval_limbs: nu[%d] is not a positive finite price", j);
@@ -4726,9 +4728,8 @@ int cfmm_time_xcd_handoff(cfmm_ctx *ctx, int np, int reps, double *out7)
 int cfmm_time_eval_kernel(cfmm_ctx *ctx, int kind, int reps, double *sec_per_launch)
 {
     if (!ctx || reps < 1 || !sec_per_launch) return CFMM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    pools_ready(ctx);
-    if (!ctx->have_nu) return fail(ctx, CFMM_E_STATE, "time_eval_kernel: no prices set");
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
+    if (!ctx->pt.have_nu) return fail(ctx, CFMM_E_STATE, "time_eval_kernel: no prices set");
     HIP_TRY(ctx, hipMemcpyAsync(ctx->nu, ctx->nu_acc, ctx->n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(ctx->nu + ctx->n, 0, sizeof(double), ctx->stream));
     const int only = kind == CFMM_TIME_ALL ? 0x7fffffff : kind;
@@ -4760,14 +4761,12 @@ int cfmm_time_eval_kernel(cfmm_ctx *ctx, int kind, int reps, double *sec_per_lau
 int cfmm_time_newton_kernels(cfmm_ctx *ctx, double mu, int reps, double *out4)
 {
     if (!ctx || reps < 1 || !out4 || !(mu > 0.0)) return CFMM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    pools_ready(ctx);
-    struct AtExit { cfmm_ctx *c; ~AtExit() { (void)hipStreamSynchronize(c->stream); release_landed(c); } } at_exit{ctx};
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
     const char *why = "";
     if (!newton_supported(ctx, &why)) return fail(ctx, CFMM_E_UNSUPPORTED, "time_newton_kernels: %s", why);
     const int n = ctx->n, nr = hess_nr(n), ld = hess_ld(n);
     int rc = smooth_buffers(ctx, true); if (rc) return rc;
-    if (!ctx->have_nu) return fail(ctx, CFMM_E_STATE, "time_newton_kernels: no prices (cfmm_set_nu or a solve first)");
+    if (!ctx->pt.have_nu) return fail(ctx, CFMM_E_STATE, "time_newton_kernels: no prices (cfmm_set_nu or a solve first)");
     HIP_TRY(ctx, hipMemcpyAsync(ctx->nu, ctx->nu_acc, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));       // (the accepted prices)
     HIP_TRY(ctx, hipMemsetAsync(ctx->sm_mask, 0, n * sizeof(int), ctx->stream));
     for (int k = 0; k < CFMM_POOL_KINDS2; ++k)
@@ -4821,7 +4820,7 @@ int cfmm_time_newton_kernels(cfmm_ctx *ctx, double mu, int reps, double *out4)
     }
     // this hook overwrote the Hessian, the pin mask and the warm starts of the smoothed per-direction solves: the next
     // second-order solve must not continue from them (it starts its barrier path afresh)
-    ctx->mu_last = 0.0; ctx->warm_mu = 0.0; ctx->slo_active = false;
+    drop_barrier(ctx);
     if (rc) { const std::string prev = ctx->err; return fail(ctx, rc, "time_newton_kernels: the factorisation launches failed (%s; %s)", prev.c_str(), hipGetErrorString(hipGetLastError())); }
     out4[2] = fac / reps; out4[3] = back / reps;
     return CFMM_OK;

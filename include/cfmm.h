@@ -181,7 +181,7 @@ int cfmm_upload_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t m, const int32_t 
  *     largest reserve) but keeps its prices, utility, ties and tie flags: cfmm_solve(ctx, NULL, ...) continues from the accepted prices,
  *     and cfmm_get_trades* before any re-solve returns the tenders of the NEW reserves at those prices;
  *   - the writes are ordered behind all work already enqueued on every context of the set, and complete when the call returns; if another
- *     context of the set is inside a solve, evaluation or batch at that moment the call returns CFMM_E_STATE;
+ *     context of the set is inside a solve, evaluation, batch or trade read-back at that moment the call returns CFMM_E_STATE;
  *   - pool-sharded contexts (cfmm_comm_init): positions are local to this rank's shard, and EVERY rank makes the call (count = 0 where it
  *     has nothing to update) so that the global maxima are re-reduced in step at the next solve. */
 int cfmm_update_pools2(cfmm_ctx *ctx, int kind, int64_t count, const int32_t *pos,

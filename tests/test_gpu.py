@@ -353,6 +353,71 @@ def test_c_abi_solve_settles_constant_sum_kinks_itself_on_small_networks(seed, u
     p.close(); q.close()
 
 
+def _kink_network(seed):
+    """constant-product and constant-sum pools only (what cfmm_solve_batch takes) of the reference's size, three constant-sum pools
+    more, as in test_c_abi_solve_settles_constant_sum_kinks_itself_on_small_networks"""
+    inst = random_instance(140 + seed, n_tokens=5 + seed % 3, n_pools=10 + 2 * seed, with_sum=True, two_asset_only=True)
+    inst["weights"] = [None] * len(inst["kinds"])                         # (every geo-mean pool constant-product)
+    rng = np.random.default_rng(seed)
+    for i in range(3):
+        a, b = rng.choice(inst["n_tokens"], 2, replace=False)
+        inst["local_indices"].append([int(a), int(b)]); inst["reserves"].append([float(np.exp(rng.normal(2, 0.5)))] * 2)
+        inst["fees"].append(float(rng.choice([0.997, 0.999, 0.99]))); inst["kinds"].append("sum"); inst["weights"].append(None); inst["params"].append(None)
+    return inst
+
+
+def _solved_in_the_kink_loop(inst):
+    """a context of `inst` after a default-method solve that the library's own kink loop settled (it left its tenders)"""
+    p = problem_of(inst)
+    u = utility_of(inst)
+    ctx = p._ensure_ctx(); ctx.set_utility(u.c, u.h, u.ctype)
+    st = ctx.solve(cfmm.start_prices(p.net, u), tol=1e-9)
+    assert st["status"] == 1 and st["method"] == _lib.METHODS["lbfgs"], st
+    return p, u, ctx
+
+
+def _trades2_of(ctx, net):
+    return {key: ctx.get_trades2(cfmm.problem.KIND2[key], len(net[key]["Ra"])) for key in cfmm.problem.KIND2 if key in net and len(net[key]["Ra"])}
+
+
+def test_batch_solve_after_the_kink_loop_reads_back_its_own_tenders():
+    """the kink loop's tenders describe the point of the solve that left them: after a batch solve moves the context to other prices,
+    cfmm_get_trades2 returns the tenders at THOSE prices -- bit for bit what a fresh context returns there -- and they add up to the
+    batch's psi (cfmm.h: "afterwards every context is read back as after cfmm_solve")"""
+    inst = _kink_network(0)
+    p, u, ctx = _solved_in_the_kink_loop(inst)
+    ctx.set_utility(np.asarray(u.c) * np.exp(np.random.default_rng(1).normal(0, 0.05, inst["n_tokens"])))
+    ctx.solve_batch([], tol=1e-9)
+    nu, psi = ctx.get_solution()
+    fresh = problem_of(inst)
+    f = fresh._ensure_ctx(); f.set_nu(nu)
+    got, want = _trades2_of(ctx, p.net), _trades2_of(f, p.net)
+    assert set(got) == {"cp2", "sum2"}
+    tot = np.zeros(inst["n_tokens"])
+    for key, (d, l) in got.items():
+        assert np.array_equal(d, want[key][0]) and np.array_equal(l, want[key][1]), key
+        np.add.at(tot, p.net[key]["ia"], l[0] - d[0]); np.add.at(tot, p.net[key]["ib"], l[1] - d[1])
+    assert np.abs(tot - psi).max() <= 1e-9 * max(1.0, np.abs(psi).max())
+    p.close(); fresh.close()
+
+
+def test_tie_flags_after_the_kink_loop_apply_to_the_read_back():
+    """cfmm_set_pool_flags after a solve the kink loop settled: the read-back follows the new flags, as a fresh context's does at the
+    same prices"""
+    inst = _kink_network(0)
+    p, _, ctx = _solved_in_the_kink_loop(inst)
+    nu, _ = ctx.get_solution()
+    flags = np.ones(len(p.net["sum2"]["Ra"]), dtype=np.int32)
+    ctx.set_pool_flags(_lib.POOL_SUM2, flags)
+    fresh = problem_of(inst)
+    f = fresh._ensure_ctx(); f.set_nu(nu); f.set_pool_flags(_lib.POOL_SUM2, flags)
+    got, want = _trades2_of(ctx, p.net), _trades2_of(f, p.net)
+    assert set(got) == {"cp2", "sum2"}
+    for key, (d, l) in got.items():
+        assert np.array_equal(d, want[key][0]) and np.array_equal(l, want[key][1]), key
+    p.close(); fresh.close()
+
+
 def test_sweep_call_refuses_what_it_cannot_index():
     """cfmm_solve_sweep's host half indexes the prices with the constant-sum columns handed in: ids out of range, a non-positive
     reserve, a fee outside (0, 1], a non-finite offset, a utility-table entry, a count that differs from the upload -- each is an
