@@ -25,6 +25,7 @@
 #include <limits>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/cfmm.h"
@@ -81,27 +82,46 @@ struct DevBuf {
     void *p = nullptr; size_t bytes = 0;
 };
 
+// the template instance for a run-time kind or size: f(std::integral_constant<int, v>) for v in [LO, HI), any other v -> HI
+template <int LO, int HI, class F> void with_int(int v, F &&f)
+{
+    if constexpr (LO < HI) if (v != LO) return with_int<LO + 1, HI>(v, f);
+    f(std::integral_constant<int, LO>{});
+}
+
 }  // namespace
+
+// one resident bucket: its columns and what the store keeps about them
+template <class B> struct Resident {
+    B b = {};
+    void *mem = nullptr;               // one arena (one hipMalloc) per bucket: every column lives in it
+    int *inv = nullptr;                // inverse of a permuted bucket's perm (caller index -> position), built at its first update
+    // token-block ordering still to be done (reorder.hpp): the arena's column bytes, 0 = nothing pending.  Done lazily, in
+    // front of the first kernel that reads the pools, so that the uploads' copies are not queued behind sort kernels
+    size_t ro = 0;
+    double mxr = 0.0, mnf = 1.0;       // largest reserve / smallest fee (read only while b.m > 0)
+    void release() { for (void *q : {mem, (void *)inv}) if (q) (void)hipFree(q); mem = nullptr; inv = nullptr; }
+};
+struct Resident2 : Resident<Bucket2> {
+    void *cmem = nullptr;              // the bucket's compact mirror (kernels.hpp: Bucket2::cid / cfee / ctab), built in pools_ready
+    bool ctried = false;               // ... or found not to apply (more than 256 distinct fees)
+    void release() { Resident::release(); if (cmem) (void)hipFree(cmem); cmem = nullptr; ctried = false; }
+};
 
 // the pool columns in HBM; shared (reference-counted) between a context and its clones
 struct PoolStore {
-    Bucket2 b2[CFMM_POOL_KINDS2] = {};
-    void *b2mem[CFMM_POOL_KINDS2] = {};           // one arena (one hipMalloc) per bucket: every column lives in it
-    void *c2mem[CFMM_POOL_KINDS2] = {};           // the bucket's compact mirror (kernels.hpp: Bucket2::cid / cfee / ctab), built in pools_ready
-    bool c2tried[CFMM_POOL_KINDS2] = {};          // ... or found not to apply (more than 256 distinct fees)
-    BucketN bn[CFMM_MAX_POOL_SIZE + 1] = {};
-    void *bnmem[CFMM_MAX_POOL_SIZE + 1] = {};
-    BucketG bg[CFMM_POOLK_KINDS][CFMM_MAX_POOL_SIZE + 1] = {};      // the K-asset table's buckets (phik.hpp): [kind][k]
-    void *bgmem[CFMM_POOLK_KINDS][CFMM_MAX_POOL_SIZE + 1] = {};
-    double mxr2[CFMM_POOL_KINDS2] = {}, mnf2[CFMM_POOL_KINDS2] = {1.0, 1.0, 1.0, 1.0};       // largest reserve / smallest fee per bucket
-    double mxrn[CFMM_MAX_POOL_SIZE + 1] = {}, mnfn[CFMM_MAX_POOL_SIZE + 1] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
-    double mxrg[CFMM_POOLK_KINDS][CFMM_MAX_POOL_SIZE + 1] = {}, mnfg[CFMM_POOLK_KINDS][CFMM_MAX_POOL_SIZE + 1] = {};      // (the table's buckets; mnfg is set with the bucket)
-    // token-block ordering still to be done (reorder.hpp): the arena's column bytes, 0 = nothing pending.  Done lazily, in
-    // front of the first kernel that reads the pools, so that the uploads' copies are not queued behind sort kernels
-    size_t ro2[CFMM_POOL_KINDS2] = {}, ron[CFMM_MAX_POOL_SIZE + 1] = {};
+    Resident2 r2[CFMM_POOL_KINDS2];
+    Resident<BucketN> rn[CFMM_MAX_POOL_SIZE + 1];
+    Resident<BucketG> rg[CFMM_POOLK_KINDS][CFMM_MAX_POOL_SIZE + 1];      // the K-asset table's buckets (phik.hpp): [kind][k]
+    template <class F> void each(F &&f)            // every record (and every slot no bucket size uses: those stay empty)
+    {
+        for (auto &r : r2) f(r);
+        for (auto &r : rn) f(r);
+        for (auto &row : rg) for (auto &r : row) f(r);
+    }
     // landing arenas whose permuted copies have been enqueued, with the stream they were enqueued on: freed by release_landed
     // of the SAME context behind its own synchronisation.  A context and its clones share this store and may be driven from
-    // different host threads (Problem.solve_many): `mu` guards landed and the pending flags ro2 / ron.
+    // different host threads (Problem.solve_many): `mu` guards landed and the pending orderings (Resident::ro).
     std::vector<std::pair<void *, hipStream_t>> landed;
     std::mutex mu;
     // in-place updates of the reserves (update.hpp: cfmm_update_pools*).  `gen` counts them; every context remembers the generation it
@@ -111,8 +131,6 @@ struct PoolStore {
     std::atomic<unsigned long long> gen{0};
     int readers = 0;
     std::vector<cfmm_ctx *> sharers;
-    int *inv2[CFMM_POOL_KINDS2] = {};              // inverse of a permuted bucket's perm (caller index -> position), built at its first update
-    int *invn[CFMM_MAX_POOL_SIZE + 1] = {};
     std::vector<unsigned long long> dup_bits;      // scratch of the updates' duplicate check (one bit per pool of the largest bucket), all zero between calls
     // host copy of the constant-sum bucket's columns as uploaded and updated (small buckets only): the host half of the library's own
     // active-set loop over their kinks reads them (cfmm_solve with CFMM_METHOD_AUTO on networks cfmm_solve_sweep serves; round 6).  Only the
@@ -121,13 +139,8 @@ struct PoolStore {
     std::vector<double> hs_fee, hs_Ra, hs_Rb;
     ~PoolStore()
     {
-        for (int *q : inv2) if (q) (void)hipFree(q);
-        for (int *q : invn) if (q) (void)hipFree(q);
         for (auto &q : landed) (void)hipFree(q.first);
-        for (void *q : b2mem) if (q) (void)hipFree(q);
-        for (void *q : c2mem) if (q) (void)hipFree(q);
-        for (void *q : bnmem) if (q) (void)hipFree(q);
-        for (auto &row : bgmem) for (void *q : row) if (q) (void)hipFree(q);
+        each([](auto &r) { r.release(); });
     }
 };
 
@@ -544,15 +557,7 @@ Col transposed_col(const T *src, int k, int64_t m, void **dst, UploadScan *scan,
         T *o = (T *)out;
         const size_t e = off / sizeof(T), cnt = len / sizeof(T);
         bool ok = true; T mx = T(0);
-        switch (k) {
-        case 2: transpose_fill<T, 2>(o, src, m, e, cnt, pred, ok, mx); break;
-        case 3: transpose_fill<T, 3>(o, src, m, e, cnt, pred, ok, mx); break;
-        case 4: transpose_fill<T, 4>(o, src, m, e, cnt, pred, ok, mx); break;
-        case 5: transpose_fill<T, 5>(o, src, m, e, cnt, pred, ok, mx); break;
-        case 6: transpose_fill<T, 6>(o, src, m, e, cnt, pred, ok, mx); break;
-        case 7: transpose_fill<T, 7>(o, src, m, e, cnt, pred, ok, mx); break;
-        default: transpose_fill<T, 8>(o, src, m, e, cnt, pred, ok, mx); break;
-        }
+        with_int<2, 8>(k, [&](auto K) { transpose_fill<T, K>(o, src, m, e, cnt, pred, ok, mx); });
         if (!ok) scan->bad.store(true, std::memory_order_relaxed);
         if (track_max) scan->fold((double)mx, 1.0);
     };
@@ -700,14 +705,27 @@ int download_staged(cfmm_ctx *ctx, void *host_dst, const void *dev_src, size_t b
     return CFMM_OK;
 }
 
+// the common tail of the read-backs: scratch for cnt tenders and as many multipliers, launch(dd, dl) filling it, the staged downloads
+template <class Launch> int read_back(cfmm_ctx *ctx, const char *who, size_t cnt, double *delta, double *lambda, Launch &&launch)
+{
+    double *dd = nullptr, *dl = nullptr;
+    { int rc = trade_scratch(ctx, cnt, &dd, &dl); if (rc) return rc; }
+    launch(dd, dl);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, CFMM_E_HIP, "%s -> %s", who, hipGetErrorString(e));
+    if (delta) { int rc = download_staged(ctx, delta, dd, cnt * sizeof(double)); if (rc) return rc; }
+    if (lambda) { int rc = download_staged(ctx, lambda, dl, cnt * sizeof(double)); if (rc) return rc; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CFMM_OK;
+}
+
 // largest reserve / smallest fee over this context's pools (the fixed-point exponent of the reproducible mode)
 void local_extrema(cfmm_ctx *ctx)
 {
     ctx->max_reserve = 0.0; ctx->min_fee = 1.0;
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) if (ctx->pools->b2[k].m) { ctx->max_reserve = std::max(ctx->max_reserve, ctx->pools->mxr2[k]); ctx->min_fee = std::min(ctx->min_fee, ctx->pools->mnf2[k]); }
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) if (ctx->pools->bn[k].m) { ctx->max_reserve = std::max(ctx->max_reserve, ctx->pools->mxrn[k]); ctx->min_fee = std::min(ctx->min_fee, ctx->pools->mnfn[k]); }
-    for (int q = 0; q < CFMM_POOLK_KINDS; ++q) for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k)
-        if (ctx->pools->bg[q][k].m) { ctx->max_reserve = std::max(ctx->max_reserve, ctx->pools->mxrg[q][k]); ctx->min_fee = std::min(ctx->min_fee, ctx->pools->mnfg[q][k]); }
+    ctx->pools->each([ctx](const auto &r) {
+        if (r.b.m) { ctx->max_reserve = std::max(ctx->max_reserve, r.mxr); ctx->min_fee = std::min(ctx->min_fee, r.mnf); }
+    });
     ctx->g_max_reserve = ctx->max_reserve;
 }
 
@@ -793,15 +811,15 @@ void det_scales(cfmm_ctx *ctx, double &sc, double &scd)
 static bool wide_tiles(const cfmm_ctx *ctx)
 {
     static const int wide_mode = getenv("CFMM_WIDE") ? atoi(getenv("CFMM_WIDE")) : -1;
-    return !CFMM_STAGED_WALK && !ctx->det && (wide_mode > 0 || (wide_mode < 0 && ctx->pools->b2[CFMM_POOL_CP2].m >= 8000000));
+    return !CFMM_STAGED_WALK && !ctx->det && (wide_mode > 0 || (wide_mode < 0 && ctx->pools->r2[CFMM_POOL_CP2].b.m >= 8000000));
 }
 // `big`: the caller launches through launch_eval / enqueue_fused_iteration, which pick the instantiation by large_set_mode()
 EvalArgs make_eval_args(cfmm_ctx *ctx, bool stable, int only = 0x7fffffff, bool big = true)
 {
     EvalArgs a = {};
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) a.b2[k] = ctx->pools->b2[k];
+    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) a.b2[k] = ctx->pools->r2[k].b;
     a.b2[CFMM_POOL_SUM2].flags = ctx->flags2;
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) a.bn[k - 3] = ctx->pools->bn[k];
+    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) a.bn[k - 3] = ctx->pools->rn[k].b;
     // wide constant-product tiles (kernels.hpp: EvalArgs::wide): for a bucket whose evaluation is bound by memory latency -- 4.8 ns per
     // 1000 pools whatever level serves them, 64 KB in flight per CU -- twice the bytes in flight per wave: 4e7 pools 192 -> 166 us,
     // 1e7 pools 40.5 -> 39.4; at 1.25e6 pools (the C4 shard) and at C3 the narrower tiles win.  CFMM_WIDE = 0 / 1 for A/B.
@@ -809,7 +827,7 @@ EvalArgs make_eval_args(cfmm_ctx *ctx, bool stable, int only = 0x7fffffff, bool 
     long long tiles = 0;
     for (int q = 0; q < N_BUCKETS; ++q) {
         const int code = kOrder[q];
-        const long long m = code < 0 ? ctx->pools->bn[-code].m : ctx->pools->b2[code].m;
+        const long long m = code < 0 ? ctx->pools->rn[-code].b.m : ctx->pools->r2[code].b.m;
         const int wt = (code == CFMM_POOL_CP2 && a.wide) ? WT_WIDE : wave_tile_pools(code);
         if ((only == 0x7fffffff || only == code) && ((code >= 0 && heavy_kind(code)) == stable)) tiles += (m + wt - 1) / wt;
         a.tile_end[q] = (int)tiles;
@@ -846,8 +864,8 @@ static bool pingpong_on(const cfmm_ctx *ctx)
     static const int mode = getenv("CFMM_PINGPONG") ? atoi(getenv("CFMM_PINGPONG")) : -1;      // (A/B: 0 never, 1 always)
     if (mode >= 0) return mode != 0;
     double b2 = 0.0, bn = 0.0;
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) b2 += (double)ctx->pools->b2[k].m * ((k == CFMM_POOL_CP2 || k == CFMM_POOL_SUM2) ? 32.0 : 40.0);
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) bn += (double)ctx->pools->bn[k].m * (20.0 + 20.0 * k);
+    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) b2 += (double)ctx->pools->r2[k].b.m * ((k == CFMM_POOL_CP2 || k == CFMM_POOL_SUM2) ? 32.0 : 40.0);
+    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) bn += (double)ctx->pools->rn[k].b.m * (20.0 + 20.0 * k);
     return bn <= 0.1 * (b2 + bn);
 }
 
@@ -858,8 +876,8 @@ static bool stream_nt(const cfmm_ctx *ctx)
     static const int mode = getenv("CFMM_NT") ? atoi(getenv("CFMM_NT")) : -1;       // (A/B: 0 never, 1 always)
     if (mode >= 0) return mode != 0 && !ctx->det;
     double bytes = 0.0;
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) if (!heavy_kind(k)) bytes += (double)ctx->pools->b2[k].m * ((k == CFMM_POOL_CP2 || k == CFMM_POOL_SUM2) ? 32.0 : 40.0);
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) bytes += (double)ctx->pools->bn[k].m * (20.0 + 20.0 * k);
+    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) if (!heavy_kind(k)) bytes += (double)ctx->pools->r2[k].b.m * ((k == CFMM_POOL_CP2 || k == CFMM_POOL_SUM2) ? 32.0 : 40.0);
+    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) bytes += (double)ctx->pools->rn[k].b.m * (20.0 + 20.0 * k);
     return !ctx->det && bytes > 2.0 * 256.0 * 1048576.0;
 }
 // The instantiation of eval_kernel / iter_kernel for this pool set (their NT parameter):
@@ -872,7 +890,7 @@ static int large_set_mode(const cfmm_ctx *ctx)
     if (ctx->det) return 0;
     if (stream_nt(ctx)) return 1;
     bool mirror = false;
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) mirror = mirror || ctx->pools->c2mem[k] != nullptr;
+    for (auto &r : ctx->pools->r2) mirror = mirror || r.cmem != nullptr;
     return (mirror || wide_tiles(ctx)) ? 2 : 0;
 }
 static bool eval_dma(const cfmm_ctx *ctx, bool with_d) { return CFMM_STAGED_WALK && ctx->tile_dma && !ctx->det && eval_lds_bytes(ctx->n, with_d, false, true) <= LDS_MAX; }
@@ -912,7 +930,7 @@ int det_finish(cfmm_ctx *ctx, double *out, const double *nu, bool with_d)
 int64_t heavy_pools(const cfmm_ctx *ctx)
 {
     int64_t m = 0;
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) if (heavy_kind(k)) m += ctx->pools->b2[k].m;
+    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) if (heavy_kind(k)) m += ctx->pools->r2[k].b.m;
     return m;
 }
 
@@ -920,7 +938,7 @@ int64_t heavy_pools(const cfmm_ctx *ctx)
 int64_t table_pools(const cfmm_ctx *ctx)
 {
     int64_t m = 0;
-    for (auto &row : ctx->pools->bg) for (auto &b : row) m += b.m;
+    for (auto &row : ctx->pools->rg) for (auto &r : row) m += r.b.m;
     return m;
 }
 // ... of which the constant-sum entry's (piecewise linear: the second-order path has no smoothing for them; the stableswap entry enters it
@@ -928,7 +946,7 @@ int64_t table_pools(const cfmm_ctx *ctx)
 int64_t table_sum_pools(const cfmm_ctx *ctx)
 {
     int64_t m = 0;
-    for (auto &b : ctx->pools->bg[CFMM_POOLK_SUM]) m += b.m;
+    for (auto &r : ctx->pools->rg[CFMM_POOLK_SUM]) m += r.b.m;
     return m;
 }
 // both read the prices (and the stop flag) the evaluation / iteration launch in front of them has left in `nu`
@@ -942,7 +960,7 @@ TableArgs make_table_args(cfmm_ctx *ctx, const double *nu, double *acc)
     long long tiles = 0;
     for (int q = 0; q < 2; ++q)
         for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) {
-            const BucketG &b = ctx->pools->bg[q == 0 ? CFMM_POOLK_STABLE : CFMM_POOLK_SUM][k];
+            const BucketG &b = ctx->pools->rg[q == 0 ? CFMM_POOLK_STABLE : CFMM_POOLK_SUM][k].b;
             (q == 0 ? a.bs : a.bq)[k - 2] = b;
             if (q == 1) a.qflags[k - 2] = ctx->flagsG[k];
             const int P = 64 / k;
@@ -1430,7 +1448,7 @@ int refresh_global_counts(cfmm_ctx *ctx)
     //  communicator, the exchange or the reproducible mode -- calls every rank makes alike -- and are kept until then)
     if (sharded(ctx) && ctx->g_counts_valid) return CFMM_OK;
     ctx->g_total = cfmm_pool_count(ctx);
-    ctx->g_stable = ctx->pools->b2[CFMM_POOL_CURVE2].m;
+    ctx->g_stable = ctx->pools->r2[CFMM_POOL_CURVE2].b.m;
     ctx->g_table = table_sum_pools(ctx);       // (what the second-order path refuses: the method choice must agree across ranks)
     local_extrema(ctx);
     if (!sharded(ctx)) return CFMM_OK;
@@ -1524,7 +1542,7 @@ int smooth_buffers(cfmm_ctx *ctx, bool hess)
         if ((rc = set_lds_attr(ctx, smooth_kernel<true>, smooth_lds_bytes(n, true)))) return rc;
     }
     for (int k : {CFMM_POOL_CP2, CFMM_POOL_W2, CFMM_POOL_CURVE2, CFMM_POOL_POW2}) {           // warm starts: sized by the bucket as it is NOW (pools may be re-uploaded)
-        const long long m = ctx->pools->b2[k].m;
+        const long long m = ctx->pools->r2[k].b.m;
         if (ctx->sm_ws_m[k] == m) continue;
         if (ctx->sm_ws[k]) { (void)hipFree(ctx->sm_ws[k]); ctx->sm_ws[k] = nullptr; }
         ctx->sm_ws_m[k] = 0;
@@ -1553,7 +1571,7 @@ int launch_smooth(cfmm_ctx *ctx, double mu, bool hess, bool warm, bool with_slo,
 {
     const int n = ctx->n;
     SmoothArgs a = {};
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) a.b2[k] = ctx->pools->b2[k];
+    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) a.b2[k] = ctx->pools->r2[k].b;
     a.b2[CFMM_POOL_SUM2].flags = ctx->flags2;
     for (int k = 0; k < CFMM_POOL_KINDS2; ++k) a.ws[k] = warm ? ctx->sm_ws[k] : nullptr;
     const int order[CFMM_POOL_KINDS2] = {CFMM_POOL_CURVE2, CFMM_POOL_POW2, CFMM_POOL_W2, CFMM_POOL_CP2, CFMM_POOL_SUM2};
@@ -1576,17 +1594,14 @@ int launch_smooth(cfmm_ctx *ctx, double mu, bool hess, bool warm, bool with_slo,
     }
     // k-asset geo-mean pools: exact solutions and their exact Hessian blocks on top
     for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) {
-        const BucketN &bn = ctx->pools->bn[k];
+        const BucketN &bn = ctx->pools->rn[k].b;
         if (!bn.m) continue;
         const dim3 g2((unsigned)std::min<long long>((bn.m + 255) / 256, 8LL * ctx->cus)), blk(256);
         const double *nup = ctx->nu;
-#define GN_LAUNCH(KK) do { if (hess) hipLaunchKernelGGL((gn_newton_kernel<KK, true>), g2, blk, 0, ctx->stream, bn, nup, a.slo, ctx->sm_out, n, ctx->H, a.ldh); \
-                           else hipLaunchKernelGGL((gn_newton_kernel<KK, false>), g2, blk, 0, ctx->stream, bn, nup, a.slo, ctx->sm_out, n, (double *)nullptr, a.ldh); } while (0)
-        switch (k) {
-        case 3: GN_LAUNCH(3); break; case 4: GN_LAUNCH(4); break; case 5: GN_LAUNCH(5); break;
-        case 6: GN_LAUNCH(6); break; case 7: GN_LAUNCH(7); break; default: GN_LAUNCH(8); break;
-        }
-#undef GN_LAUNCH
+        with_int<3, 8>(k, [&](auto K) {
+            if (hess) hipLaunchKernelGGL((gn_newton_kernel<K, true>), g2, blk, 0, ctx->stream, bn, nup, a.slo, ctx->sm_out, n, ctx->H, a.ldh);
+            else hipLaunchKernelGGL((gn_newton_kernel<K, false>), g2, blk, 0, ctx->stream, bn, nup, a.slo, ctx->sm_out, n, (double *)nullptr, a.ldh);
+        });
     }
     // the K-asset table's stableswap pools likewise: ONE launch of the table's wave-tiles (phik.hpp: table_newton_kernel)
     {
@@ -1604,14 +1619,14 @@ int launch_smooth(cfmm_ctx *ctx, double mu, bool hess, bool warm, bool with_slo,
     }
     // ... and its constant-sum pools, smoothed in price space with the path's barrier weight (phik.hpp: gk_sum_newton_kernel)
     for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) {
-        const BucketG &bq = ctx->pools->bg[CFMM_POOLK_SUM][k];
+        const BucketG &bq = ctx->pools->rg[CFMM_POOLK_SUM][k].b;
         if (!bq.m) continue;
         const dim3 g2((unsigned)std::min<long long>((bq.m + 255) / 256, 8LL * ctx->cus)), blk(256);
         const double *nup = ctx->nu;
-#define GQ_LAUNCH(KK) case KK: if (hess) hipLaunchKernelGGL((gk_sum_newton_kernel<KK, true>), g2, blk, 0, ctx->stream, bq, nup, a.slo, mu, ctx->sm_out, n, ctx->H, a.ldh); \
-                           else hipLaunchKernelGGL((gk_sum_newton_kernel<KK, false>), g2, blk, 0, ctx->stream, bq, nup, a.slo, mu, ctx->sm_out, n, (double *)nullptr, a.ldh); break;
-        switch (k) { GQ_LAUNCH(2) GQ_LAUNCH(3) GQ_LAUNCH(4) GQ_LAUNCH(5) GQ_LAUNCH(6) GQ_LAUNCH(7) default: GQ_LAUNCH(8) }
-#undef GQ_LAUNCH
+        with_int<2, 8>(k, [&](auto K) {
+            if (hess) hipLaunchKernelGGL((gk_sum_newton_kernel<K, true>), g2, blk, 0, ctx->stream, bq, nup, a.slo, mu, ctx->sm_out, n, ctx->H, a.ldh);
+            else hipLaunchKernelGGL((gk_sum_newton_kernel<K, false>), g2, blk, 0, ctx->stream, bq, nup, a.slo, mu, ctx->sm_out, n, (double *)nullptr, a.ldh);
+        });
     }
     HIP_TRY(ctx, hipGetLastError());
     if (sharded(ctx)) {                     // pool-sharded: every rank needs the whole [psi | value | trade] and the whole Hessian
@@ -1642,9 +1657,9 @@ int listed_tokens(cfmm_ctx *ctx)
         hipLaunchKernelGGL(mark_tokens_kernel, dim3(grid), dim3(256), 0, ctx->stream, ids, count, mark);
     };
     const PoolStore &ps = *ctx->pools;
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) { pass(ps.b2[k].ia, ps.b2[k].m); pass(ps.b2[k].ib, ps.b2[k].m); }
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) pass(ps.bn[k].idx, (long long)k * ps.bn[k].m);
-    for (auto &row : ps.bg) for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) pass(row[k].idx, (long long)k * row[k].m);
+    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) { pass(ps.r2[k].b.ia, ps.r2[k].b.m); pass(ps.r2[k].b.ib, ps.r2[k].b.m); }
+    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) pass(ps.rn[k].b.idx, (long long)k * ps.rn[k].b.m);
+    for (auto &row : ps.rg) for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) pass(row[k].b.idx, (long long)k * row[k].b.m);
     HIP_TRY(ctx, hipGetLastError());
     if (sharded(ctx)) { int rc = all_reduce(ctx, mark, (size_t)n, NCCL_FLOAT64, NCCL_SUM); if (rc) return rc; }
     std::vector<double> h(n);
@@ -1730,7 +1745,7 @@ int solve_newton(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out, int evals_b
     if (!pin_scratch(ctx, 8 * (size_t)n + 64 + n + (size_t)acc_stride(n))) return fail(ctx, CFMM_E_HIP, "pinned staging (%d tokens)", n);      // (the loop's part + cfmm_eval_dual's: no regrowth inside the loop)
     if (ctx->lean_io) {                          // the start prices up; the warm starts of the per-direction solves zeroed (handoff.hpp)
         IoList z;
-        for (int k = 0; k < CFMM_POOL_KINDS2; ++k) if (ctx->sm_ws[k]) z.zero(ctx->sm_ws[k], 2 * (size_t)ctx->pools->b2[k].m * sizeof(double));
+        for (int k = 0; k < CFMM_POOL_KINDS2; ++k) if (ctx->sm_ws[k]) z.zero(ctx->sm_ws[k], 2 * (size_t)ctx->pools->r2[k].b.m * sizeof(double));
         if (z.a.njobs && (rc = launch_io(ctx, z, false))) return rc;
         IoList p;
         p.copy(pin_device(ctx, ctx->pin), ctx->nu_acc, n * sizeof(double));
@@ -1747,9 +1762,9 @@ int solve_newton(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out, int evals_b
     std::vector<char> listed(n);
     for (int j = 0; j < n; ++j) listed[j] = !(ct[j] < CFMM_ULOG && !ctx->listed[j] && h[j] == 0.0);
     long long nbar = 0;
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) nbar += 2 * ctx->pools->b2[k].m;
-    nbar += 2 * ctx->pools->b2[CFMM_POOL_SUM2].m;
-    for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) nbar += 3LL * k * ctx->pools->bg[CFMM_POOLK_SUM][k].m;      // (phik.hpp: the barrier-smoothed constant-sum entry, 3 K barrier terms)
+    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) nbar += 2 * ctx->pools->r2[k].b.m;
+    nbar += 2 * ctx->pools->r2[CFMM_POOL_SUM2].b.m;
+    for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) nbar += 3LL * k * ctx->pools->rg[CFMM_POOLK_SUM][k].b.m;      // (phik.hpp: the barrier-smoothed constant-sum entry, 3 K barrier terms)
     for (int j = 0; j < n; ++j) {
         mask[j] = ct[j] == CFMM_FREE || !listed[j];              // (a token the dual is flat in: its price stays where it starts)
         lob[j] = (ct[j] == CFMM_GE && c[j] > 0.0) ? std::log(c[j]) : -INFINITY;
@@ -1809,7 +1824,7 @@ int solve_newton(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out, int evals_b
 
     if (!ctx->lean_io)
         for (int k = 0; k < CFMM_POOL_KINDS2; ++k)
-            if (ctx->sm_ws[k]) HIP_TRY(ctx, hipMemsetAsync(ctx->sm_ws[k], 0, 2 * (size_t)ctx->pools->b2[k].m * sizeof(double), ctx->stream));
+            if (ctx->sm_ws[k]) HIP_TRY(ctx, hipMemsetAsync(ctx->sm_ws[k], 0, 2 * (size_t)ctx->pools->r2[k].b.m * sizeof(double), ctx->stream));
     if ((rc = exact(nu))) return rc;
     double dual = arb_x;
     for (int j = 0; j < n; ++j) dual += ct[j] >= CFMM_ULOG ? host_utility_term(ct[j], c[j], h[j], nu[j], 0.0).ubar : (nu[j] - c[j]) * h[j];
@@ -2371,9 +2386,7 @@ int64_t cfmm_pool_count(cfmm_ctx *ctx)
 {
     if (!ctx) return 0;
     int64_t m = 0;
-    for (auto &b : ctx->pools->b2) m += b.m;
-    for (auto &b : ctx->pools->bn) m += b.m;
-    for (auto &row : ctx->pools->bg) for (auto &b : row) m += b.m;
+    ctx->pools->each([&m](const auto &r) { m += r.b.m; });
     return m;
 }
 
@@ -2385,17 +2398,17 @@ int64_t cfmm_eval_bytes(cfmm_ctx *ctx)
     int64_t bytes = 0;
     for (int k = 0; k < CFMM_POOL_KINDS2; ++k) {
         const bool par = !(k == CFMM_POOL_CP2 || k == CFMM_POOL_SUM2);
-        const bool mirror = ctx->pools->c2mem[k] != nullptr && !ctx->det && !heavy_kind(k);
-        bytes += ctx->pools->b2[k].m * ((mirror ? 21 : 32) + (par ? 8 : 0));
+        const bool mirror = ctx->pools->r2[k].cmem != nullptr && !ctx->det && !heavy_kind(k);
+        bytes += ctx->pools->r2[k].b.m * ((mirror ? 21 : 32) + (par ? 8 : 0));
     }
     // K-asset geo-mean buckets: ids, reserves, weights per leg, fee and log fee per pool -- and, in every evaluation of a solve but
     // its first (outside the reproducible mode and the staged-walk variant), the derived column log(R / w) per leg that the tiles
     // read INSTEAD of recomputing it (kernels.hpp: tilen<LNU>): 8 more bytes per leg that do move
     const bool lrw = !ctx->det && !CFMM_STAGED_WALK;
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) bytes += ctx->pools->bn[k].m * (20 + (lrw ? 28 : 20) * k);
-    for (auto &row : ctx->pools->bg) {                  // the K-asset table's buckets: ids and reserves per leg, fee (and parameter) per pool
+    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) bytes += ctx->pools->rn[k].b.m * (20 + (lrw ? 28 : 20) * k);
+    for (auto &row : ctx->pools->rg) {                  // the K-asset table's buckets: ids and reserves per leg, fee (and parameter) per pool
         int k = 0;
-        for (auto &b : row) { bytes += b.m * (12 * k + (b.param ? 40 : 16)); ++k; }      // per pool: 1 / fee | alpha, s_R, warm start read and written  /  fee, 1 / fee
+        for (auto &r : row) { bytes += r.b.m * (12 * k + (r.b.param ? 40 : 16)); ++k; }      // per pool: 1 / fee | alpha, s_R, warm start read and written  /  fee, 1 / fee
     }
     return bytes;
 }
@@ -2419,10 +2432,11 @@ static char *reorder_arena(cfmm_ctx *ctx, size_t total, int64_t m, int **perm, u
     (void)hipMemsetAsync(*hist, 0, RO_KEYS * sizeof(unsigned), ctx->stream);
     return na;
 }
-static bool reorder_bucket2(cfmm_ctx *ctx, Bucket2 &b, void **arena, size_t total)
+static bool reorder_bucket2(cfmm_ctx *ctx, Resident2 &r)
 {
+    Bucket2 &b = r.b;
     int *perm; unsigned *hist;
-    char *old = (char *)*arena, *na = reorder_arena(ctx, total, b.m, &perm, &hist);
+    char *old = (char *)r.mem, *na = reorder_arena(ctx, r.ro, b.m, &perm, &hist);
     if (!na) return false;                             // (no memory for the second copy: the pools stay in the caller's order)
     auto sh = [&](const void *p) { return p ? (void *)(na + ((const char *)p - old)) : nullptr; };
     Cols2 d{(double *)sh(b.Ra), (double *)sh(b.Rb), (double *)sh(b.fee), (double *)sh(b.param), (int *)sh(b.ia), (int *)sh(b.ib)};
@@ -2432,28 +2446,27 @@ static bool reorder_bucket2(cfmm_ctx *ctx, Bucket2 &b, void **arena, size_t tota
     hipLaunchKernelGGL(ro_scan_kernel, dim3(1), dim3(64), 0, ctx->stream, hist);
     hipLaunchKernelGGL(ro_scatter2_kernel, dim3(grid), dim3(RO_THREADS), 0, ctx->stream, b, d, perm, bsz, hist);
     b.Ra = d.Ra; b.Rb = d.Rb; b.fee = d.fee; b.param = d.param; b.ia = d.ia; b.ib = d.ib; b.perm = perm;
-    *arena = na;
+    r.mem = na;
     return true;
 }
-static bool reorder_bucketN(cfmm_ctx *ctx, int k, BucketN &b, void **arena, size_t total)
+static bool reorder_bucketN(cfmm_ctx *ctx, int k, Resident<BucketN> &r)
 {
+    BucketN &b = r.b;
     int *perm; unsigned *hist;
-    char *old = (char *)*arena, *na = reorder_arena(ctx, total, b.m, &perm, &hist);
+    char *old = (char *)r.mem, *na = reorder_arena(ctx, r.ro, b.m, &perm, &hist);
     if (!na) return false;
     auto sh = [&](const void *p) { return (void *)(na + ((const char *)p - old)); };
     ColsN d{(int *)sh(b.idx), (double *)sh(b.R), (double *)sh(b.w), (double *)sh(b.fee), (double *)sh(b.lfee), (double *)sh(b.lrw)};
     const int bsz = (ctx->n + RO_NB - 1) / RO_NB;
     const int per = RO_THREADS * RO_PER, grid = (int)((b.m + per - 1) / per);
     const dim3 gh(std::min(grid, 2048)), gs(grid), blk(RO_THREADS);
-    switch (k) {
-#define RO_CASE(KK) case KK: hipLaunchKernelGGL(ro_hist_kernel<KK>, gh, blk, 0, ctx->stream, b.idx, (const int *)nullptr, (long long)b.m, bsz, hist); \
-                             hipLaunchKernelGGL(ro_scan_kernel, dim3(1), dim3(64), 0, ctx->stream, hist); \
-                             hipLaunchKernelGGL(ro_scatterN_kernel<KK>, gs, blk, 0, ctx->stream, b, d, perm, bsz, hist); break;
-    RO_CASE(3) RO_CASE(4) RO_CASE(5) RO_CASE(6) RO_CASE(7) default: RO_CASE(8)
-#undef RO_CASE
-    }
+    with_int<3, 8>(k, [&](auto K) {
+        hipLaunchKernelGGL(ro_hist_kernel<K>, gh, blk, 0, ctx->stream, b.idx, (const int *)nullptr, (long long)b.m, bsz, hist);
+        hipLaunchKernelGGL(ro_scan_kernel, dim3(1), dim3(64), 0, ctx->stream, hist);
+        hipLaunchKernelGGL(ro_scatterN_kernel<K>, gs, blk, 0, ctx->stream, b, d, perm, bsz, hist);
+    });
     b.idx = d.idx; b.R = d.R; b.w = d.w; b.fee = d.fee; b.lfee = d.lfee; b.lrw = d.lrw; b.perm = perm;
-    *arena = na;
+    r.mem = na;
     return true;
 }
 
@@ -2466,9 +2479,10 @@ static void build_compact_mirrors(cfmm_ctx *ctx, PoolStore &ps)
     static const int mode = getenv("CFMM_COMPACT") ? atoi(getenv("CFMM_COMPACT")) : -1;
     if (mode == 0 || ctx->n > 65536) return;
     for (int k : {CFMM_POOL_CP2, CFMM_POOL_W2, CFMM_POOL_SUM2}) {
-        Bucket2 &b = ps.b2[k];
-        if (ps.c2tried[k] || b.m == 0 || (mode < 0 && b.m < 1000000)) continue;
-        ps.c2tried[k] = true;
+        Resident2 &r = ps.r2[k];
+        Bucket2 &b = r.b;
+        if (r.ctried || b.m == 0 || (mode < 0 && b.m < 1000000)) continue;
+        r.ctried = true;
         const size_t m = (size_t)b.m, off_fee = (4 * m + 255) & ~(size_t)255, off_tab = (off_fee + m + 255) & ~(size_t)255;
         char *mem = nullptr;
         if (hipMalloc((void **)&mem, off_tab + 256 * 8 + 64) != hipSuccess) { (void)hipGetLastError(); continue; }
@@ -2479,7 +2493,7 @@ static void build_compact_mirrors(cfmm_ctx *ctx, PoolStore &ps)
         int over = 1;
         if (hipMemcpyAsync(&over, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) over = 1;
         if (over) { (void)hipGetLastError(); (void)hipFree(mem); continue; }      // more than 256 distinct fees: the bucket keeps its columns
-        ps.c2mem[k] = mem;
+        r.cmem = mem;
         b.cid = (const unsigned *)mem; b.cfee = (const unsigned char *)(mem + off_fee); b.ctab = (const double *)(mem + off_tab);
     }
 }
@@ -2495,26 +2509,24 @@ static void pools_ready(cfmm_ctx *ctx)
         // the two-asset pools (C3: 1e5 K-asset pools, ~1400 stray legs per workgroup over 1000 tokens: the ordering bought
         // nothing there and cost 0.4 ms on the first solve).  Then the buckets stay in the caller's order.
         bool pending = false;
-        for (size_t v : ps.ro2) pending |= v != 0;
-        for (size_t v : ps.ron) pending |= v != 0;
+        ps.each([&pending](const auto &r) { pending |= r.ro != 0; });
         if (!pending) return;
         double stray = 0.0;
-        for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) stray += (double)ps.bn[k].m * (k - 2);
+        for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) stray += (double)ps.rn[k].b.m * (k - 2);
         if (stray / (double)ctx->cus >= 0.5 * ctx->n) {
-            for (size_t &v : ps.ro2) v = 0;
-            for (size_t &v : ps.ron) v = 0;
+            ps.each([](auto &r) { r.ro = 0; });
             return;
         }
     }
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) if (ps.ro2[k]) {
-        void *old = ps.b2mem[k];
-        if (reorder_bucket2(ctx, ps.b2[k], &ps.b2mem[k], ps.ro2[k])) ps.landed.emplace_back(old, ctx->stream);
-        ps.ro2[k] = 0;
+    for (auto &r : ps.r2) if (r.ro) {
+        void *old = r.mem;
+        if (reorder_bucket2(ctx, r)) ps.landed.emplace_back(old, ctx->stream);
+        r.ro = 0;
     }
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) if (ps.ron[k]) {
-        void *old = ps.bnmem[k];
-        if (reorder_bucketN(ctx, k, ps.bn[k], &ps.bnmem[k], ps.ron[k])) ps.landed.emplace_back(old, ctx->stream);
-        ps.ron[k] = 0;
+    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) if (ps.rn[k].ro) {
+        void *old = ps.rn[k].mem;
+        if (reorder_bucketN(ctx, k, ps.rn[k])) ps.landed.emplace_back(old, ctx->stream);
+        ps.rn[k].ro = 0;
     }
 }
 // at the END of an entry point: the landing arenas whose permuted copies this context's stream enqueued go, behind a synchronisation
@@ -2563,6 +2575,27 @@ static const Kind2Info kKind2[CFMM_POOL_KINDS2] = {
     {"power sum", true, [](double x) { return x >= 1e-3 && x <= 0.999; }, "an exponent t in [0.001, 0.999]"},
 };
 
+extern "C++" {          // (templates need C++ linkage)
+// The start of every upload, behind its argument checks: the device; a store shared with a clone is refused (a clone may be reading the
+// arena on another stream, or hold captured launches that point into it); replacing a bucket waits for the kernels that may still read it.
+static int upload_begin(cfmm_ctx *ctx, const char *who, const void *old_arena)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ctx->pools.use_count() > 1) return fail(ctx, CFMM_E_STATE, "%s: the pools are shared with a clone (cfmm_clone); destroy the clones first", who);
+    if (old_arena) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CFMM_OK;
+}
+// ... and its end, once every column has arrived and passed its checks: the new bucket replaces the record's (the old arena, mirror and
+// inverse go).  A failed upload never gets here and leaves the previous pools, and everything derived from them, untouched.
+template <class R, class B> static void upload_install(cfmm_ctx *ctx, R &r, const B &b, void *arena, const UploadScan &scan, size_t ro_total)
+{
+    r.release();
+    r.b = b; r.mem = arena; r.ro = ro_total;
+    r.mxr = scan.mxr; r.mnf = scan.mnf;
+    pools_changed(ctx);
+}
+}  // extern "C++"
+
 int cfmm_upload_pools2(cfmm_ctx *ctx, int kind, int64_t m, const double *Ra, const double *Rb, const double *fee,
                        const double *param, const int32_t *ia, const int32_t *ib)
 {
@@ -2571,12 +2604,10 @@ int cfmm_upload_pools2(cfmm_ctx *ctx, int kind, int64_t m, const double *Ra, con
     if (m >= (1ll << 29)) return fail(ctx, CFMM_E_LIMIT, "upload_pools2: %lld pools in one bucket (the kernels address a column with 32-bit byte offsets: < 2^29)", (long long)m);
     if (m > 0 && (!Ra || !Rb || !fee || !ia || !ib)) return fail(ctx, CFMM_E_ARG, "upload_pools2: NULL column");
     if (m > 0 && kKind2[kind].needs_param && !param) return fail(ctx, CFMM_E_ARG, "upload_pools2: kind %d (%s) needs param", kind, kKind2[kind].name);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->pools.use_count() > 1) return fail(ctx, CFMM_E_STATE, "upload_pools2: the pools are shared with a clone (cfmm_clone); destroy the clones first");
-    if (ctx->pools->b2mem[kind]) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));       // (replacing a bucket kernels may still be reading)
-    // the new bucket is built first and swapped in only once every column has arrived and passed its checks: a failed
-    // upload leaves the previous pools (and everything derived from them) untouched.  The checks (ids, reserves, fee,
-    // parameter) and the extrema the reproducible mode needs ride on the staging copy: one pass over the caller's data.
+    Resident2 &r = ctx->pools->r2[kind];
+    { int rc = upload_begin(ctx, "upload_pools2", r.mem); if (rc) return rc; }
+    // the new bucket is built first and swapped in by upload_install.  The checks (ids, reserves, fee, parameter) and the
+    // extrema the reproducible mode needs ride on the staging copy: one pass over the caller's data.
     Bucket2 b = {};
     b.m = m;
     void *arena = nullptr;
@@ -2627,24 +2658,15 @@ int cfmm_upload_pools2(cfmm_ctx *ctx, int kind, int64_t m, const double *Ra, con
         if (rc) return rc;
         if (ro) ro_total = total;
     }
-    const double mxr = scan.mxr, mnf = scan.mnf;
-    if (ctx->pools->b2mem[kind]) (void)hipFree(ctx->pools->b2mem[kind]);
-    if (ctx->pools->c2mem[kind]) { (void)hipFree(ctx->pools->c2mem[kind]); ctx->pools->c2mem[kind] = nullptr; }
-    ctx->pools->c2tried[kind] = false;
-    if (ctx->pools->inv2[kind]) { (void)hipFree(ctx->pools->inv2[kind]); ctx->pools->inv2[kind] = nullptr; }
-    ctx->pools->b2mem[kind] = arena;
-    ctx->pools->b2[kind] = b;
     if (kind == CFMM_POOL_SUM2) {
         ctx->pools->hs_ia.clear(); ctx->pools->hs_ib.clear(); ctx->pools->hs_fee.clear(); ctx->pools->hs_Ra.clear(); ctx->pools->hs_Rb.clear();
         if (m > 0 && m <= 65536) {
             ctx->pools->hs_ia.assign(ia, ia + m); ctx->pools->hs_ib.assign(ib, ib + m); ctx->pools->hs_fee.assign(fee, fee + m);
             ctx->pools->hs_Ra.assign(Ra, Ra + m); ctx->pools->hs_Rb.assign(Rb, Rb + m);
         }
+        if (ctx->flags2) { (void)hipFree(ctx->flags2); ctx->flags2 = nullptr; }
     }
-    ctx->pools->ro2[kind] = ro_total;
-    ctx->pools->mxr2[kind] = mxr; ctx->pools->mnf2[kind] = mnf;
-    if (kind == CFMM_POOL_SUM2 && ctx->flags2) { (void)hipFree(ctx->flags2); ctx->flags2 = nullptr; }
-    pools_changed(ctx);
+    upload_install(ctx, r, b, arena, scan, ro_total);
     return CFMM_OK;
 }
 
@@ -2654,9 +2676,8 @@ int cfmm_upload_poolsN(cfmm_ctx *ctx, int k, int64_t m, const int32_t *idx, cons
     if (k < 3 || k > CFMM_MAX_POOL_SIZE || m < 0) return fail(ctx, CFMM_E_LIMIT, "upload_poolsN: pool size %d outside 3..%d", k, CFMM_MAX_POOL_SIZE);
     if ((long long)k * m >= (1ll << 29)) return fail(ctx, CFMM_E_LIMIT, "upload_poolsN: %lld legs in one bucket (the kernels address a column with 32-bit byte offsets: < 2^29)", (long long)k * m);
     if (m > 0 && (!idx || !R || !w || !fee)) return fail(ctx, CFMM_E_ARG, "upload_poolsN: NULL column");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->pools.use_count() > 1) return fail(ctx, CFMM_E_STATE, "upload_poolsN: the pools are shared with a clone (cfmm_clone); destroy the clones first");
-    if (ctx->pools->bnmem[k]) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // (replacing a bucket kernels may still be reading)
+    Resident<BucketN> &r = ctx->pools->rn[k];
+    { int rc = upload_begin(ctx, "upload_poolsN", r.mem); if (rc) return rc; }
     BucketN b = {};
     b.m = m;
     void *arena = nullptr;
@@ -2708,14 +2729,7 @@ int cfmm_upload_poolsN(cfmm_ctx *ctx, int k, int64_t m, const int32_t *idx, cons
         }
         if (ro) ro_total = total;
     }
-    const double mxr = scan.mxr, mnf = scan.mnf;
-    if (ctx->pools->bnmem[k]) (void)hipFree(ctx->pools->bnmem[k]);
-    if (ctx->pools->invn[k]) { (void)hipFree(ctx->pools->invn[k]); ctx->pools->invn[k] = nullptr; }
-    ctx->pools->bnmem[k] = arena;
-    ctx->pools->bn[k] = b;
-    ctx->pools->ron[k] = ro_total;
-    ctx->pools->mxrn[k] = mxr; ctx->pools->mnfn[k] = mnf;
-    pools_changed(ctx);
+    upload_install(ctx, r, b, arena, scan, ro_total);
     return CFMM_OK;
 }
 
@@ -2727,10 +2741,8 @@ int cfmm_upload_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t m, const int32_t 
     if (m > 0 && (!idx || !R || !fee)) return fail(ctx, CFMM_E_ARG, "upload_poolsG: null column");
     if (m > 0 && kind == CFMM_POOLK_STABLE && !param) return fail(ctx, CFMM_E_ARG, "upload_poolsG: stableswap pools need param = alpha");
     if (m > (1ll << 26)) return fail(ctx, CFMM_E_LIMIT, "upload_poolsG: a bucket holds < 2^26 pools");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // (as the two sibling uploaders: a clone may be reading the arena on another stream, or hold captured launches that point into it)
-    if (ctx->pools.use_count() > 1) return fail(ctx, CFMM_E_STATE, "upload_poolsG: the pools are shared with a clone (cfmm_clone); destroy the clones first");
-    if (ctx->pools->bgmem[kind][k]) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    Resident<BucketG> &r = ctx->pools->rg[kind][k];
+    { int rc = upload_begin(ctx, "upload_poolsG", r.mem); if (rc) return rc; }
     BucketG b = {};
     b.m = m;
     void *arena = nullptr;
@@ -2763,12 +2775,8 @@ int cfmm_upload_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t m, const int32_t 
         hipLaunchKernelGGL(gk_derive_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, b, k, d_ifee, d_sR, d_ws);
         HIP_TRY(ctx, hipGetLastError());
     }
-    if (ctx->pools->bgmem[kind][k]) (void)hipFree(ctx->pools->bgmem[kind][k]);
     if (kind == CFMM_POOLK_SUM && ctx->flagsG[k]) { (void)hipFree(ctx->flagsG[k]); ctx->flagsG[k] = nullptr; }
-    ctx->pools->bgmem[kind][k] = arena;
-    ctx->pools->mxrg[kind][k] = scan.mxr; ctx->pools->mnfg[kind][k] = scan.mnf;
-    ctx->pools->bg[kind][k] = b;
-    pools_changed(ctx);
+    upload_install(ctx, r, b, arena, scan, 0);
     return CFMM_OK;
 }
 
@@ -2847,51 +2855,70 @@ int update_check_reserves(cfmm_ctx *ctx, const char *who, const double *R, int64
     return CFMM_OK;
 }
 
-// the common frame of the three entry points: after the checks, under the store's lock
-//   launch(dev, offs, lowered)    enqueues the scatter of the staged parts
-//   reduce(out)                   enqueues the bucket's maximum into *out (zeroed)
-//   commit(mx)                    records the new maximum (and the host copies) once the writes are complete
-int update_run(cfmm_ctx *ctx, const char *who, const std::vector<UpdPart> &parts, const int *perm, int **inv, int64_t m, double mx_old, double mx_new,
-               const std::function<void(const char *, const std::vector<size_t> &, const int *, int *)> &launch,
-               const std::function<void(unsigned long long *)> &reduce, const std::function<void(double)> &commit, int64_t count)
-{
-    PoolStore &ps = *ctx->pools;
-    for (cfmm_ctx *s : ps.sharers) {
-        if (s == ctx) continue;
-        HIP_TRY(ctx, hipEventRecord(s->ev_pool, s->stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s->ev_pool, 0));
+// The common frame of the three entry points, behind their argument checks.  open(): the store entered as no reader (a pending
+// token-block ordering first: the positions go through its permutation), the empty-bucket refusal (`none` reports it), the store's
+// lock, the refusal while a context of the store reads the columns, the position check.  The caller then checks its values and calls
+// run(), still under the lock:
+//   launch(dev, offs, inv, lowered)   enqueues the scatter of the staged parts
+//   reduce(out)                       enqueues the bucket's maximum into *out (zeroed)
+// and run() records the new maximum once the writes are complete.
+extern "C++" template <class R> struct UpdateFrame {
+    cfmm_ctx *ctx;
+    const char *who;
+    R &r;
+    PoolEntry entry;
+    std::unique_lock<std::mutex> lock;
+    UpdateFrame(cfmm_ctx *c, const char *w, R &rec) : ctx(c), who(w), r(rec), entry(c, false), lock(entry.ps.mu, std::defer_lock) {}
+
+    template <class None> int open(int64_t count, const int32_t *pos, None &&none)
+    {
+        HIP_TRY(ctx, entry.device);
+        if (r.b.m == 0 && count > 0) return none();
+        lock.lock();
+        if (entry.ps.readers > 0) return fail(ctx, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve, evaluation or read-back", who);
+        return update_check_positions(ctx, who, r.b.m, count, pos);
     }
-    double mx = std::max(mx_old, mx_new);
-    if (count > 0) {
-        if (perm && !*inv) {
-            HIP_TRY(ctx, hipMalloc((void **)inv, (size_t)m * sizeof(int) + 16));
-            hipLaunchKernelGGL(upd_inverse_kernel, dim3((unsigned)std::min<int64_t>((m + UP_THREADS - 1) / UP_THREADS, 4096)), dim3(UP_THREADS), 0, ctx->stream, perm, (long long)m, *inv);
-            HIP_TRY(ctx, hipGetLastError());
+
+    template <class Launch, class Reduce>
+    int run(const std::vector<UpdPart> &parts, const int *perm, double mx_new, int64_t count, Launch &&launch, Reduce &&reduce)
+    {
+        const int64_t m = r.b.m;
+        for (cfmm_ctx *s : entry.ps.sharers) {
+            if (s == ctx) continue;
+            HIP_TRY(ctx, hipEventRecord(s->ev_pool, s->stream));
+            HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s->ev_pool, 0));
         }
-        std::vector<size_t> offs;
-        { int rc = update_stage(ctx, parts, offs); if (rc) return rc; }
-        int *lowered = (int *)ctx->upd_dev;
-        launch(ctx->upd_dev, offs, perm ? *inv : nullptr, lowered);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->upd_host, lowered, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (*(const int *)ctx->upd_host) {                 // a reserve equal to the bucket's maximum went down: reduce the bucket again
-            unsigned long long *out = (unsigned long long *)(ctx->upd_dev + 64);
-            reduce(out);
+        double mx = std::max(r.mxr, mx_new);
+        if (count > 0) {
+            if (perm && !r.inv) {
+                HIP_TRY(ctx, hipMalloc((void **)&r.inv, (size_t)m * sizeof(int) + 16));
+                hipLaunchKernelGGL(upd_inverse_kernel, dim3((unsigned)std::min<int64_t>((m + UP_THREADS - 1) / UP_THREADS, 4096)), dim3(UP_THREADS), 0, ctx->stream, perm, (long long)m, r.inv);
+                HIP_TRY(ctx, hipGetLastError());
+            }
+            std::vector<size_t> offs;
+            { int rc = update_stage(ctx, parts, offs); if (rc) return rc; }
+            int *lowered = (int *)ctx->upd_dev;
+            launch(ctx->upd_dev, offs, perm ? r.inv : nullptr, lowered);
             HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->upd_host, out, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->upd_host, lowered, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            double r; std::memcpy(&r, ctx->upd_host, sizeof r);
-            mx = std::max(r, mx_new);
+            if (*(const int *)ctx->upd_host) {                 // a reserve equal to the bucket's maximum went down: reduce the bucket again
+                unsigned long long *out = (unsigned long long *)(ctx->upd_dev + 64);
+                reduce(out);
+                HIP_TRY(ctx, hipGetLastError());
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->upd_host, out, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                double d; std::memcpy(&d, ctx->upd_host, sizeof d);
+                mx = std::max(d, mx_new);
+            }
+        } else {
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         }
-    } else {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        r.mxr = mx;
+        entry.ps.gen.fetch_add(1, std::memory_order_acq_rel);
+        return CFMM_OK;
     }
-    (void)who;
-    commit(mx);
-    ps.gen.fetch_add(1, std::memory_order_acq_rel);
-    return CFMM_OK;
-}
+};
 
 unsigned upd_grid(int64_t count) { return (unsigned)((count + UP_THREADS - 1) / UP_THREADS); }
 unsigned max_grid(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + UP_THREADS - 1) / UP_THREADS, 1024)); }
@@ -2905,37 +2932,32 @@ int cfmm_update_pools2(cfmm_ctx *ctx, int kind, int64_t count, const int32_t *po
     if (count > 0 && (!pos || !Ra || !Rb)) return fail(ctx, CFMM_E_ARG, "%s: NULL column", who);
     if (param && !kKind2[kind].needs_param) return fail(ctx, CFMM_E_ARG, "%s: kind %d (%s) has no parameter", who, kind, kKind2[kind].name);
     if (param && kind == CFMM_POOL_W2) return fail(ctx, CFMM_E_ARG, "%s: the weights of weighted pools cannot be updated (a re-upload)", who);
-    PoolEntry entry(ctx, false); HIP_TRY(ctx, entry.device);     // (a pending token-block ordering first: the positions go through its permutation)
-    PoolStore &ps = *ctx->pools;
-    const int64_t m = ps.b2[kind].m;
-    if (m == 0 && count > 0) return fail(ctx, CFMM_E_STATE, "%s: no %s pools uploaded", who, kKind2[kind].name);
-    std::lock_guard<std::mutex> guard(ps.mu);
-    if (ps.readers > 0) return fail(ctx, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve, evaluation or read-back", who);
-    { int rc = update_check_positions(ctx, who, m, count, pos); if (rc) return rc; }
+    UpdateFrame f(ctx, who, ctx->pools->r2[kind]);
+    { int rc = f.open(count, pos, [&] { return fail(ctx, CFMM_E_STATE, "%s: no %s pools uploaded", who, kKind2[kind].name); }); if (rc) return rc; }
     double mx_new = 0.0;
     { int rc = update_check_reserves(ctx, who, Ra, count, mx_new); if (rc) return rc; }
     { int rc = update_check_reserves(ctx, who, Rb, count, mx_new); if (rc) return rc; }
     if (param && kKind2[kind].param_ok)
         for (int64_t i = 0; i < count; ++i)
             if (!kKind2[kind].param_ok(param[i])) return fail(ctx, CFMM_E_ARG, "%s: entry %lld (%s) has parameter %g: expected %s", who, (long long)i, kKind2[kind].name, param[i], kKind2[kind].param_rule);
-    const Bucket2 b = ps.b2[kind];
-    const double mx_old = ps.mxr2[kind];
+    const Bucket2 b = f.r.b;
+    const int64_t m = b.m;
+    const double mx_old = f.r.mxr;
     std::vector<UpdPart> parts = {{pos, (size_t)count * 4}, {Ra, (size_t)count * 8}, {Rb, (size_t)count * 8}};
     if (param) parts.push_back({param, (size_t)count * 8});
     const int cnt = (int)count;
-    return update_run(ctx, who, parts, b.perm, &ps.inv2[kind], m, mx_old, mx_new,
+    int rc = f.run(parts, b.perm, mx_new, count,
         [&](const char *d, const std::vector<size_t> &o, const int *inv, int *low) {
             hipLaunchKernelGGL(upd_scatter2_kernel, dim3(upd_grid(count)), dim3(UP_THREADS), 0, ctx->stream, b, cnt, (const int *)(d + o[0]),
                                (const double *)(d + o[1]), (const double *)(d + o[2]), param ? (const double *)(d + o[3]) : nullptr, inv, mx_old, low);
         },
         [&](unsigned long long *out) {
             hipLaunchKernelGGL(upd_max_kernel, dim3(max_grid(2 * m)), dim3(UP_THREADS), 0, ctx->stream, b.Ra, (long long)m, b.Rb, (long long)m, out);
-        },
-        [&](double mx) {
-            ps.mxr2[kind] = mx;
-            if (kind == CFMM_POOL_SUM2 && (int64_t)ps.hs_Ra.size() == m)
-                for (int64_t i = 0; i < count; ++i) { ps.hs_Ra[pos[i]] = Ra[i]; ps.hs_Rb[pos[i]] = Rb[i]; }
-        }, count);
+        });
+    PoolStore &ps = *ctx->pools;
+    if (rc == CFMM_OK && kind == CFMM_POOL_SUM2 && (int64_t)ps.hs_Ra.size() == m)
+        for (int64_t i = 0; i < count; ++i) { ps.hs_Ra[pos[i]] = Ra[i]; ps.hs_Rb[pos[i]] = Rb[i]; }
+    return rc;
 }
 
 int cfmm_update_poolsN(cfmm_ctx *ctx, int k, int64_t count, const int32_t *pos, const double *R)
@@ -2944,28 +2966,23 @@ int cfmm_update_poolsN(cfmm_ctx *ctx, int k, int64_t count, const int32_t *pos, 
     if (!ctx) return CFMM_E_ARG;
     if (k < 3 || k > CFMM_MAX_POOL_SIZE || count < 0) return fail(ctx, CFMM_E_ARG, "%s: pool size %d outside 3..%d, or count %lld", who, k, CFMM_MAX_POOL_SIZE, (long long)count);
     if (count > 0 && (!pos || !R)) return fail(ctx, CFMM_E_ARG, "%s: NULL column", who);
-    PoolEntry entry(ctx, false); HIP_TRY(ctx, entry.device);
-    PoolStore &ps = *ctx->pools;
-    const int64_t m = ps.bn[k].m;
-    if (m == 0 && count > 0) return fail(ctx, CFMM_E_STATE, "%s: no geo-mean pools of %d assets uploaded", who, k);
-    std::lock_guard<std::mutex> guard(ps.mu);
-    if (ps.readers > 0) return fail(ctx, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve, evaluation or read-back", who);
-    { int rc = update_check_positions(ctx, who, m, count, pos); if (rc) return rc; }
+    UpdateFrame f(ctx, who, ctx->pools->rn[k]);
+    { int rc = f.open(count, pos, [&] { return fail(ctx, CFMM_E_STATE, "%s: no geo-mean pools of %d assets uploaded", who, k); }); if (rc) return rc; }
     double mx_new = 0.0;
     { int rc = update_check_reserves(ctx, who, R, (int64_t)k * count, mx_new); if (rc) return rc; }
-    const BucketN b = ps.bn[k];
-    const double mx_old = ps.mxrn[k];
+    const BucketN b = f.r.b;
+    const int64_t m = b.m;
+    const double mx_old = f.r.mxr;
     const std::vector<UpdPart> parts = {{pos, (size_t)count * 4}, {R, (size_t)count * k * 8}};
     const int cnt = (int)count;
-    return update_run(ctx, who, parts, b.perm, &ps.invn[k], m, mx_old, mx_new,
+    return f.run(parts, b.perm, mx_new, count,
         [&](const char *d, const std::vector<size_t> &o, const int *inv, int *low) {
             hipLaunchKernelGGL(upd_scatterN_kernel, dim3(upd_grid(count)), dim3(UP_THREADS), 0, ctx->stream, b, k, cnt, (const int *)(d + o[0]),
                                (const double *)(d + o[1]), inv, mx_old, low);
         },
         [&](unsigned long long *out) {
             hipLaunchKernelGGL(upd_max_kernel, dim3(max_grid((int64_t)k * m)), dim3(UP_THREADS), 0, ctx->stream, b.R, (long long)k * m, (const double *)nullptr, 0ll, out);
-        },
-        [&](double mx) { ps.mxrn[k] = mx; }, count);
+        });
 }
 
 int cfmm_update_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t count, const int32_t *pos, const double *R, const double *param)
@@ -2976,59 +2993,45 @@ int cfmm_update_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t count, const int3
         return fail(ctx, CFMM_E_ARG, "%s: kind %d, %d assets, count %lld", who, kind, k, (long long)count);
     if (count > 0 && (!pos || !R)) return fail(ctx, CFMM_E_ARG, "%s: NULL column", who);
     if (param && kind != CFMM_POOLK_STABLE) return fail(ctx, CFMM_E_ARG, "%s: constant-sum pools have no parameter", who);
-    PoolEntry entry(ctx, false); HIP_TRY(ctx, entry.device);
-    PoolStore &ps = *ctx->pools;
-    const int64_t m = ps.bg[kind][k].m;
-    if (m == 0 && count > 0) return fail(ctx, CFMM_E_STATE, "%s: no pools of kind %d with %d assets uploaded", who, kind, k);
-    std::lock_guard<std::mutex> guard(ps.mu);
-    if (ps.readers > 0) return fail(ctx, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve, evaluation or read-back", who);
-    { int rc = update_check_positions(ctx, who, m, count, pos); if (rc) return rc; }
+    UpdateFrame f(ctx, who, ctx->pools->rg[kind][k]);
+    { int rc = f.open(count, pos, [&] { return fail(ctx, CFMM_E_STATE, "%s: no pools of kind %d with %d assets uploaded", who, kind, k); }); if (rc) return rc; }
     double mx_new = 0.0;
     { int rc = update_check_reserves(ctx, who, R, (int64_t)k * count, mx_new); if (rc) return rc; }
     if (param)
         for (int64_t i = 0; i < count; ++i)
             if (!(param[i] > 0.0 && param[i] <= std::numeric_limits<double>::max())) return fail(ctx, CFMM_E_ARG, "%s: entry %lld has alpha %g (need > 0)", who, (long long)i, param[i]);
-    const BucketG b = ps.bg[kind][k];
-    const double mx_old = ps.mxrg[kind][k];
+    const BucketG b = f.r.b;
+    const int64_t m = b.m;
+    const double mx_old = f.r.mxr;
     std::vector<UpdPart> parts = {{pos, (size_t)count * 4}, {R, (size_t)count * k * 8}};
     if (param) parts.push_back({param, (size_t)count * 8});
     const int cnt = (int)count;
-    return update_run(ctx, who, parts, nullptr, nullptr, m, mx_old, mx_new,
+    return f.run(parts, nullptr, mx_new, count,
         [&](const char *d, const std::vector<size_t> &o, const int *, int *low) {
             hipLaunchKernelGGL(upd_scatterG_kernel, dim3(upd_grid(count)), dim3(UP_THREADS), 0, ctx->stream, b, k, cnt, (const int *)(d + o[0]),
                                (const double *)(d + o[1]), param ? (const double *)(d + o[2]) : nullptr, mx_old, low);
         },
         [&](unsigned long long *out) {
             hipLaunchKernelGGL(upd_max_kernel, dim3(max_grid((int64_t)k * m)), dim3(UP_THREADS), 0, ctx->stream, b.R, (long long)k * m, (const double *)nullptr, 0ll, out);
-        },
-        [&](double mx) { ps.mxrg[kind][k] = mx; }, count);
+        });
 }
 
 int cfmm_get_tradesG(cfmm_ctx *ctx, int kind, int k, double *delta, double *lambda)
 {
     if (!ctx || kind < 0 || kind >= CFMM_POOLK_KINDS || k < 2 || k > CFMM_MAX_POOL_SIZE) return CFMM_E_ARG;
     PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
-    const BucketG &b = ctx->pools->bg[kind][k];
+    const BucketG &b = ctx->pools->rg[kind][k].b;
     if (b.m == 0) return CFMM_OK;
-    const size_t cnt = (size_t)k * b.m;
-    double *dd = nullptr, *dl = nullptr;
-    { int rc = trade_scratch(ctx, cnt, &dd, &dl); if (rc) return rc; }
     const dim3 grid((unsigned)((b.m + GK_THREADS - 1) / GK_THREADS)), blk(GK_THREADS);
     const double *nu = ctx->nu_acc;
     const int *fl = kind == CFMM_POOLK_SUM ? ctx->flagsG[k] : nullptr;
     const double *slo = (ctx->pt.mu_last > 0.0 && ctx->pt.slo_active) ? ctx->sm_slo : nullptr;       // (as cfmm_get_tradesN)
     const double mu = ctx->pt.mu_last > 0.0 ? ctx->pt.mu_last : 0.0;     // (behind a second-order solve: the constant-sum entry's smoothed tenders)
-#define GK_T1(KIND_, KK) case KK: hipLaunchKernelGGL((tradesg_kernel<KIND_, KK>), grid, blk, 0, ctx->stream, b, fl, nu, slo, mu, dd, dl); break;
-#define GK_T(KIND_) switch (k) { GK_T1(KIND_, 2) GK_T1(KIND_, 3) GK_T1(KIND_, 4) GK_T1(KIND_, 5) GK_T1(KIND_, 6) GK_T1(KIND_, 7) default: hipLaunchKernelGGL((tradesg_kernel<KIND_, 8>), grid, blk, 0, ctx->stream, b, fl, nu, slo, mu, dd, dl); break; }
-    if (kind == CFMM_POOLK_STABLE) { GK_T(CFMM_POOLK_STABLE) } else { GK_T(CFMM_POOLK_SUM) }
-#undef GK_T1
-#undef GK_T
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ctx, CFMM_E_HIP, "get_tradesG -> %s", hipGetErrorString(e));
-    if (delta) { int rc = download_staged(ctx, delta, dd, cnt * sizeof(double)); if (rc) return rc; }
-    if (lambda) { int rc = download_staged(ctx, lambda, dl, cnt * sizeof(double)); if (rc) return rc; }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CFMM_OK;
+    return read_back(ctx, "get_tradesG", (size_t)k * b.m, delta, lambda, [&](double *dd, double *dl) {
+        with_int<CFMM_POOLK_STABLE, CFMM_POOLK_SUM>(kind, [&](auto KIND) {
+            with_int<2, 8>(k, [&](auto K) { hipLaunchKernelGGL((tradesg_kernel<KIND, K>), grid, blk, 0, ctx->stream, b, fl, nu, slo, mu, dd, dl); });
+        });
+    });
 }
 
 int cfmm_set_pool_flags(cfmm_ctx *ctx, int kind, const int32_t *flags)
@@ -3036,7 +3039,7 @@ int cfmm_set_pool_flags(cfmm_ctx *ctx, int kind, const int32_t *flags)
     if (!ctx) return CFMM_E_ARG;
     if (kind != CFMM_POOL_SUM2) return fail(ctx, CFMM_E_ARG, "set_pool_flags: only CFMM_POOL_SUM2 pools can be tied");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const Bucket2 &b = ctx->pools->b2[kind];
+    const Bucket2 &b = ctx->pools->r2[kind].b;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->flags2) { (void)hipFree(ctx->flags2); ctx->flags2 = nullptr; }
     ctx->g_valid = false;
@@ -3055,7 +3058,7 @@ int cfmm_set_pool_flagsG(cfmm_ctx *ctx, int k, const int32_t *flags)
 {
     if (!ctx || k < 2 || k > CFMM_MAX_POOL_SIZE) return ctx ? fail(ctx, CFMM_E_ARG, "set_pool_flagsG: %d assets", k) : CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const BucketG &b = ctx->pools->bg[CFMM_POOLK_SUM][k];
+    const BucketG &b = ctx->pools->rg[CFMM_POOLK_SUM][k].b;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->flagsG[k]) { (void)hipFree(ctx->flagsG[k]); ctx->flagsG[k] = nullptr; }
     ctx->g_valid = false;
@@ -3352,7 +3355,7 @@ static int solve_lbfgs(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out);
 static int solve_tiny_kinks(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out)
 {
     const int n = ctx->n;
-    const int64_t msum = ctx->pools->b2[CFMM_POOL_SUM2].m;
+    const int64_t msum = ctx->pools->r2[CFMM_POOL_SUM2].b.m;
     if (msum == 0 || ctx->is_clone || (int64_t)ctx->pools->hs_ia.size() != msum || ctx->general_utility || ctx->ng != n || ctx->flags2 || sharded(ctx) || ctx->det || o.pg_rule) return 0;
     {
         const EvalArgs ea = make_eval_args(ctx, false, 0x7fffffff, false);
@@ -3368,8 +3371,8 @@ static int solve_tiny_kinks(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out)
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     size_t tr_len = 0;
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) tr_len += 4 * (size_t)ctx->pools->b2[k].m;
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) tr_len += 2 * (size_t)k * ctx->pools->bn[k].m;
+    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) tr_len += 4 * (size_t)ctx->pools->r2[k].b.m;
+    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) tr_len += 2 * (size_t)k * ctx->pools->rn[k].b.m;
     std::vector<double> nu(n), psi(n), theta(msum), tr(tr_len);
     std::vector<int32_t> tsgn(msum), ct(ctx->hctype.begin(), ctx->hctype.begin() + n);
     cfmm_opts os = o;
@@ -3384,7 +3387,7 @@ static int solve_tiny_kinks(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out)
     if (rc) return rc;
     // psi_total = psi + sum theta d, the tied pools' tenders = theta x their full fill (cfmm.h: cfmm_solve_sweep)
     size_t off_sum = 0;
-    for (int k = 0; k < CFMM_POOL_SUM2; ++k) off_sum += 4 * (size_t)ctx->pools->b2[k].m;
+    for (int k = 0; k < CFMM_POOL_SUM2; ++k) off_sum += 4 * (size_t)ctx->pools->r2[k].b.m;
     double *dS = tr.data() + off_sum, *lS = dS + 2 * msum;                                  // delta [2][m] | lambda [2][m]
     for (int64_t i = 0; i < msum; ++i) {
         if (!std::isfinite(theta[i])) continue;
@@ -4124,7 +4127,7 @@ int cfmm_solve_sweep(cfmm_ctx *ctx, int B, const double *c, const double *h, con
         return fail(ctx, CFMM_E_UNSUPPORTED, "solve_sweep: serves networks one workgroup evaluates (<= %d tokens, <= %d wave-tiles, no stableswap / generic / K-asset table pools, "
                                              "one GPU, not the reproducible mode); solve the points one at a time or through cfmm_solve_batch", TINY_N, TINY_MAX_TILES);
     if (B > 4096) return fail(ctx, CFMM_E_LIMIT, "solve_sweep: %d points (at most 4096 per call)", B);
-    if (m_sum != ctx->pools->b2[CFMM_POOL_SUM2].m) return fail(ctx, CFMM_E_ARG, "solve_sweep: %lld constant-sum pools handed in, %lld uploaded", (long long)m_sum, (long long)ctx->pools->b2[CFMM_POOL_SUM2].m);
+    if (m_sum != ctx->pools->r2[CFMM_POOL_SUM2].b.m) return fail(ctx, CFMM_E_ARG, "solve_sweep: %lld constant-sum pools handed in, %lld uploaded", (long long)m_sum, (long long)ctx->pools->r2[CFMM_POOL_SUM2].b.m);
     if (m_sum > 0 && (!sum_ia || !sum_ib || !sum_fee || !sum_Ra || !sum_Rb || !theta_out || !tsgn_out)) return fail(ctx, CFMM_E_ARG, "solve_sweep: the constant-sum columns (and theta / tsgn) are needed when such pools exist");
     for (int p = 0; p < B; ++p) for (int j = 0; j < n; ++j) {
         const double cj = c[(size_t)p * n + j], v = nu0[(size_t)p * n + j];
@@ -4148,8 +4151,8 @@ int cfmm_solve_sweep(cfmm_ctx *ctx, int B, const double *c, const double *h, con
     const SweepLayout L(n, B, msum);
     // tenders: per point, for every non-empty bucket in the order two-asset kinds 0.., then K = 3..8: delta [k][m] | lambda [k][m]
     size_t tr_stride = 0;
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) tr_stride += 4 * (size_t)ctx->pools->b2[k].m;
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) tr_stride += 2 * (size_t)k * ctx->pools->bn[k].m;
+    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) tr_stride += 4 * (size_t)ctx->pools->r2[k].b.m;
+    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) tr_stride += 2 * (size_t)k * ctx->pools->rn[k].b.m;
     cfmm_sweep_buffers *sb;
     {
         std::lock_guard<std::mutex> g(g_sweep_mu);
@@ -4312,32 +4315,23 @@ int cfmm_solve_sweep(cfmm_ctx *ctx, int B, const double *c, const double *h, con
         size_t boff = 0;
         const dim3 blk(256);
         for (int k = 0; k < CFMM_POOL_KINDS2; ++k) {
-            Bucket2 b = ctx->pools->b2[k];
+            Bucket2 b = ctx->pools->r2[k].b;
             if (b.m == 0) continue;
             const dim3 grid((unsigned)((b.m + 255) / 256), (unsigned)B);
             double *dd = td + boff, *dl = dd + 2 * b.m;
-            switch (k) {
-            case 0: hipLaunchKernelGGL(trades2_sweep_kernel<0>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride, fl_d, fls); break;
-            case 1: hipLaunchKernelGGL(trades2_sweep_kernel<1>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride, fl_d, fls); break;
-            case 2: hipLaunchKernelGGL(trades2_sweep_kernel<2>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride, fl_d, fls); break;
-            case 3: hipLaunchKernelGGL(trades2_sweep_kernel<3>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride, fl_d, fls); break;
-            default: hipLaunchKernelGGL(trades2_sweep_kernel<4>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride, fl_d, fls); break;
-            }
+            with_int<0, 4>(k, [&](auto K) {
+                hipLaunchKernelGGL(trades2_sweep_kernel<K>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride, fl_d, fls);
+            });
             boff += 4 * (size_t)b.m;
         }
         for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) {
-            const BucketN &b = ctx->pools->bn[k];
+            const BucketN &b = ctx->pools->rn[k].b;
             if (b.m == 0) continue;
             const dim3 grid((unsigned)((b.m + 255) / 256), (unsigned)B);
             double *dd = td + boff, *dl = dd + (size_t)k * b.m;
-            switch (k) {
-            case 3: hipLaunchKernelGGL(tradesn_sweep_kernel<3>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride); break;
-            case 4: hipLaunchKernelGGL(tradesn_sweep_kernel<4>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride); break;
-            case 5: hipLaunchKernelGGL(tradesn_sweep_kernel<5>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride); break;
-            case 6: hipLaunchKernelGGL(tradesn_sweep_kernel<6>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride); break;
-            case 7: hipLaunchKernelGGL(tradesn_sweep_kernel<7>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride); break;
-            default: hipLaunchKernelGGL(tradesn_sweep_kernel<8>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride); break;
-            }
+            with_int<3, 8>(k, [&](auto K) {
+                hipLaunchKernelGGL(tradesn_sweep_kernel<K>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride);
+            });
             boff += 2 * (size_t)k * b.m;
         }
         HIP_TRY(ctx, hipGetLastError());
@@ -4379,73 +4373,42 @@ int cfmm_get_trades2(cfmm_ctx *ctx, int kind, double *delta, double *lambda)
 {
     if (!ctx || kind < 0 || kind >= CFMM_POOL_KINDS2) return CFMM_E_ARG;
     PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
-    Bucket2 b = ctx->pools->b2[kind];
+    Bucket2 b = ctx->pools->r2[kind].b;
     if (kind == CFMM_POOL_SUM2) b.flags = ctx->flags2;
     if (b.m == 0) return CFMM_OK;
     if (ctx->pt.tr_ovr_valid) {                 // the library's own kink loop left the tenders (solve_tiny_kinks)
         size_t off = 0;
-        for (int k = 0; k < kind; ++k) off += 4 * (size_t)ctx->pools->b2[k].m;
+        for (int k = 0; k < kind; ++k) off += 4 * (size_t)ctx->pools->r2[k].b.m;
         if (delta) std::memcpy(delta, ctx->pt.tr_ovr.data() + off, 2 * (size_t)b.m * sizeof(double));
         if (lambda) std::memcpy(lambda, ctx->pt.tr_ovr.data() + off + 2 * (size_t)b.m, 2 * (size_t)b.m * sizeof(double));
         return CFMM_OK;
     }
-    double *dd = nullptr, *dl = nullptr;
-    { int rc = trade_scratch(ctx, 2 * (size_t)b.m, &dd, &dl); if (rc) return rc; }
     const dim3 grid((unsigned)((b.m + 255) / 256)), blk(256);
-    if (ctx->pt.mu_last > 0.0) {           // after a second-order solve: the smoothed primal point
-        const double mu = ctx->pt.mu_last;
-        const double *slo = ctx->pt.slo_active ? ctx->sm_slo : nullptr;
-        switch (kind) {
-        case 0: hipLaunchKernelGGL(smooth_trades_kernel<0>, grid, blk, 0, ctx->stream, b, (const double *)ctx->nu_acc, slo, mu, dd, dl); break;
-        case 1: hipLaunchKernelGGL(smooth_trades_kernel<1>, grid, blk, 0, ctx->stream, b, (const double *)ctx->nu_acc, slo, mu, dd, dl); break;
-        case 2: hipLaunchKernelGGL(smooth_trades_kernel<2>, grid, blk, 0, ctx->stream, b, (const double *)ctx->nu_acc, slo, mu, dd, dl); break;
-        case 3: hipLaunchKernelGGL(smooth_trades_kernel<3>, grid, blk, 0, ctx->stream, b, (const double *)ctx->nu_acc, slo, mu, dd, dl); break;
-        default: hipLaunchKernelGGL(smooth_trades_kernel<4>, grid, blk, 0, ctx->stream, b, (const double *)ctx->nu_acc, slo, mu, dd, dl); break;
-        }
-    } else
-    switch (kind) {
-    case 0: hipLaunchKernelGGL(trades2_kernel<0>, grid, blk, 0, ctx->stream, b, (const double *)ctx->nu_acc, dd, dl); break;
-    case 1: hipLaunchKernelGGL(trades2_kernel<1>, grid, blk, 0, ctx->stream, b, (const double *)ctx->nu_acc, dd, dl); break;
-    case 2: hipLaunchKernelGGL(trades2_kernel<2>, grid, blk, 0, ctx->stream, b, (const double *)ctx->nu_acc, dd, dl); break;
-    case 3: hipLaunchKernelGGL(trades2_kernel<3>, grid, blk, 0, ctx->stream, b, (const double *)ctx->nu_acc, dd, dl); break;
-    default: hipLaunchKernelGGL(trades2_kernel<4>, grid, blk, 0, ctx->stream, b, (const double *)ctx->nu_acc, dd, dl); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ctx, CFMM_E_HIP, "get_trades2 -> %s", hipGetErrorString(e));
-    if (delta) { int rc = download_staged(ctx, delta, dd, 2 * b.m * sizeof(double)); if (rc) return rc; }
-    if (lambda) { int rc = download_staged(ctx, lambda, dl, 2 * b.m * sizeof(double)); if (rc) return rc; }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CFMM_OK;
+    const double *nu = ctx->nu_acc;
+    return read_back(ctx, "get_trades2", 2 * (size_t)b.m, delta, lambda, [&](double *dd, double *dl) {
+        with_int<0, 4>(kind, [&](auto K) {
+            if (ctx->pt.mu_last > 0.0) {           // after a second-order solve: the smoothed primal point
+                const double *slo = ctx->pt.slo_active ? ctx->sm_slo : nullptr;
+                hipLaunchKernelGGL(smooth_trades_kernel<K>, grid, blk, 0, ctx->stream, b, nu, slo, ctx->pt.mu_last, dd, dl);
+            } else hipLaunchKernelGGL(trades2_kernel<K>, grid, blk, 0, ctx->stream, b, nu, dd, dl);
+        });
+    });
 }
 
 int cfmm_get_tradesN(cfmm_ctx *ctx, int k, double *delta, double *lambda)
 {
     if (!ctx || k < 3 || k > CFMM_MAX_POOL_SIZE) return CFMM_E_ARG;
     PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
-    const BucketN &b = ctx->pools->bn[k];
+    const BucketN &b = ctx->pools->rn[k].b;
     if (b.m == 0) return CFMM_OK;
-    const size_t cnt = (size_t)k * b.m;
-    double *dd = nullptr, *dl = nullptr;
-    { int rc = trade_scratch(ctx, cnt, &dd, &dl); if (rc) return rc; }
     const dim3 grid((unsigned)((b.m + 255) / 256)), blk(256);
     const double *nu = ctx->nu_acc;
     // after a second-order solve that ended with low-order log-prices the k-asset pools were evaluated with them
     // (gn_newton_kernel): the tenders handed out must be those of the same point, or they would not sum to psi
     const double *slo = (ctx->pt.mu_last > 0.0 && ctx->pt.slo_active) ? ctx->sm_slo : nullptr;
-    switch (k) {
-    case 3: hipLaunchKernelGGL(tradesn_kernel<3>, grid, blk, 0, ctx->stream, b, nu, slo, dd, dl); break;
-    case 4: hipLaunchKernelGGL(tradesn_kernel<4>, grid, blk, 0, ctx->stream, b, nu, slo, dd, dl); break;
-    case 5: hipLaunchKernelGGL(tradesn_kernel<5>, grid, blk, 0, ctx->stream, b, nu, slo, dd, dl); break;
-    case 6: hipLaunchKernelGGL(tradesn_kernel<6>, grid, blk, 0, ctx->stream, b, nu, slo, dd, dl); break;
-    case 7: hipLaunchKernelGGL(tradesn_kernel<7>, grid, blk, 0, ctx->stream, b, nu, slo, dd, dl); break;
-    default: hipLaunchKernelGGL(tradesn_kernel<8>, grid, blk, 0, ctx->stream, b, nu, slo, dd, dl); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ctx, CFMM_E_HIP, "get_tradesN -> %s", hipGetErrorString(e));
-    if (delta) { int rc = download_staged(ctx, delta, dd, cnt * sizeof(double)); if (rc) return rc; }
-    if (lambda) { int rc = download_staged(ctx, lambda, dl, cnt * sizeof(double)); if (rc) return rc; }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CFMM_OK;
+    return read_back(ctx, "get_tradesN", (size_t)k * b.m, delta, lambda, [&](double *dd, double *dl) {
+        with_int<3, 8>(k, [&](auto K) { hipLaunchKernelGGL(tradesn_kernel<K>, grid, blk, 0, ctx->stream, b, nu, slo, dd, dl); });
+    });
 }
 
 int cfmm_comm_unique_id(void *uid128)
@@ -4770,7 +4733,7 @@ int cfmm_time_newton_kernels(cfmm_ctx *ctx, double mu, int reps, double *out4)
     HIP_TRY(ctx, hipMemcpyAsync(ctx->nu, ctx->nu_acc, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));       // (the accepted prices)
     HIP_TRY(ctx, hipMemsetAsync(ctx->sm_mask, 0, n * sizeof(int), ctx->stream));
     for (int k = 0; k < CFMM_POOL_KINDS2; ++k)
-        if (ctx->sm_ws[k]) HIP_TRY(ctx, hipMemsetAsync(ctx->sm_ws[k], 0, 2 * (size_t)ctx->pools->b2[k].m * sizeof(double), ctx->stream));
+        if (ctx->sm_ws[k]) HIP_TRY(ctx, hipMemsetAsync(ctx->sm_ws[k], 0, 2 * (size_t)ctx->pools->r2[k].b.m * sizeof(double), ctx->stream));
     float ms = 0.f;
     for (int which = 0; which < 2; ++which) {            // 0: with the Hessian, 1: without (warm-started from the first)
         if ((rc = launch_smooth(ctx, mu, which == 0, true, false))) return rc;
