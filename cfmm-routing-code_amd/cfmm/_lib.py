@@ -72,7 +72,7 @@ _lib = None
 
 SYMBOLS = ["cfmm_create", "cfmm_clone", "cfmm_destroy", "cfmm_last_error", "cfmm_backend", "cfmm_default_opts",
            "cfmm_upload_pools2", "cfmm_upload_poolsN", "cfmm_upload_poolsG", "cfmm_update_pools2", "cfmm_update_poolsN", "cfmm_update_poolsG", "cfmm_set_pool_flags", "cfmm_set_pool_flagsG", "cfmm_set_utility",
-           "cfmm_set_ties", "cfmm_set_deterministic", "cfmm_debug_eval_limbs", "cfmm_eval_dual", "cfmm_eval_smooth", "cfmm_debug_cholesky", "cfmm_debug_cholesky_apply", "cfmm_time_xcd_handoff", "cfmm_solve", "cfmm_solve_batch", "cfmm_batch_capacity", "cfmm_solve_sweep", "cfmm_get_nu", "cfmm_set_nu", "cfmm_get_psi",
+           "cfmm_set_ties", "cfmm_set_deterministic", "cfmm_debug_eval_limbs", "cfmm_eval_dual", "cfmm_eval_smooth", "cfmm_debug_cholesky", "cfmm_debug_cholesky_apply", "cfmm_time_xcd_handoff", "cfmm_solve", "cfmm_solve_batch", "cfmm_eval_dual_batch", "cfmm_batch_capacity", "cfmm_solve_sweep", "cfmm_get_nu", "cfmm_set_nu", "cfmm_get_psi",
            "cfmm_get_solution", "cfmm_get_trades2", "cfmm_get_tradesN", "cfmm_get_tradesG", "cfmm_comm_unique_id", "cfmm_comm_init",
            "cfmm_oneshot_export", "cfmm_oneshot_import", "cfmm_oneshot_attach", "cfmm_oneshot_mailbox", "cfmm_oneshot_enable",
            "cfmm_time_eval_kernel", "cfmm_time_collective", "cfmm_time_newton_kernels", "cfmm_selftest", "cfmm_debug_timers", "cfmm_clock_probe_start", "cfmm_clock_probe_read", "cfmm_clock_probe_stop", "cfmm_clock_probe_chain", "cfmm_pool_count", "cfmm_eval_bytes", "cfmm_stream"]
@@ -113,6 +113,7 @@ def lib():
     L.cfmm_time_xcd_handoff.argtypes = [vp, C.c_int, C.c_int, dp]
     L.cfmm_solve.argtypes = [vp, dp, C.POINTER(Opts), C.POINTER(Stats)]
     L.cfmm_solve_batch.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(dp), C.POINTER(Opts), C.POINTER(Stats)]
+    L.cfmm_eval_dual_batch.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(dp), dp, C.POINTER(dp)]
     L.cfmm_batch_capacity.argtypes = [C.c_int]
     L.cfmm_solve_sweep.argtypes = [vp, C.c_int, dp, dp, ip, dp, C.c_int64, ip, ip, dp, dp, dp, C.POINTER(Opts), C.c_double, C.c_int,
                                    dp, dp, dp, ip, dp, C.POINTER(Stats), ip]
@@ -362,6 +363,25 @@ class Context:
         st = (Stats * nb)()
         self._chk(self.L.cfmm_solve_batch(hs, nb, ptrs, C.byref(o), st))
         return [st[b].asdict() for b in range(nb)]
+
+    def eval_dual_batch(self, clones, nus):
+        """one dual evaluation at len(nus) price vectors in ONE pass over the pools (cfmm_eval_dual_batch: what solve_batch iterates
+        on), vector b on context b of [self] + clones.  Returns arb_sum [nb], psi [nb][n]."""
+        ctxs = [self] + list(clones)
+        nb = len(ctxs)
+        if len(nus) != nb:
+            raise ValueError(f"eval_dual_batch: {len(nus)} price vectors for {nb} contexts")
+        hs = (C.c_void_p * nb)(*[c.h for c in ctxs])
+        keep = [f64(a) for a in nus]
+        for a in keep:
+            if a.shape != (self.n,):
+                raise ValueError(f"eval_dual_batch: a price vector of shape {a.shape}, expected ({self.n},)")
+        psi = np.zeros((nb, self.n))
+        arb = np.zeros(nb)
+        ptrs = (C.POINTER(C.c_double) * nb)(*[_d(a) for a in keep])
+        outs = (C.POINTER(C.c_double) * nb)(*[_d(psi[b]) for b in range(nb)])
+        self._chk(self.L.cfmm_eval_dual_batch(hs, nb, ptrs, _d(arb), outs))
+        return arb, psi
 
     def solve_sweep(self, c, h, ctype, nu0, sum2=None, trades_per_point=0, kink_tol=1e-3, max_rounds=6, **kw):
         """B utilities over this context's (tiny) network in lock-step, the constant-sum kink loop included (cfmm_solve_sweep:

@@ -576,6 +576,9 @@ class HostComm:
 
 # ------------------------------------------------------------------------------- Problem
 AUTO_NEWTON_MIN_STABLE = 4096      # include/cfmm.h: CFMM_AUTO_NEWTON_MIN_STABLE
+# solve_many's default (batch=None) over networks with curve2 / pow2 / table stableswap pools: the batched path or the clone path.
+# Opt-in until tools/batch_timing.py --mix has shown the batched path faster (see the solve_many docstring).
+BATCH_SEARCH_POOLS_BY_DEFAULT = False
 
 
 def _drain_leg(code):
@@ -634,10 +637,16 @@ class Problem:
         """Solve the same pools under many utilities (the two-asset.py:34-100 sweep; independent baskets).  Returns one
         dict per utility, in order: value, status, psi, nu, gap, infeas, stats.
 
-        Batched (the default wherever it applies: first-order method, no constant-sum / stableswap pools, one GPU):
+        Batched (first-order method, no constant-sum pools, linear-plus-box utilities, one GPU: `_batch_applies`):
         `batch` solves at a time (default: as many as the LDS tile takes, 8 up to ~1100 tokens) run in lock-step through
         cfmm_solve_batch -- every outer iteration reads every pool column once for all of them.  With warm_start the
         solves of one group start from the prices the same slot reached in the previous group.
+        Networks with curve2 / pow2 pools or stableswap buckets of the K-asset table are taken too, under method="lbfgs" and
+        under "auto" below AUTO_NEWTON_MIN_STABLE stableswap pools (from there on "auto" means the second-order method: an
+        explicit `batch=` raises); under "auto" a member that ends without its certificates is re-solved alone, which hands it on
+        to the second-order method as `solve` does.  For these networks the batched path is opt-in (`batch=8`): it has not yet
+        been measured against the clone path (tools/batch_timing.py --mix), and becomes the default
+        (BATCH_SEARCH_POOLS_BY_DEFAULT) only once it is shown faster; batch=None keeps them on the clone path until then.
         Otherwise (`batch=0`, or a network the batched path does not take): `concurrency` clones work through the list
         from as many host threads."""
         utilities = list(utilities)
@@ -651,14 +660,12 @@ class Problem:
             except CfmmError as e:
                 if getattr(e, "code", None) != _lib.E_UNSUPPORTED:
                     raise
-        can_batch = (hasattr(ctx, "solve_batch") and "sum2" not in self.net and "curve2" not in self.net and "pow2" not in self.net and self._host is None
-                     and not any(_is_general(x) for x in utilities)
-                     and not self.deterministic and kw.get("method", "auto") in ("auto", "lbfgs"))
+        can_batch = hasattr(ctx, "solve_batch") and self._batch_applies(utilities, kw)
         if batch is None:
-            batch = ctx.batch_capacity() if can_batch else 0
+            batch = ctx.batch_capacity() if can_batch and (BATCH_SEARCH_POOLS_BY_DEFAULT or not self._search_pools()) else 0
         if batch and not can_batch:
-            raise ValueError("solve_many(batch=...): the batched path takes first-order solves of networks without constant-sum / "
-                             "stableswap pools on one GPU")
+            raise ValueError("solve_many(batch=...): the batched path takes first-order solves of networks without constant-sum pools on "
+                             "one GPU (method=\"auto\" means first order below AUTO_NEWTON_MIN_STABLE stableswap pools)")
         if batch:
             return self._solve_batched(utilities, int(batch), nu0s, warm_start, **kw)
         import threading
@@ -693,6 +700,29 @@ class Problem:
         if errors:
             raise errors[0]
         return results
+
+    def _stable_count(self):
+        """stableswap pools as `solve` counts them for method="auto": curve2 plus the table's stableswap buckets"""
+        return ((len(self.net["curve2"]["Ra"]) if "curve2" in self.net else 0)
+                + sum(b["R"].shape[1] for (kd, _), b in self.net.get("gk", {}).items() if kd == "stable"))
+
+    def _search_pools(self):
+        """the network holds pools whose subproblem is a root search: curve2, pow2, the table's stableswap buckets"""
+        return "curve2" in self.net or "pow2" in self.net or any(kd == "stable" for kd, _ in self.net.get("gk", {}))
+
+    def _batch_applies(self, utilities, kw):
+        """Does cfmm_solve_batch take these solves?  Reads the network, the utilities and the options only (no device).
+        Constant-sum pools (sum2 and the table's ("sum", k) buckets) stay out: their kinks need the tie loop.  curve2, pow2 and
+        ("stable", k) buckets ride along under method="lbfgs", and under "auto" while the stableswap count is below
+        AUTO_NEWTON_MIN_STABLE -- from there on "auto" means the second-order method, which is not batched."""
+        if "sum2" in self.net or any(kd == "sum" for kd, _ in self.net.get("gk", {})):
+            return False
+        if self._host is not None or self.deterministic or any(_is_general(x) for x in utilities):
+            return False
+        method = kw.get("method", "auto")
+        if method == "lbfgs":
+            return True
+        return method == "auto" and (not self._search_pools() or self._stable_count() < AUTO_NEWTON_MIN_STABLE)
 
     # -- the reference's own sweep (two-asset.py:34-100): tiny networks, constant-sum pools included, one library call --------
     _WT = dict(cp2=128, sum2=128, w2=64)               # pools per wave-tile (csrc/kernels.hpp: wave_tile_pools)
@@ -832,6 +862,10 @@ class Problem:
                 total = dict(evals=st["evals"], iters=st["iters"], wall_seconds=st["wall_seconds"], device_seconds=st["device_seconds"],
                              rounds=1, batch=len(group))
                 p._finish(st, nu, psi, total)
+                if method == "auto" and p.status != "optimal" and self._search_pools():
+                    # what `solve` does for such a network: hand the member on to the second-order method, from where it stands
+                    p.solve(tol=tol, max_evals=max_evals, memory=memory, warm_start=True, method="auto")
+                    p.stats["batch"] = len(group)
                 results.append(p._result())
         return results
 

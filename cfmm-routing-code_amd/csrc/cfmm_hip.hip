@@ -242,6 +242,10 @@ struct cfmm_ctx {
     bool listed_valid = false;
     // batched solves (cfmm_solve_batch): the per-solve update arguments, on the lead context
     UpdArgs *upd_batch_d = nullptr, *upd_batch_h = nullptr;
+    // ... and the warm starts of the table's stableswap search, [batch_capacity][m] doubles per bucket of 2..8 assets (batch_slab)
+    double *batch_ws[7] = {};
+    long long batch_ws_m[7] = {};
+    const double *batch_ws_of[7] = {};     // the bucket's own warm-start column when the slab was sized: another one = the bucket was replaced
 
     // graph cache
     hipGraphExec_t gexec = nullptr;
@@ -976,18 +980,22 @@ TableArgs make_table_args(cfmm_ctx *ctx, const double *nu, double *acc)
     a.ftol = ftol;
     return a;
 }
+// `ws_row` (the first evaluation of a batched solve): the stableswap buckets' warm starts are this solve's row of the batch's slab
+// instead of BucketG::ws, which every context of the pool set shares
 template <bool WITH_D>
-void launch_table_evals(cfmm_ctx *ctx, const double *nu, double *acc)
+void launch_table_evals(cfmm_ctx *ctx, const double *nu, double *acc, hipStream_t stream = nullptr, double *const *ws_row = nullptr)
 {
-    const TableArgs a = make_table_args(ctx, nu, acc);
+    TableArgs a = make_table_args(ctx, nu, acc);
     if (a.ntiles == 0) return;
+    if (!stream) stream = ctx->stream;
+    if (ws_row) for (int q = 0; q < 7; ++q) { a.bs[q].ws = ws_row[q]; if (!ws_row[q] && a.bs[q].m) a.warm = 0; }      // (no slab: a cold search)
     const int waves = std::min(GT_THREADS / 64, a.ntiles);
     int grid = (a.ntiles + waves - 1) / waves;
     static const int gmult = getenv("CFMM_TABLE_GRID_MULT") ? std::max(1, atoi(getenv("CFMM_TABLE_GRID_MULT"))) : 1;      // (A/B)
     grid = std::min(grid, gmult * ctx->cus);
     const size_t lds = table_lds_bytes(ctx->n, WITH_D, ctx->det, waves);
-    if (ctx->det) hipLaunchKernelGGL((table_eval_kernel<WITH_D, true>), dim3(grid), dim3(64 * waves), lds, ctx->stream, a);
-    else hipLaunchKernelGGL((table_eval_kernel<WITH_D, false>), dim3(grid), dim3(64 * waves), lds, ctx->stream, a);
+    if (ctx->det) hipLaunchKernelGGL((table_eval_kernel<WITH_D, true>), dim3(grid), dim3(64 * waves), lds, stream, a);
+    else hipLaunchKernelGGL((table_eval_kernel<WITH_D, false>), dim3(grid), dim3(64 * waves), lds, stream, a);
 }
 
 // one dual evaluation of every bucket: one launch, plus one for the heavy buckets (stableswap, generic) when there are any
@@ -1055,6 +1063,8 @@ int set_all_lds_attrs_uncached(cfmm_ctx *ctx)
     if ((rc = set_lds_attr(ctx, update_gram_kernel<512, 2, true>, upd_lds_bytes(ctx->n)))) return rc;
     if ((rc = set_lds_attr(ctx, start_kernel<true>, upd_lds_bytes(ctx->n)))) return rc;
     if ((rc = set_lds_attr(ctx, eval_batch_kernel, batch_lds_bytes(ctx->n, batch_capacity(ctx->n))))) return rc;
+    if ((rc = set_lds_attr(ctx, eval_batch_heavy_kernel, batch_lds_bytes(ctx->n, batch_capacity(ctx->n))))) return rc;
+    if ((rc = set_lds_attr(ctx, table_batch_eval_kernel, table_batch_lds_bytes(ctx->n, batch_capacity(ctx->n), GT_THREADS / 64)))) return rc;
     if ((rc = set_lds_attr(ctx, table_eval_kernel<false, false>, table_lds_bytes(ctx->n, false, false, GT_THREADS / 64)))) return rc;
     if ((rc = set_lds_attr(ctx, table_eval_kernel<true, false>, table_lds_bytes(ctx->n, true, false, GT_THREADS / 64)))) return rc;
     if ((rc = set_lds_attr(ctx, table_newton_kernel<false>, table_newton_lds_bytes(ctx->n, GT_THREADS / 64)))) return rc;
@@ -2369,6 +2379,7 @@ int cfmm_destroy(cfmm_ctx *ctx)
     if (ctx->probe_stream) (void)hipStreamDestroy(ctx->probe_stream);
     if (ctx->upd_batch_d) (void)hipFree(ctx->upd_batch_d);
     if (ctx->upd_batch_h) (void)hipHostFree(ctx->upd_batch_h);
+    for (double *q : ctx->batch_ws) if (q) (void)hipFree(q);
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_t0) (void)hipEventDestroy(ctx->ev_t0);
     if (ctx->ev_t1) (void)hipEventDestroy(ctx->ev_t1);
@@ -3736,13 +3747,110 @@ static int solve_lbfgs(cfmm_ctx *ctx, const cfmm_opts &o_in, cfmm_stats *out)
     return CFMM_OK;
 }
 
+// ---- the batched evaluation: what cfmm_solve_batch iterates on and cfmm_eval_dual_batch runs once ----------------------------------
+// what a context must be to ride in a batch led by c0 (the refusals that concern the pools and the mode)
+static int batch_member_check(cfmm_ctx *c0, cfmm_ctx *const *ctxs, int b, const char *who)
+{
+    cfmm_ctx *c = ctxs[b];
+    if (!c) return fail(c0, CFMM_E_ARG, "%s: context %d is NULL", who, b);
+    for (int q = 0; q < b; ++q) if (ctxs[q] == c) return fail(c0, CFMM_E_ARG, "%s: context %d appears twice", who, b);
+    if (c->pools.get() != c0->pools.get() || c->n != c0->n || c->device != c0->device || c->nslices != c0->nslices)
+        return fail(c0, CFMM_E_ARG, "%s: context %d does not share the lead context's pools (cfmm_clone)", who, b);
+    bool tied = c->ng != c->n || c->flags2;
+    for (const int *q : c->flagsG) tied = tied || q;
+    if (tied) return fail(c0, CFMM_E_UNSUPPORTED, "%s: context %d has price ties set", who, b);
+    if (sharded(c) || c->det) return fail(c0, CFMM_E_UNSUPPORTED, "%s: pool-sharded / reproducible contexts are solved one at a time", who);
+    return CFMM_OK;
+}
+
+// The batch's own warm starts of the table's stableswap search (phik.hpp: TableBatchWs): [batch_capacity][m] doubles per stableswap
+// bucket on the lead context, allocated on first use, again when the bucket has been replaced, and NaN (= none) at the start of every
+// call -- so a call's result is a function of its inputs alone, whatever ran before and whichever cfmm_update_pools* came in between.
+// CFMM_BATCH_WARM=0 runs every search cold (A/B against the slab: tools/batch_timing.py --mix; not yet measured).
+static int batch_slab(cfmm_ctx *c0, int nb, hipStream_t stream, TableBatchWs &tw)
+{
+    tw = TableBatchWs{};
+    const int cap = batch_capacity(c0->n);
+    for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) {
+        const BucketG &b = c0->pools->rg[CFMM_POOLK_STABLE][k].b;
+        const int q = k - 2;
+        if (c0->batch_ws[q] && (c0->batch_ws_m[q] != b.m || c0->batch_ws_of[q] != b.ws)) {
+            HIP_TRY(c0, hipStreamSynchronize(stream));
+            (void)hipFree(c0->batch_ws[q]);
+            c0->batch_ws[q] = nullptr;
+        }
+        if (b.m == 0) continue;
+        if (!c0->batch_ws[q]) {
+            HIP_TRY(c0, hipMalloc((void **)&c0->batch_ws[q], (size_t)cap * b.m * sizeof(double)));
+            c0->batch_ws_m[q] = b.m; c0->batch_ws_of[q] = b.ws;
+        }
+        HIP_TRY(c0, hipMemsetAsync(c0->batch_ws[q], 0xff, (size_t)nb * b.m * sizeof(double), stream));      // (all bits set: a NaN)
+        tw.ws[q] = c0->batch_ws[q];
+    }
+    return CFMM_OK;
+}
+
+// the three launches of one batched evaluation, each only when its buckets are non-empty: main tiles, heavy two-asset tiles, the table
+struct BatchEval {
+    EvalArgs ea, eh;
+    TableArgs ta;
+    BatchArgs bt;
+    TableBatchWs tw;
+    int egrid, ethreads, hgrid, hthreads, tgrid, twaves;
+    size_t elds, tlds;
+};
+// (the table's strips are no larger than the main kernel's and its ticket area is smaller: wherever nb vectors fit eval_batch_kernel's
+//  LDS -- nb <= batch_capacity(n) -- they fit table_batch_eval_kernel's, so the table launch never has to split its vectors)
+static_assert((size_t)(GT_THREADS / 64) * GT_STRIP * sizeof(double2) <= (size_t)2 * 64 * (EVAL_THREADS / 64) * sizeof(double), "table_batch_eval_kernel's strips");
+static int make_batch_eval(cfmm_ctx *const *ctxs, int nb, hipStream_t stream, BatchEval &e)
+{
+    cfmm_ctx *c0 = ctxs[0];
+    const int n = c0->n;
+    e.bt = BatchArgs{};
+    e.bt.nb = nb;
+    for (int b = 0; b < nb; ++b) { e.bt.nu[b] = ctxs[b]->nu; e.bt.acc[b] = ctxs[b]->acc; }
+    e.ea = make_eval_args(c0, false, 0x7fffffff, false);
+    e.eh = make_eval_args(c0, true, 0x7fffffff, false);
+    eval_geometry(c0, e.ea.ntiles, e.egrid, e.ethreads);
+    eval_geometry(c0, e.eh.ntiles, e.hgrid, e.hthreads);
+    e.elds = batch_lds_bytes(n, nb);
+    e.ta = make_table_args(c0, nullptr, nullptr);
+    static const bool warm_off = getenv("CFMM_BATCH_WARM") && atoi(getenv("CFMM_BATCH_WARM")) == 0;      // (A/B)
+    if (warm_off) e.ta.warm = 0;
+    e.twaves = std::max(1, std::min(GT_THREADS / 64, e.ta.ntiles));
+    e.tgrid = std::min((e.ta.ntiles + e.twaves - 1) / e.twaves, c0->cus);
+    e.tlds = table_batch_lds_bytes(n, nb, e.twaves);
+    e.tw = TableBatchWs{};
+    if (e.ta.ntiles > 0 && e.ta.tile_end[6] > 0 && e.ta.warm) return batch_slab(c0, nb, stream, e.tw);
+    e.ta.warm = 0;
+    return CFMM_OK;
+}
+static void launch_batch_eval(cfmm_ctx *c0, const BatchEval &e, hipStream_t stream, int t)
+{
+    const int rev = pingpong_on(c0) ? (t & 1) : 0;
+    if (e.ea.ntiles > 0) {
+        EvalArgs eb = e.ea;
+        eb.rev = rev;
+        hipLaunchKernelGGL(eval_batch_kernel, dim3(e.egrid), dim3(e.ethreads), e.elds, stream, eb, e.bt);
+    }
+    if (e.eh.ntiles > 0) {
+        EvalArgs eb = e.eh;
+        eb.rev = rev;
+        hipLaunchKernelGGL(eval_batch_heavy_kernel, dim3(e.hgrid), dim3(e.hthreads), e.elds, stream, eb, e.bt);
+    }
+    if (e.ta.ntiles > 0) hipLaunchKernelGGL(table_batch_eval_kernel, dim3(e.tgrid), dim3(64 * e.twaves), e.tlds, stream, e.ta, e.bt, e.tw);
+}
+
 // B first-order solves over ONE resident pool set in lock-step ("B price vectors per pool read"; the
 // reference use is the sweep of two-asset.py:34-100).  ctxs[0] is the lead context, the others its clones (cfmm_clone):
-// each holds its own utility, prices and solver state.  Per outer iteration TWO launches serve all B solves:
-//   eval_batch_kernel    every pool column read once, every pool solved at the B price vectors
-//   update_*_kernel<BATCH>   B workgroups, one projected L-BFGS step each
-// A solve that has ended drops out of both (its stop flag / status), the loop ends when all have.  The first evaluation
-// of every solve also builds the diagonal metric and runs through eval_kernel, one launch per solve.
+// each holds its own utility, prices and solver state.  Per outer iteration up to FOUR launches serve all B solves:
+//   eval_batch_kernel          every pool column read once, every pool solved at the B price vectors
+//   eval_batch_heavy_kernel    the same for the heavy two-asset buckets (stableswap, power sum), when there are any
+//   table_batch_eval_kernel    the same for the K-asset table's buckets, when there are any
+//   update_*_kernel<BATCH>     B workgroups, one projected L-BFGS step each
+// A solve that has ended drops out of all of them (its stop flag / status), the loop ends when all have.  The first evaluation
+// of every solve also builds the diagonal metric and runs through eval_kernel / table_eval_kernel, one set of launches per solve.
+// The table's constant-sum pools are evaluated at their LP vertex like the two-asset ones: kinks are left to the caller.
 int cfmm_solve_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu0, const cfmm_opts *opts_in, cfmm_stats *out)
 {
     if (!ctxs || nb < 1 || !ctxs[0] || !out) return CFMM_E_ARG;
@@ -3757,13 +3865,8 @@ int cfmm_solve_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu0, co
     if (o.memory < 1 || o.memory > MAX_MEMORY || o.max_evals < 1) return fail(c0, CFMM_E_ARG, "solve_batch: memory %d, max_evals %d", o.memory, o.max_evals);
     if (o.method == CFMM_METHOD_NEWTON) return fail(c0, CFMM_E_UNSUPPORTED, "solve_batch: first-order method only");
     for (int b = 0; b < nb; ++b) {
+        { int rc = batch_member_check(c0, ctxs, b, "solve_batch"); if (rc) return rc; }
         cfmm_ctx *c = ctxs[b];
-        if (!c) return fail(c0, CFMM_E_ARG, "solve_batch: context %d is NULL", b);
-        for (int q = 0; q < b; ++q) if (ctxs[q] == c) return fail(c0, CFMM_E_ARG, "solve_batch: context %d appears twice", b);
-        if (c->pools.get() != c0->pools.get() || c->n != n || c->device != c0->device || c->nslices != c0->nslices)
-            return fail(c0, CFMM_E_ARG, "solve_batch: context %d does not share the lead context's pools (cfmm_clone)", b);
-        if (c->ng != n || c->flags2) return fail(c0, CFMM_E_UNSUPPORTED, "solve_batch: context %d has price ties set", b);
-        if (sharded(c) || c->det) return fail(c0, CFMM_E_UNSUPPORTED, "solve_batch: pool-sharded / reproducible contexts are solved one at a time");
         if (!c->have_utility) return fail(c0, CFMM_E_STATE, "solve_batch: context %d has no utility", b);
         if (c->general_utility) return fail(c0, CFMM_E_UNSUPPORTED, "solve_batch: context %d has a utility beyond linear-plus-box (CFMM_ULOG / CFMM_UQUAD): solved one at a time", b);
         if (nu0 && nu0[b]) { int rc = cfmm_set_nu(c, nu0[b]); if (rc) { c0->err = c->err; return rc; } }
@@ -3772,27 +3875,22 @@ int cfmm_solve_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu0, co
         HIP_TRY(c0, hipStreamSynchronize(c->stream));
     }
     if (cfmm_pool_count(c0) == 0) return fail(c0, CFMM_E_STATE, "solve_batch: no pools uploaded");
-    if (extra_launch_pools(c0) > 0) return fail(c0, CFMM_E_UNSUPPORTED, "solve_batch: stableswap / generic-bucket / K-asset table pools are evaluated by their own launch: one solve at a time");
     if (!c0->upd_batch_d) {
         HIP_TRY(c0, hipMalloc((void **)&c0->upd_batch_d, BATCH_MAX * sizeof(UpdArgs)));
         HIP_TRY(c0, hipHostMalloc((void **)&c0->upd_batch_h, BATCH_MAX * sizeof(UpdArgs), hipHostMallocDefault));
     }
     hipStream_t stream = c0->stream;
-    BatchArgs bt = {};
-    bt.nb = nb;
     for (int b = 0; b < nb; ++b) {
         UpdArgs ua = make_upd_args(ctxs[b], o);
         ua.hstat = c0->hstat_d + b;
         c0->upd_batch_h[b] = ua;
         c0->hstat_h[b] = 0;
-        bt.nu[b] = ctxs[b]->nu; bt.acc[b] = ctxs[b]->acc;
     }
     UpdArgs lead = c0->upd_batch_h[0];
     lead.batch = c0->upd_batch_d;
-    const EvalArgs ea = make_eval_args(c0, false, 0x7fffffff, false);
-    int egrid, ethreads;
-    eval_geometry(c0, ea.ntiles, egrid, ethreads);
-    const size_t elds = batch_lds_bytes(n, nb), ulds = upd_lds_bytes(n);
+    BatchEval be;
+    { int rc = make_batch_eval(ctxs, nb, stream, be); if (rc) return rc; }
+    const size_t ulds = upd_lds_bytes(n);
     auto launch_update_batch = [&]() {
         const int M = o.memory;
         auto thr = [n](int E) { return 64 * ((n + 64 * E - 1) / (64 * E)); };
@@ -3813,7 +3911,15 @@ int cfmm_solve_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu0, co
     HIP_TRY(c0, hipMemcpyAsync(c0->upd_batch_d, c0->upd_batch_h, nb * sizeof(UpdArgs), hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(start_kernel<true>, dim3(nb), dim3(UPD_THREADS), ulds, stream, lead, (const double *)nullptr, (double *)nullptr,
                        (long long)((size_t)c0->nslices * acc_stride(n)), (DevState *)nullptr, 0);
-    for (int b = 0; b < nb; ++b) launch_eval<true, false>(ctxs[b], make_eval_args(ctxs[b], false), stream);     // first evaluation: with the metric
+    for (int b = 0; b < nb; ++b) {                                              // first evaluation: with the metric, every piece on the batch's stream
+        launch_eval<true, false>(ctxs[b], make_eval_args(ctxs[b], false), stream);
+        if (be.eh.ntiles > 0) launch_eval<true, true>(ctxs[b], make_eval_args(ctxs[b], true), stream);
+        if (be.ta.ntiles > 0) {
+            double *row[7];
+            for (int q = 0; q < 7; ++q) row[q] = be.tw.ws[q] ? be.tw.ws[q] + (size_t)b * be.ta.bs[q].m : nullptr;
+            launch_table_evals<true>(ctxs[b], ctxs[b]->nu, ctxs[b]->acc, stream, row);
+        }
+    }
     launch_update_batch();
     HIP_TRY(c0, hipGetLastError());
     int t = 1;
@@ -3830,9 +3936,7 @@ int cfmm_solve_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu0, co
             if (!running) break;
             if (t > o.max_evals + 1) { HIP_TRY(c0, hipStreamSynchronize(stream)); break; }      // the device ends every solve at its budget (status 3)
             if (t - done <= c0->run_ahead) {
-                EvalArgs eb = ea;
-                eb.rev = pingpong_on(c0) ? (t & 1) : 0;
-                hipLaunchKernelGGL(eval_batch_kernel, dim3(egrid), dim3(ethreads), elds, stream, eb, bt);
+                launch_batch_eval(c0, be, stream, t);
                 launch_update_batch();
                 ++t; spins = 0;
                 continue;
@@ -3874,6 +3978,55 @@ int cfmm_solve_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu0, co
         if (!std::isfinite(st.f)) { s->status = CFMM_E_NUMERIC; rc_all = fail(c0, CFMM_E_NUMERIC, "solve_batch: dual value of solve %d is not finite", b); }
     }
     return rc_all;
+}
+
+// one dual evaluation at nb price vectors in ONE pass over the pools: the batched launches of cfmm_solve_batch, once, without a solver
+int cfmm_eval_dual_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu, double *arb_sum, double *const *psi)
+{
+    if (!ctxs || nb < 1 || !ctxs[0] || !nu) return CFMM_E_ARG;
+    cfmm_ctx *c0 = ctxs[0];
+    PoolEntry entry(c0); HIP_TRY(c0, entry.device);
+    for (int b = 1; b < nb; ++b) if (ctxs[b]) pools_seen(ctxs[b]);
+    const int n = c0->n;
+    if (nb > batch_capacity(n)) return fail(c0, CFMM_E_LIMIT, "eval_dual_batch: %d price vectors, at most %d fit the LDS tile at %d tokens", nb, batch_capacity(n), n);
+    for (int b = 0; b < nb; ++b) {
+        { int rc = batch_member_check(c0, ctxs, b, "eval_dual_batch"); if (rc) return rc; }
+        if (!nu[b]) return fail(c0, CFMM_E_ARG, "eval_dual_batch: nu[%d] is NULL", b);
+        { int rc = check_prices(ctxs[b], "eval_dual_batch: nu", nu[b]); if (rc) { c0->err = ctxs[b]->err; return rc; } }
+    }
+    if (cfmm_pool_count(c0) == 0) return fail(c0, CFMM_E_STATE, "eval_dual_batch: no pools uploaded");
+    hipStream_t stream = c0->stream;
+    const int len = acc_arb(n) + 1;
+    // the prices become every context's point (nu_acc) and its trial prices (nu) with a clear stop flag behind them; accumulators zeroed
+    for (int b = 0; b < nb; ++b) {
+        cfmm_ctx *c = ctxs[b];
+        HIP_TRY(c0, hipStreamSynchronize(c->stream));
+        std::memcpy(c->hnu0, nu[b], n * sizeof(double));
+        HIP_TRY(c0, hipMemcpyAsync(c->nu_acc, c->hnu0, n * sizeof(double), hipMemcpyHostToDevice, stream));
+        HIP_TRY(c0, hipMemcpyAsync(c->nu, c->hnu0, n * sizeof(double), hipMemcpyHostToDevice, stream));
+        HIP_TRY(c0, hipMemsetAsync(c->nu + n, 0, sizeof(double), stream));
+        HIP_TRY(c0, hipMemsetAsync(c->acc, 0, (size_t)c->nslices * acc_stride(n) * sizeof(double), stream));
+        point_from_caller(c);
+    }
+    BatchEval be;
+    { int rc = make_batch_eval(ctxs, nb, stream, be); if (rc) return rc; }
+    launch_batch_eval(c0, be, stream, 0);
+    for (int b = 0; b < nb; ++b) {
+        cfmm_ctx *c = ctxs[b];
+        hipLaunchKernelGGL(fold_kernel, dim3((len + 255) / 256), dim3(256), 0, stream, c->acc, n, c->nslices, 0, (const DevState *)nullptr);
+        double *pin = pin_scratch(c, (size_t)len);              // (pinned staging: at least 8 n + 64 doubles)
+        if (!pin) return fail(c0, CFMM_E_HIP, "pinned staging (%d tokens)", n);
+        HIP_TRY(c0, hipMemcpyAsync(pin, c->acc, len * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(c0, hipMemsetAsync(c->acc, 0, (size_t)len * sizeof(double), stream));
+    }
+    HIP_TRY(c0, hipGetLastError());
+    HIP_TRY(c0, hipStreamSynchronize(stream));
+    for (int b = 0; b < nb; ++b) {
+        const double *h = ctxs[b]->pin;
+        if (psi && psi[b]) std::memcpy(psi[b], h, n * sizeof(double));
+        if (arb_sum) arb_sum[b] = h[acc_arb(n)];
+    }
+    return CFMM_OK;
 }
 
 int cfmm_batch_capacity(int n_tokens) { return n_tokens < 1 ? 0 : batch_capacity(n_tokens); }

@@ -969,8 +969,9 @@ eval_kernel(EvalArgs a)
 // The B solves share the pool set (cfmm_clone) and differ in utility, prices and solver state: vector b's prices come
 // from nu[b] (its own stop flag behind them), its psi tile is flushed into acc[b].  Per tile the pool columns are loaded
 // once; arithmetic, LDS gathers and scatters are per vector.  LDS: psi[B][n] | nu[B][n + 2] | fpart[B_MAX][16] | ticket
-// | strips: 144 KB at B = 8 and 1000 tokens.  No metric (WITH_D) and no stableswap bucket here: the first evaluation
-// of every solve (which builds the metric) runs through eval_kernel.
+// | strips: 144 KB at B = 8 and 1000 tokens.  No metric (WITH_D) here: the first evaluation of every solve (which builds
+// the metric) runs through eval_kernel.  The heavy two-asset buckets have their own instantiation (eval_batch_heavy_kernel),
+// the K-asset table its own kernel (phik.hpp: table_batch_eval_kernel).
 // ------------------------------------------------------------------------------------------
 struct BatchArgs {
     const double *nu[BATCH_MAX];
@@ -1021,6 +1022,34 @@ eval_batch_kernel(EvalArgs a, BatchArgs bt)
     if (!alive) return;
     const BatchCtl bc{alive, nus, n};
     eval_tiles_and_flush<false, false, false, true>(a, nullptr, nu_s, psi_s, nullptr, fpart, next_tile, xs, bc, bt.acc);
+}
+// The heavy two-asset tile space (curve2, pow2: eval_kernel<., STABLE = true>'s) of a batched iteration, launched behind
+// eval_batch_kernel and in front of the batched update: the same LDS layout, the same alive mask.  A sibling with the prologue
+// written out again, not a template parameter or a shared body: either moved instructions inside eval_batch_kernel, whose time
+// tests/test_gpu_perf.py guards.
+__global__ void __launch_bounds__(EVAL_THREADS, EVAL_WAVES_PER_SIMD)
+eval_batch_heavy_kernel(EvalArgs a, BatchArgs bt)
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int n = a.n, nb = bt.nb, nus = batch_nu_stride(n);
+    double *psi_s = lds;                                // [nb][n]
+    double *nu_s = lds + nb * n;                        // [nb][nus]: prices, then the stop flag
+    double *fpart = nu_s + nb * nus;                    // [BATCH_MAX][16]
+    int *next_tile = reinterpret_cast<int *>(fpart + BATCH_MAX * 16);
+    if (threadIdx.x < 64) build_tile_table(a, next_tile, threadIdx.x);
+    double2 *xs = reinterpret_cast<double2 *>(lds + batch_lds_doubles(n, nb)) + 64 * (threadIdx.x >> 6);
+    for (int b = 0; b < nb; ++b) {
+        const double *src = bt.nu[b];
+        for (int j = threadIdx.x; j <= n; j += blockDim.x) nu_s[b * nus + j] = src[j];
+    }
+    for (int j = threadIdx.x; j < nb * n; j += blockDim.x) psi_s[j] = 0.0;
+    __syncthreads();
+    unsigned alive = 0;
+    for (int b = 0; b < nb; ++b) alive |= (nu_s[b * nus + n] == 0.0 ? 1u : 0u) << b;
+    alive = __builtin_amdgcn_readfirstlane(alive);
+    if (!alive) return;
+    const BatchCtl bc{alive, nus, n};
+    eval_tiles_and_flush<false, true, false, true>(a, nullptr, nu_s, psi_s, nullptr, fpart, next_tile, xs, bc, bt.acc);
 }
 
 // ------------------------------------------------------------------------------------------

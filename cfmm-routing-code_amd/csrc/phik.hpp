@@ -348,11 +348,32 @@ __host__ __device__ inline void pool_table_k(const double (&R)[K], const double 
 // log-prices `nw.slo_s` (smooth.hpp: apply_slo; null: none) and the pool's value p'y is summed into nw.vsum; 2 = also the pool's exact
 // Hessian block in log-prices (stable_block above), leg pair (j, k <= j) by lane j, through global atomics into nw.H
 struct TileNewt { const double *slo_s; double *H; int ldh; double *vsum; };
-template <int K, bool WITH_D, bool DET, int NEWT = 0>
+// a table wave-tile's columns as one lane holds them (the batched evaluation loads them once for all its price vectors: gk_tile_load);
+// ws: the warm-start column the tile reads and writes in place of the bucket's own
+struct GkRegs { int tok, tied; unsigned pl; bool live; double R, fee, ifee, al, sR; double *ws; };
+template <int K, bool STABLE>
+__device__ __forceinline__ void gk_tile_load(const BucketG &b, const int *flags, int tb, int lane, GkRegs &r)
+{
+    constexpr int P = 64 / K;
+    const int g = lane / K, j = lane - g * K;
+    const unsigned pool = (unsigned)tb * P + g;
+    r.live = g < P && pool < (unsigned long long)b.m;
+    const unsigned leg = r.live ? pool * K + j : 0u;
+    r.pl = r.live ? pool : 0u;
+    r.tok = b.idx[leg]; r.R = b.R[leg];
+    r.fee = b.fee[r.pl]; r.ifee = b.ifee[r.pl];
+    r.al = STABLE ? b.param[r.pl] : 0.0; r.sR = STABLE ? b.sR[r.pl] : 0.0;
+    r.tied = (!STABLE && flags) ? flags[leg] : 0;
+    r.ws = nullptr;
+}
+// PRE: the columns come from `pre` instead of global memory, the warm start from pre->ws (never BucketG::ws)
+template <int K, bool WITH_D, bool DET, int NEWT = 0, bool PRE = false>
 __device__ __forceinline__ void tileg_stable(const BucketG &b, int tb, int lane, const double *nu_s, const Scatter<DET> &psi_s, const Scatter<DET> &diag_s,
-                                             double2 *xs, bool warm, double ftol_rel, const TileNewt &nw = TileNewt{nullptr, nullptr, 0, nullptr})
+                                             double2 *xs, bool warm, double ftol_rel, const TileNewt &nw = TileNewt{nullptr, nullptr, 0, nullptr},
+                                             const GkRegs *pre = nullptr)
 {
     static_assert(!NEWT || (!WITH_D && !DET), "the second-order tile: plain accumulation, no metric");
+    static_assert(!PRE || (!WITH_D && !DET && !NEWT), "columns held in registers: the batched evaluation's tiles");
     constexpr int P = 64 / K;
     constexpr double INF = 1.7976931348623157e308;
     // (opaque copy, as in kernels.hpp: tilen -- otherwise lane / K, lane % K and the strip addresses of all seven instantiations are hoisted
@@ -362,11 +383,12 @@ __device__ __forceinline__ void tileg_stable(const BucketG &b, int tb, int lane,
 #endif
     const int g = lane / K, j = lane - g * K;
     const unsigned pool = (unsigned)tb * P + g;
-    const bool live = g < P && pool < (unsigned long long)b.m;
+    const bool live = PRE ? pre->live : g < P && pool < (unsigned long long)b.m;
     const unsigned leg = live ? pool * K + j : 0u, pl = live ? pool : 0u;
-    const int tok = b.idx[leg];
-    const double R = b.R[leg], ifee = b.ifee[pl], al = b.param[pl], sR = b.sR[pl];
-    const double wsv = (!DET && warm) ? b.ws[pl] : __builtin_nan("");
+    const int tok = PRE ? pre->tok : b.idx[leg];
+    const double R = PRE ? pre->R : b.R[leg], ifee = PRE ? pre->ifee : b.ifee[pl], al = PRE ? pre->al : b.param[pl], sR = PRE ? pre->sR : b.sR[pl];
+    double *const wsc = PRE ? pre->ws : b.ws;
+    const double wsv = (!DET && warm) ? wsc[pl] : __builtin_nan("");
     const double nu = nu_s[tok];
     const int gb = (g < P ? g : 0) * K;
     double2 *xt = xs + 64;
@@ -470,7 +492,7 @@ __device__ __forceinline__ void tileg_stable(const BucketG &b, int tb, int lane,
             }
         }
     }
-    if (!DET && warm && trade && j == 0) b.ws[pl] = th;
+    if (!DET && warm && trade && j == 0) wsc[pl] = th;
     if constexpr (NEWT != 0) {
         // the pool of the second-order path, leg per lane: pools that trade on at least two legs enter with tenders, value and block; the others
         // not at all (a single active leg cannot move along the level set)
@@ -526,17 +548,18 @@ __device__ __forceinline__ void tileg_stable(const BucketG &b, int tb, int lane,
 // tender the cheapest token, drain every token worth more than it after the fee.  flags (per leg, or null): legs the host's
 // active-set loop has TIED to the pool's cheapest token (gamma nu_j = nu_lo: a kink of the dual) are left out here -- the host
 // adds their partial fill (cfmm/problem.py)
-template <int K, bool DET>
-__device__ __forceinline__ void tileg_sum(const BucketG &b, const int *flags, int tb, int lane, const double *nu_s, const Scatter<DET> &psi_s, double2 *xs)
+template <int K, bool DET, bool PRE = false>
+__device__ __forceinline__ void tileg_sum(const BucketG &b, const int *flags, int tb, int lane, const double *nu_s, const Scatter<DET> &psi_s, double2 *xs,
+                                          const GkRegs *pre = nullptr)
 {
     constexpr int P = 64 / K;
     const int g = lane / K, j = lane - g * K;
     const unsigned pool = (unsigned)tb * P + g;
-    const bool live = g < P && pool < (unsigned long long)b.m;
+    const bool live = PRE ? pre->live : g < P && pool < (unsigned long long)b.m;
     const unsigned leg = live ? pool * K + j : 0u, pl = live ? pool : 0u;
-    const int tok = b.idx[leg];
-    const double R = b.R[leg], fee = b.fee[pl], ifee = b.ifee[pl];
-    const bool tied = flags && flags[leg] != 0;
+    const int tok = PRE ? pre->tok : b.idx[leg];
+    const double R = PRE ? pre->R : b.R[leg], fee = PRE ? pre->fee : b.fee[pl], ifee = PRE ? pre->ifee : b.ifee[pl];
+    const bool tied = PRE ? pre->tied != 0 : flags && flags[leg] != 0;
     const double nu = nu_s[tok];
     const int gb = (g < P ? g : 0) * K;
     xs[lane] = make_double2(nu, 0.0);
@@ -639,6 +662,113 @@ table_eval_kernel(TableArgs a)
         double f = 0.0;
         for (int w = 0; w < nw; ++w) f += fpart[w];
         if (f != 0.0) unsafeAtomicAdd(&base[acc_arb(n)], f);
+    }
+}
+
+// ---- the table's launch of a batched iteration (cfmm_solve_batch, cfmm_eval_dual_batch): table_eval_kernel<false, false> at B price vectors --------
+// A wave-tile's columns are loaded ONCE (gk_tile_load); the tile then runs per live vector (a rolled loop: the stableswap search sits near
+// the 256-VGPR budget) against nu_s + b * stride into vector b's psi tile, and every vector's tile is flushed into its own accumulator with its
+// own nu' psi, as eval_tiles_and_flush<BATCH> does.  LDS: psi[nb][n] | nu[nb][stride] | fpart[BATCH_MAX][16] | ticket | strips.
+// (Its name keeps clear of "eval_batch_kernel": tests/test_host.py tells the kernels' register budgets apart by substrings of their names,
+//  and this one has table_eval_kernel's budget -- 8 waves of 512 threads, 256 VGPRs -- not the main batched kernel's 128.)
+// The stableswap search's warm starts: BucketG::ws is ONE root per pool, shared by every context of the pool set -- B vectors writing it in
+// turn would hand each vector another vector's root.  The batch has its own slab, ws[k - 2] = [vectors][m] doubles per stableswap bucket
+// (cfmm_hip.hip: batch_slab), row b0 + b for the launch's vector b; this kernel neither reads nor writes BucketG::ws.
+struct TableBatchWs { double *ws[7]; int b0, pad; };
+__host__ __device__ inline int table_batch_lds_doubles(int n, int nb) { return (nb * n + nb * batch_nu_stride(n) + BATCH_MAX * 16 + 2 + 1) & ~1; }
+__host__ __device__ inline size_t table_batch_lds_bytes(int n, int nb, int waves)
+{
+    return (size_t)table_batch_lds_doubles(n, nb) * sizeof(double) + (size_t)waves * GT_STRIP * sizeof(double2);
+}
+template <int K>
+__device__ __forceinline__ void tileg_stable_batch(const BucketG &b, double *ws, int tb, int lane, const double *nu_s, double *psi_t, int n, double2 *xs,
+                                                   bool warm, double ftol_rel, const BatchCtl &bc)
+{
+    GkRegs r;
+    gk_tile_load<K, true>(b, nullptr, tb, lane, r);
+#pragma unroll 1
+    for (unsigned mask = bc.alive; mask; mask &= mask - 1) {
+        const int bb = __builtin_ctz(mask);
+        const Scatter<false> ps{psi_t + bb * bc.tile_stride, n, 0.0};
+        r.ws = ws + (long long)bb * b.m;
+        tileg_stable<K, false, false, 0, true>(b, tb, lane, nu_s + bb * bc.nu_stride, ps, ps, xs, warm, ftol_rel, TileNewt{nullptr, nullptr, 0, nullptr}, &r);
+    }
+}
+template <int K>
+__device__ __forceinline__ void tileg_sum_batch(const BucketG &b, const int *flags, int tb, int lane, const double *nu_s, double *psi_t, int n, double2 *xs,
+                                                const BatchCtl &bc)
+{
+    GkRegs r;
+    gk_tile_load<K, false>(b, flags, tb, lane, r);
+#pragma unroll 1
+    for (unsigned mask = bc.alive; mask; mask &= mask - 1) {
+        const int bb = __builtin_ctz(mask);
+        const Scatter<false> ps{psi_t + bb * bc.tile_stride, n, 0.0};
+        tileg_sum<K, false, true>(b, flags, tb, lane, nu_s + bb * bc.nu_stride, ps, xs, &r);
+    }
+}
+__global__ void __launch_bounds__(GT_THREADS, GT_WAVES_PER_SIMD)
+table_batch_eval_kernel(TableArgs a, BatchArgs bt, TableBatchWs tw)
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int n = a.n, nb = bt.nb, nus = batch_nu_stride(n);
+    double *psi_t = lds;                               // [nb][n]
+    double *nu_s = lds + nb * n;                       // [nb][nus]: prices, then the stop flag
+    double *fpart = nu_s + nb * nus;                   // [BATCH_MAX][16]
+    int *next_tile = reinterpret_cast<int *>(fpart + BATCH_MAX * 16);
+    const int lane = threadIdx.x & 63, wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+    double2 *xs = reinterpret_cast<double2 *>(lds + table_batch_lds_doubles(n, nb)) + GT_STRIP * wib;
+    for (int b = 0; b < nb; ++b) {
+        const double *src = bt.nu[b];
+        for (int j = threadIdx.x; j <= n; j += blockDim.x) nu_s[b * nus + j] = src[j];
+    }
+    for (int j = threadIdx.x; j < nb * n; j += blockDim.x) psi_t[j] = 0.0;
+    const int t0 = (int)(((long long)blockIdx.x * a.ntiles) / gridDim.x), t1 = (int)(((long long)(blockIdx.x + 1) * a.ntiles) / gridDim.x);
+    if (threadIdx.x == 0) *next_tile = t0 + nw;
+    __syncthreads();
+    unsigned alive = 0;
+    for (int b = 0; b < nb; ++b) alive |= (nu_s[b * nus + n] == 0.0 ? 1u : 0u) << b;
+    alive = __builtin_amdgcn_readfirstlane(alive);
+    if (!alive) return;
+    const BatchCtl bc{alive, nus, n};
+    int ticket = t0 + wib;
+    for (;;) {
+        const int t = __builtin_amdgcn_readfirstlane(ticket);
+        if (t >= t1) break;
+        if (lane == 0) ticket = atomicAdd(next_tile, 1);
+        int q = 0, first = 0;
+#pragma unroll
+        for (int i = 0; i < 13; ++i) if (t >= a.tile_end[i]) { q = i + 1; first = a.tile_end[i]; }
+        const int tb = t - first;
+        switch (q) {
+#define GT_S(KK) case KK - 2: tileg_stable_batch<KK>(a.bs[KK - 2], tw.ws[KK - 2] + (long long)tw.b0 * a.bs[KK - 2].m, tb, lane, nu_s, psi_t, n, xs, a.warm != 0, a.ftol, bc); break;
+#define GT_Q(KK) case 7 + KK - 2: tileg_sum_batch<KK>(a.bq[KK - 2], a.qflags[KK - 2], tb, lane, nu_s, psi_t, n, xs, bc); break;
+        GT_S(2) GT_S(3) GT_S(4) GT_S(5) GT_S(6) GT_S(7) GT_S(8)
+        GT_Q(2) GT_Q(3) GT_Q(4) GT_Q(5) GT_Q(6) GT_Q(7) GT_Q(8)
+#undef GT_S
+#undef GT_Q
+        default: break;
+        }
+    }
+    // the flush: every live vector's tile into its own accumulator, as eval_tiles_and_flush<BATCH>'s (kernels.hpp)
+    __syncthreads();
+    for (unsigned mask = alive; mask; mask &= mask - 1) {
+        const int bb = __builtin_ctz(mask);
+        double *base = bt.acc[bb] + (size_t)(blockIdx.x % a.nslices) * acc_stride(n);
+        const double *pt = psi_t + bb * n, *nub = nu_s + bb * nus;
+        double f = 0.0;
+        for (int j = threadIdx.x; j < n; j += blockDim.x) {
+            const double v = pt[j];
+            if (v != 0.0) { unsafeAtomicAdd(&base[j], v); f += nub[j] * v; }
+        }
+        f = wave_sum(f);
+        if (lane == 0) fpart[bb * 16 + wib] = f;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < BATCH_MAX && ((alive >> threadIdx.x) & 1u)) {
+        double f = 0.0;
+        for (int w = 0; w < nw; ++w) f += fpart[threadIdx.x * 16 + w];
+        if (f != 0.0) unsafeAtomicAdd(&bt.acc[threadIdx.x][(size_t)(blockIdx.x % a.nslices) * acc_stride(n) + acc_arb(n)], f);
     }
 }
 

@@ -252,10 +252,20 @@ int cfmm_solve(cfmm_ctx *ctx, const double *nu0, const cfmm_opts *opts, cfmm_sta
  * baskets over one pool set.  ctxs[0] is the context the pools were uploaded to, ctxs[1..] its cfmm_clone()s, each with
  * its own cfmm_set_utility; nu0[b] (or nu0 itself) may be NULL = continue from that context's prices.  Every outer
  * iteration reads every pool column ONCE and solves each pool at all nb price vectors (first-order method; no price
- * ties, no stableswap pools, not pool-sharded); out[b] are the statistics of solve b (wall / device seconds: of the
- * whole batch).  nb <= cfmm_batch_capacity(n_tokens) (8 up to ~1100 tokens; bounded by the LDS tile beyond).
+ * ties or tie flags, linear-plus-box utilities, not pool-sharded, not reproducible); out[b] are the statistics of solve b
+ * (wall / device seconds: of the whole batch).  nb <= cfmm_batch_capacity(n_tokens) (8 up to ~1100 tokens; bounded by the
+ * LDS tile beyond).  Every pool family rides along: the stableswap / power-sum two-asset buckets and the K-asset table's
+ * buckets through batched launches of their own behind the main one.  Constant-sum pools, two-asset or of the table, are
+ * evaluated at their LP vertex: an optimum on one of their kinks is left to the caller (cfmm_set_ties, cfmm_solve).  The
+ * table's stableswap search warm-starts from a slab of the batch's own, cleared at every call: a call's result is a function
+ * of its inputs alone.
  * Afterwards every context is read back as after cfmm_solve (cfmm_get_solution, cfmm_get_trades*). */
 int cfmm_solve_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu0, const cfmm_opts *opts, cfmm_stats *out);
+/* one dual evaluation at nb price vectors in ONE pass over the pools (what cfmm_solve_batch iterates on):
+ * ctxs as for cfmm_solve_batch; nu[b]: [n]; arb_sum[nb]; psi[b]: [n].  No metric.  Refusals: those of cfmm_solve_batch that
+ * concern the pools and the mode (ties, sharded, reproducible); needs no utility.  The prices become every context's point, as
+ * after cfmm_set_nu. */
+int cfmm_eval_dual_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu, double *arb_sum, double *const *psi);
 int cfmm_batch_capacity(int n_tokens);
 
 /* The reference's OWN sweep as one call: two-asset.py:34-100 solves the same 5-pool network (constant-sum pool included,
