@@ -238,6 +238,17 @@ struct cfmm_ctx {
     volatile unsigned long long *hstat_h = nullptr;     // pinned, device-mapped progress word (iterate.hpp: IterArgs::hstat)
     unsigned long long *hstat_d = nullptr;
     int run_ahead = 3;                 // CFMM_RUN_AHEAD: launches the host keeps enqueued beyond the last one the device reported
+    // The sealed envelope of the single-GPU one-launch-per-iteration solve (iterate.hpp: EnvRec; solve_lbfgs).  INVARIANT: every entry
+    // point returns with its stream drained, EXCEPT such a solve, which returns once its result is sealed and sets `tail`: launches that
+    // found the solve ended may still be in flight.  They read and write nothing but the rotating state records (st3) and the envelope
+    // record, under their own solve's epoch, and everything enqueued on the stream later runs behind them.  Whatever is NOT ordered by the
+    // stream -- host writes into memory the device maps, other streams, frees -- calls settle() first: PoolEntry does for every call that
+    // reads pools, the other entry points do themselves; only the next sealed solve goes on without.
+    volatile EnvRec *env_h = nullptr;  // pinned, device-mapped (behind the progress ring in hstat's allocation)
+    EnvRec *env_d = nullptr;
+    unsigned epoch = 0;                // solves counted on this context; 0 is never handed out (the words start as zero)
+    bool tail = false;
+    double wall_clock_hz = 1e8;        // rate of the device's constant clock (wall_clock64): EnvRec::t0 / t1
     std::vector<char> listed;          // per token: some pool (of any rank) lists it -- the second-order path pins the others (listed_tokens)
     bool listed_valid = false;
     // batched solves (cfmm_solve_batch): the per-solve update arguments, on the lead context
@@ -313,6 +324,15 @@ int fail(cfmm_ctx *ctx, int code, const char *fmt, ...)
         hipError_t e_ = (call);                                                                   \
         if (e_ != hipSuccess) return fail(ctx, CFMM_E_HIP, "%s -> %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
+
+// the launches a sealed first-order solve may have left in flight (cfmm_ctx::tail) are waited for: one test when there are none
+inline int settle(cfmm_ctx *ctx)
+{
+    if (!ctx->tail) return CFMM_OK;
+    ctx->tail = false;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CFMM_OK;
+}
 
 // pool-sharded: a communicator (RCCL) and / or an attached one-shot exchange
 inline bool sharded(const cfmm_ctx *ctx) { return ctx->comm != nullptr || ctx->os_ready; }
@@ -1741,7 +1761,8 @@ int solve_newton(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out, int evals_b
     const char *why = "";
     if (!newton_supported(ctx, &why)) return fail(ctx, CFMM_E_UNSUPPORTED, "solve: the second-order method cannot take this problem: %s", why);
     const int n = ctx->n;
-    int rc = smooth_buffers(ctx, true); if (rc) return rc;
+    int rc = settle(ctx); if (rc) return rc;             // (a first-order prelude may have left its tail in flight)
+    rc = smooth_buffers(ctx, true); if (rc) return rc;
     const std::vector<double> &c = ctx->hc, &h = ctx->hh;
     const std::vector<int> &ct = ctx->hctype;
 
@@ -2283,9 +2304,18 @@ int cfmm_create(int device, int n_tokens, cfmm_ctx **out)
         std::memset(ctx->util_h, 0, ctx->util_span);
     }
     lap("device + pinned arenas");
-    TRY_C(hipHostMalloc((void **)&ctx->hstat_h, 64 + ITER_HRING * sizeof(unsigned long long), hipHostMallocMapped));      // (8 progress words | the per-launch ring)
+    TRY_C(hipHostMalloc((void **)&ctx->hstat_h, 64 + ITER_HRING * sizeof(unsigned long long) + 64, hipHostMallocMapped));      // (8 progress words | the per-launch ring | the envelope record)
     TRY_C(hipHostGetDevicePointer((void **)&ctx->hstat_d, (void *)ctx->hstat_h, 0));
     *ctx->hstat_h = 0;
+    static_assert(sizeof(EnvRec) <= 64, "the envelope record has 64 bytes behind the ring");
+    ctx->env_h = reinterpret_cast<volatile EnvRec *>(ctx->hstat_h + 8 + ITER_HRING);
+    ctx->env_d = reinterpret_cast<EnvRec *>(ctx->hstat_d + 8 + ITER_HRING);
+    ctx->env_h->prog = 0; ctx->env_h->seal = 0; ctx->env_h->t0 = 0; ctx->env_h->t1 = 0;
+    {
+        int khz = 0;
+        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) ctx->wall_clock_hz = 1e3 * khz;
+        else (void)hipGetLastError();
+    }
     lap("mapped progress word");
     for (int i = 0; i < 2; ++i) TRY_C(hipEventCreateWithFlags(&ctx->ev[i], hipEventDisableTiming));
     TRY_C(hipEventCreate(&ctx->ev_t0));
@@ -2325,6 +2355,7 @@ int cfmm_clone(cfmm_ctx *src, cfmm_ctx **out)
 {
     if (!src || !out) return CFMM_E_ARG;
     HIP_TRY(src, hipSetDevice(src->device));
+    { int rc_ = settle(src); if (rc_) return rc_; }
     pools_ready(src);
     HIP_TRY(src, hipStreamSynchronize(src->stream));         // (the pools the clone will read may still be arriving)
     release_landed(src);                                     // (behind that synchronisation: clones never see a non-empty landing list)
@@ -2349,7 +2380,8 @@ int cfmm_destroy(cfmm_ctx *ctx)
 {
     if (!ctx) return CFMM_OK;
     (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);      // (the tail of a sealed solve included: the records it touches go below)
+    ctx->tail = false;
     drop_graph(ctx);
     if (ctx->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(ctx->comm);
     for (void *q : ctx->os_opened) (void)hipIpcCloseMemHandle(q);
@@ -2566,10 +2598,15 @@ struct PoolEntry {
     PoolStore &ps;
     const bool reader;
     hipError_t device;
-    explicit PoolEntry(cfmm_ctx *c, bool rd = true) : ctx(c), ps(*c->pools), reader(rd)
+    // keep_tail: cfmm_solve alone -- a sealed solve may follow a sealed solve without draining the stream in between (cfmm_ctx::tail);
+    // whichever other path the solve takes settles in its own time
+    explicit PoolEntry(cfmm_ctx *c, bool rd = true, bool keep_tail = false) : ctx(c), ps(*c->pools), reader(rd)
     {
         if (reader) { std::lock_guard<std::mutex> g(ps.mu); ++ps.readers; }
-        if ((device = hipSetDevice(c->device)) == hipSuccess) pools_ready(c);
+        if ((device = hipSetDevice(c->device)) == hipSuccess) {
+            if (!keep_tail && c->tail) { c->tail = false; device = hipStreamSynchronize(c->stream); }
+            if (device == hipSuccess) pools_ready(c);
+        }
     }
     ~PoolEntry() { release_landed(ctx); if (reader) { std::lock_guard<std::mutex> g(ps.mu); --ps.readers; } }
 };
@@ -2592,6 +2629,7 @@ extern "C++" {          // (templates need C++ linkage)
 static int upload_begin(cfmm_ctx *ctx, const char *who, const void *old_arena)
 {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     if (ctx->pools.use_count() > 1) return fail(ctx, CFMM_E_STATE, "%s: the pools are shared with a clone (cfmm_clone); destroy the clones first", who);
     if (old_arena) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CFMM_OK;
@@ -3086,6 +3124,7 @@ int cfmm_set_utility(cfmm_ctx *ctx, const double *c, const double *h, const int3
 {
     if (!ctx || !c) return ctx ? fail(ctx, CFMM_E_ARG, "set_utility: c is NULL") : CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     const int n = ctx->n;
     bool general = false;
     for (int j = 0; j < n; ++j) {
@@ -3127,6 +3166,7 @@ int cfmm_set_ties(cfmm_ctx *ctx, int n_groups, const int32_t *grp, const double 
 {
     if (!ctx) return CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     const int n = ctx->n;
     if (!grp) {
         ctx->ng = n;
@@ -3174,6 +3214,7 @@ int cfmm_set_nu(cfmm_ctx *ctx, const double *nu)
 {
     if (!ctx || !nu) return CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     { int rc = check_prices(ctx, "set_nu: nu", nu); if (rc) return rc; }
     // through the context's own pinned vector: the caller's (pageable) buffer may go away after we return, and copying it
     // here spares a stream synchronisation per solve (the previous copy out of hnu0 has completed: every solve ends synchronised)
@@ -3188,6 +3229,7 @@ int cfmm_get_nu(cfmm_ctx *ctx, double *nu)
 {
     if (!ctx || !nu) return CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     HIP_TRY(ctx, hipMemcpyAsync(nu, ctx->nu_acc, ctx->n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CFMM_OK;
@@ -3197,6 +3239,7 @@ int cfmm_get_psi(cfmm_ctx *ctx, double *psi)
 {
     if (!ctx || !psi) return CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     pools_seen(ctx);
     HIP_TRY(ctx, hipMemcpyAsync(psi, ctx->psi_acc, ctx->n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -3213,6 +3256,7 @@ int cfmm_get_solution(cfmm_ctx *ctx, double *nu, double *psi)
         return CFMM_OK;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     if (nu) HIP_TRY(ctx, hipMemcpyAsync(nu, ctx->nu_acc, ctx->n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (psi) HIP_TRY(ctx, hipMemcpyAsync(psi, ctx->psi_acc, ctx->n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -3301,6 +3345,7 @@ int cfmm_debug_cholesky(cfmm_ctx *ctx, int n, const double *A, const double *b, 
 {
     if (!ctx || !A || !b || !x || n != ctx->n) return ctx ? fail(ctx, CFMM_E_ARG, "debug_cholesky: n must equal the context's token count") : CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     int rc = smooth_buffers(ctx, true); if (rc) return rc;
     const int ld = hess_ld(n);
     std::vector<double> hd(n, 0.0);
@@ -3326,6 +3371,7 @@ int cfmm_debug_cholesky_apply(cfmm_ctx *ctx, int n, const double *b, double *x)
 {
     if (!ctx || !b || !x || n != ctx->n || !ctx->H) return ctx ? fail(ctx, CFMM_E_STATE, "debug_cholesky_apply: call cfmm_debug_cholesky first") : CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     HIP_TRY(ctx, hipMemcpyAsync(ctx->sm_vec + n, b, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     { int rc = launch_chord(ctx, n, ctx->sm_vec + n, ctx->sm_vec); if (rc) return rc; }
     HIP_TRY(ctx, hipMemcpyAsync(x, ctx->sm_vec, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -3435,7 +3481,7 @@ static int solve_tiny_kinks(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out)
 int cfmm_solve(cfmm_ctx *ctx, const double *nu0, const cfmm_opts *opts_in, cfmm_stats *out)
 {
     if (!ctx || !out) return CFMM_E_ARG;
-    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
+    PoolEntry entry(ctx, true, true); HIP_TRY(ctx, entry.device);      // (the tail of a sealed solve stays: solve_lbfgs)
     drop_tenders(ctx);
     cfmm_opts o;
     if (opts_in) o = *opts_in; else cfmm_default_opts(&o);
@@ -3582,13 +3628,31 @@ static int solve_lbfgs(cfmm_ctx *ctx, const cfmm_opts &o_in, cfmm_stats *out)
     // single GPU, one launch per iteration, eager run-ahead: the kernels leave the result in pinned memory themselves
     static const bool zc_off = getenv("CFMM_ZERO_COPY") && atoi(getenv("CFMM_ZERO_COPY")) == 0;     // (A/B)
     const bool zero_copy = fused && !shard && !use_graph_opt && !ctx->det && !zc_off;
+    // ... and the host neither synchronises the stream nor records events around the solve: the result is read once a launch behind the
+    // one that stored it has sealed it, progress and seal are told from those of other solves by the epoch, the device time comes from
+    // the launches' own stamps (iterate.hpp: EnvRec).  CFMM_ENVELOPE=classic: the synchronised envelope (A/B)
+    static const bool env_classic = getenv("CFMM_ENVELOPE") && !strcmp(getenv("CFMM_ENVELOPE"), "classic");
+    const bool sealed = zero_copy && !env_classic && o.max_evals < 0xffffff;      // (the words carry 24 bits of evaluation count)
+    unsigned epoch = 0;
+    if (sealed) {
+        if (++ctx->epoch == 0) ++ctx->epoch;
+        epoch = ctx->epoch;
+        ia.env = ctx->env_d; ia.epoch = epoch; ia.hstat = nullptr;
+    } else {
+        // (whatever a sealed solve left in flight: this path resets words and reads records the old way)
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->tail = false;
+    }
+    // (sealed: the one thing of the previous solve that a launch in flight could still write is not this record -- the launch that
+    //  stores it ran in front of the seal the host has seen)
     if (zero_copy) { ia.h_nu_acc = ctx->hsol_d; ia.h_psi_acc = ctx->hsol_d + n; ia.h_final = ctx->hst_d; ctx->hst[0] = DevState{}; }
 
     // ---- timed region: the outer loop (upload and trade read-back excluded) ----------------
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
-    *ctx->hstat_h = 0;                                     // (the stream is idle: nothing can still write the progress word)
+    if (!sealed) {
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
+        *ctx->hstat_h = 0;                                 // (the stream is idle: nothing can still write the progress word)
+    }
     if (ctx->det) HIP_TRY(ctx, hipMemsetAsync(ctx->acc_l, 0, 6 * (size_t)n * sizeof(unsigned long long), ctx->stream));
     if (fused) {
         // launch 0: the start point and the first evaluation (with the diagonal metric) into state / accumulator set 0
@@ -3597,7 +3661,7 @@ static int solve_lbfgs(cfmm_ctx *ctx, const cfmm_opts &o_in, cfmm_stats *out)
         double *x0 = ctx->xs3;
         ua.s = x0; ua.s_t = x0 + ia.xvs; ua.Gs = x0 + 2 * ia.xvs; ua.d = x0 + 3 * ia.xvs; ua.nu = x0 + 4 * ia.xvs; ua.st = ctx->st3;
         hipLaunchKernelGGL(start_kernel<false>, dim3(1), dim3(UPD_THREADS), upd_lds_bytes(ctx->ng), ctx->stream, ua, nu_src,
-                           ctx->acc3, (long long)(3 * aset), ctx->st3 + 1, 2);
+                           ctx->acc3, (long long)(3 * aset), ctx->st3 + 1, 2, sealed ? (long long *)&ctx->env_d->t0 : (long long *)nullptr);
         for (int stable = 0; stable < 2; ++stable) {
             EvalArgs e0 = make_eval_args(ctx, stable != 0);
             e0.nu = ua.nu; e0.acc = ctx->acc3;
@@ -3644,15 +3708,25 @@ static int solve_lbfgs(cfmm_ctx *ctx, const cfmm_opts &o_in, cfmm_stats *out)
         // copy engine).  No graph-replay gaps (~19 us per replay), and only `run_ahead` idle launches behind the end.
         const auto spin0 = std::chrono::steady_clock::now();
         long spins = 0;
+        int done = 0;
         for (;;) {
-            const unsigned long long w = *ctx->hstat_h;
-            const int done = (int)(w & 0xffffffffu);
-            status = (int)(w >> 32);
+            if (sealed) {                                  // (a word of another epoch is an earlier solve's: nothing reported yet)
+                const unsigned long long w = ctx->env_h->prog;
+                const bool cur = (unsigned)(w >> 32) == epoch;
+                done = cur ? (int)(w & 0xffffffu) : 0;
+                status = cur ? (int)((w >> 24) & 0xffu) : 0;
+            } else {
+                const unsigned long long w = *ctx->hstat_h;
+                done = (int)(w & 0xffffffffu);
+                status = (int)(w >> 32);
+            }
             if (status != 0) break;
             if (t > o.max_evals + 1) {                     // every evaluation the budget allows is enqueued: the device ends it (status 3)
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                break;
-            }
+                if (!sealed) {
+                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                    break;
+                }                                          // (sealed: the last of them reports the end like any other)
+            } else
             if (t - done <= ctx->run_ahead) {
                 int rc = enqueue_fused_iteration(ctx, ia, t); if (rc) return rc;
                 ++t; spins = 0;
@@ -3664,6 +3738,10 @@ static int solve_lbfgs(cfmm_ctx *ctx, const cfmm_opts &o_in, cfmm_stats *out)
             }
         }
         HIP_TRY(ctx, hipGetLastError());
+        // sealed: the launch that ended the solve is launch `done` (every update counts one evaluation); the result it and two other
+        // workgroups stored counts as complete once a launch BEHIND it says so -- if the host had not run that far ahead, one more goes
+        // out to say it
+        if (sealed && t < done + 2) { int rc = enqueue_fused_iteration(ctx, ia, t); if (rc) return rc; ++t; HIP_TRY(ctx, hipGetLastError()); }
     } else if (fused && shard && !use_graph) {
         // Pool-sharded through RCCL, one launch per iteration: chunks of `iters_per_graph` launches (each with its collective) enqueued
         // eagerly, the decision to go on taken one chunk behind -- on the progress slot of the LAST launch of the previous chunk, which that
@@ -3710,13 +3788,25 @@ static int solve_lbfgs(cfmm_ctx *ctx, const cfmm_opts &o_in, cfmm_stats *out)
             if (status != 0) break;
         }
     }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
+    if (!sealed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
     if (zero_copy) {
         // the kernels have left the result in pinned memory themselves (iterate.hpp: h_nu_acc / h_psi_acc / h_final)
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        bool drained = !sealed;
+        if (sealed) {
+            // wait for the seal of THIS solve; a device that does not deliver it (an error, 120 s) is asked the old way
+            const auto spin0 = std::chrono::steady_clock::now();
+            long spins = 0;
+            while ((unsigned)(ctx->env_h->seal >> 32) != epoch) {
+                if ((++spins & 0xfffff) == 0 && (hipGetLastError() != hipSuccess || std::chrono::duration<double>(std::chrono::steady_clock::now() - spin0).count() > 120.0)) { drained = true; break; }
+            }
+            std::atomic_thread_fence(std::memory_order_acquire);
+            ctx->tail = !drained;                          // (launches behind the sealing one may still be in flight: cfmm_ctx::tail)
+        }
+        if (drained) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         hring[0] = ctx->hst[0];
         for (int q = 1; q < nst; ++q) hring[q] = DevState{};
         if (hring[0].status == 0) {              // (the device ended without a final record: cannot happen -- read it the slow way)
+            { int rc = settle(ctx); if (rc) return rc; }
             HIP_TRY(ctx, hipMemcpy(hring, dst, nst * sizeof(DevState), hipMemcpyDeviceToHost));
             HIP_TRY(ctx, hipMemcpy(ctx->hsol, ctx->nu_acc, n * sizeof(double), hipMemcpyDeviceToHost));
             HIP_TRY(ctx, hipMemcpy(ctx->hsol + n, ctx->psi_acc, n * sizeof(double), hipMemcpyDeviceToHost));
@@ -3731,7 +3821,14 @@ static int solve_lbfgs(cfmm_ctx *ctx, const cfmm_opts &o_in, cfmm_stats *out)
     { double mx = 0.0; for (int j = 0; j < n; ++j) mx = std::max(mx, ctx->hsol[j]); if (mx > 0.0 && std::isfinite(mx)) ctx->nu_max = mx; }
     const auto t1 = std::chrono::steady_clock::now();
     float ms = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1));
+    double dev_s = 0.0;
+    if (sealed) {                                          // start of the first launch .. start of the launch that found the solve ended
+        const long long c0 = ctx->env_h->t0, c1 = ctx->env_h->t1;
+        if (c1 > c0) dev_s = (double)(c1 - c0) / ctx->wall_clock_hz;
+    } else {
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1));
+        dev_s = ms * 1e-3;
+    }
 
     const DevState st = newest(hring);
     std::memset(out, 0, sizeof *out);
@@ -3739,7 +3836,7 @@ static int solve_lbfgs(cfmm_ctx *ctx, const cfmm_opts &o_in, cfmm_stats *out)
     out->n_ranks = ctx->n_ranks;
     out->dual_value = st.f; out->primal_value = st.primal; out->gap = st.gap; out->infeas = st.infeas;
     out->wall_seconds = std::chrono::duration<double>(t1 - t0).count();
-    out->device_seconds = ms * 1e-3;
+    out->device_seconds = dev_s;
     out->pg = st.pg;
     out->pool_subproblems = (int64_t)st.evals * cfmm_pool_count(ctx);
     out->method = CFMM_METHOD_LBFGS;
@@ -3872,7 +3969,7 @@ int cfmm_solve_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu0, co
         if (nu0 && nu0[b]) { int rc = cfmm_set_nu(c, nu0[b]); if (rc) { c0->err = c->err; return rc; } }
         if (!c->pt.have_nu) return fail(c0, CFMM_E_STATE, "solve_batch: context %d has no start prices", b);
         point_from_caller(c);
-        HIP_TRY(c0, hipStreamSynchronize(c->stream));
+        HIP_TRY(c0, hipStreamSynchronize(c->stream)); c->tail = false;
     }
     if (cfmm_pool_count(c0) == 0) return fail(c0, CFMM_E_STATE, "solve_batch: no pools uploaded");
     if (!c0->upd_batch_d) {
@@ -4000,7 +4097,7 @@ int cfmm_eval_dual_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu,
     // the prices become every context's point (nu_acc) and its trial prices (nu) with a clear stop flag behind them; accumulators zeroed
     for (int b = 0; b < nb; ++b) {
         cfmm_ctx *c = ctxs[b];
-        HIP_TRY(c0, hipStreamSynchronize(c->stream));
+        HIP_TRY(c0, hipStreamSynchronize(c->stream)); c->tail = false;
         std::memcpy(c->hnu0, nu[b], n * sizeof(double));
         HIP_TRY(c0, hipMemcpyAsync(c->nu_acc, c->hnu0, n * sizeof(double), hipMemcpyHostToDevice, stream));
         HIP_TRY(c0, hipMemcpyAsync(c->nu, c->hnu0, n * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -4580,6 +4677,7 @@ int cfmm_comm_init(cfmm_ctx *ctx, int n_ranks, int rank, const void *uid128)
 {
     if (!ctx || n_ranks < 1 || rank < 0 || rank >= n_ranks || !uid128) return ctx ? fail(ctx, CFMM_E_ARG, "comm_init: bad arguments") : CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     std::string err;
     if (!g_rccl.load(err)) return fail(ctx, CFMM_E_RCCL, "%s", err.c_str());
     ncclUniqueId id;
@@ -4648,6 +4746,7 @@ int cfmm_oneshot_export(cfmm_ctx *ctx, void *handle64)
 {
     if (!ctx || !handle64) return CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     { int rc = oneshot_alloc(ctx); if (rc) return rc; }
     hipIpcMemHandle_t h;
     static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size");
@@ -4661,6 +4760,7 @@ int cfmm_oneshot_attach(cfmm_ctx *ctx, int n_ranks, int rank, void *const *mailb
     if (!ctx || !mailboxes || n_ranks < 1 || n_ranks > ONESHOT_MAX_RANKS || rank < 0 || rank >= n_ranks)
         return ctx ? fail(ctx, CFMM_E_ARG, "oneshot_attach: %d ranks (at most %d), rank %d", n_ranks, ONESHOT_MAX_RANKS, rank) : CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     { int rc = oneshot_alloc(ctx); if (rc) return rc; }
     if (ctx->comm && ctx->n_ranks != n_ranks) return fail(ctx, CFMM_E_STATE, "oneshot_attach: the RCCL communicator has %d ranks", ctx->n_ranks);
     for (int r = 0; r < n_ranks; ++r) {
@@ -4698,6 +4798,7 @@ int cfmm_oneshot_enable(cfmm_ctx *ctx, int on)
     if (on && !ctx->os_peers[ctx->rank]) return fail(ctx, CFMM_E_STATE, "oneshot_enable: no mailboxes attached (cfmm_oneshot_import / _attach first)");
     if (!on && !ctx->comm && ctx->os_ready) return fail(ctx, CFMM_E_STATE, "oneshot_enable(0): no RCCL communicator to fall back on");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if ((on != 0) != ctx->os_ready) drop_graph(ctx);
     ctx->os_ready = on != 0; ctx->g_counts_valid = false;
@@ -4708,6 +4809,7 @@ int cfmm_selftest(cfmm_ctx *ctx)
 {
     if (!ctx) return CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     int *d = nullptr, h = -1;
     HIP_TRY(ctx, hipMalloc((void **)&d, sizeof(int)));
     HIP_TRY(ctx, hipMemsetAsync(d, 0, sizeof(int), ctx->stream));
@@ -4728,6 +4830,7 @@ int cfmm_debug_timers(cfmm_ctx *ctx, int64_t *out64)
 {
     if (!ctx || !out64) return CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(out64, ctx->ts, (64 + 8 * 4096 + 2048) * sizeof(int64_t), hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemset(ctx->ts, 0, (64 + 8 * 4096 + 2048) * sizeof(int64_t)));
@@ -4746,6 +4849,7 @@ int cfmm_clock_probe_start(cfmm_ctx *ctx, double period_us, double max_ms)
 {
     if (!ctx || !(period_us >= 1.0) || !(max_ms > 0.0) || max_ms > 60000.0) return CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     if (ctx->probe_running) return fail(ctx, CFMM_E_STATE, "clock probe: already running (cfmm_clock_probe_stop first)");
     if (!ctx->probe_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->probe_stream, hipStreamNonBlocking));
     if (!ctx->probe_ring) {
@@ -4801,6 +4905,7 @@ int cfmm_time_xcd_handoff(cfmm_ctx *ctx, int np, int reps, double *out7)
     double *out6 = out7;
     if (!ctx || !out6 || np < 1 || np > 8192 || reps < 1) return CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     const int grid = ctx->cus;
     double *pub = nullptr; unsigned long long *flag = nullptr; long long *stamps = nullptr;
     HIP_TRY(ctx, hipMalloc(&pub, (size_t)16 * np * sizeof(double)));
@@ -4946,6 +5051,7 @@ int cfmm_time_collective(cfmm_ctx *ctx, int reps, double *fold_sec, double *allr
 {
     if (!ctx || reps < 1) return CFMM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = settle(ctx); if (rc_) return rc_; }
     const int n = ctx->n, len = acc_arb(n) + 1;
     float ms = 0.f;
     HIP_TRY(ctx, hipMemsetAsync(ctx->acc, 0, (size_t)ctx->nslices * acc_stride(n) * sizeof(double), ctx->stream));

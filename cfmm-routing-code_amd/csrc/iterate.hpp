@@ -51,6 +51,21 @@ __host__ __device__ inline unsigned long long iter_hring_word(int evals, int sta
 {
     return (unsigned long long)((unsigned)evals & 0xffffffu) | ((unsigned long long)((unsigned)status & 0xffu) << 24) | ((unsigned long long)(unsigned)launch << 32);
 }
+// The envelope record of a first-order solve that never synchronises its stream (pinned HOST memory, mapped; DESIGN.md "The sealed
+// result"; docs/solve_envelope.md).  `prog` and `seal` are iter_hring_word(evals, status, EPOCH): the context counts its solves, every
+// launch carries its solve's count, and the host believes a word only under the count of the solve it is waiting for -- the idle
+// launches a finished solve leaves in the stream can neither report progress nor seal for the next one, and no word is ever reset.
+//   prog  stored with the state record by the workgroup that stores it (as IterArgs::hstat): the host's run-ahead control.
+//         status != 0 there does NOT say that the result is complete -- the accepted prices, their net trade and the final record
+//         are stored by three different workgroups of that launch.
+//   seal  stored by the launches that find the solve ended (the early exit of iter_kernel).  They run behind the kernel boundary
+//         that follows the launch which stored the result, so the host may read the result once it sees the seal.
+//   t0    the constant-rate device clock at the start of the solve's first launch (start_kernel), t1 at the start of the first
+//         launch that found it ended.
+struct EnvRec {
+    unsigned long long prog, seal;
+    long long t0, t1;
+};
 struct IterArgs {
     EvalArgs ev;                    // tile space of the evaluation (ev.nu / ev.acc are not used here)
     int n, M, nread, phase;         // nread: accumulator slices to read (nslices, or 1 behind an all-reduce)
@@ -72,9 +87,11 @@ struct IterArgs {
     unsigned long long *hring;
     int launch;
     // pinned HOST mirrors (mapped; null = none): the accepted prices / net trade are stored there as well whenever a point is
-    // accepted, the state record when the solve ends -- the host reads its result after one synchronisation, no copies
+    // accepted, the state record when the solve ends -- the host reads its result there, no copies: behind one synchronisation, or behind the seal (EnvRec)
     double *h_nu_acc, *h_psi_acc;
     DevState *h_final;
+    EnvRec *env;                            // null: the host synchronises the stream behind the solve (hstat, events)
+    unsigned epoch;
 };
 
 template <int E> __device__ __forceinline__ void ldE(const double *p, int first, double (&v)[E]);
@@ -359,6 +376,10 @@ iter_kernel(IterArgs a)
         if (blockIdx.x == 0 && tid == 0) {
             a.st3[p] = st;                               // the final state is handed on, or the launch after next would read a set
             if (a.hring) __hip_atomic_store(a.hring + (a.launch & (ITER_HRING - 1)), iter_hring_word(st.evals, st.status, a.launch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (a.env) {                                 // the launch that stored the result lies behind a kernel boundary: seal it (EnvRec)
+                if (a.launch == st.evals + 1) a.env->t1 = wall_clock64();      // (the first launch behind the end: every update counts one evaluation)
+                __hip_atomic_store(&a.env->seal, iter_hring_word(st.evals, st.status, (int)a.epoch), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
         }
         return;                                          // from before the end (status 0) and resume from stale state
     }
@@ -681,7 +702,8 @@ iter_kernel(IterArgs a)
                 a.st3[p] = st; a.nu[n] = st.status != 0 ? 1.0 : 0.0;
                 if (st.status != 0 && a.h_final) *a.h_final = st;
                 // progress word for the host (system-scope store into pinned host memory: no copy, no API call on the host side)
-                if (a.hstat) __hip_atomic_store(a.hstat, (unsigned long long)(unsigned)st.evals | ((unsigned long long)(unsigned)st.status << 32),
+                if (a.env) __hip_atomic_store(&a.env->prog, iter_hring_word(st.evals, st.status, (int)a.epoch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                else if (a.hstat) __hip_atomic_store(a.hstat, (unsigned long long)(unsigned)st.evals | ((unsigned long long)(unsigned)st.status << 32),
                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 if (a.hring) __hip_atomic_store(a.hring + (a.launch & (ITER_HRING - 1)), iter_hring_word(st.evals, st.status, a.launch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }

@@ -2397,8 +2397,11 @@ selftest_log_kernel(int *out)
 // start of a solve: group variable = mean over members of (log nu0_j - off_j), clamped
 template <bool BATCH = false>
 __global__ void __launch_bounds__(UPD_THREADS)
-start_kernel(UpdArgs a0, const double *nu0_, double *zero, long long nzero, DevState *st_clear, int n_clear)
+start_kernel(UpdArgs a0, const double *nu0_, double *zero, long long nzero, DevState *st_clear, int n_clear, long long *t0_stamp = nullptr)
 {
+    // (t0_stamp: pinned host word that takes the device's constant-rate clock at the start of a solve's first launch -- the
+    //  first-order solve that does not synchronise the stream takes its device time from such stamps; iterate.hpp: EnvRec)
+    if (t0_stamp && blockIdx.x == 0 && threadIdx.x == 0) *t0_stamp = wall_clock64();
     // (batched: workgroup b starts solve b from ITS previous / given prices a.nu_acc, and clears its own accumulator)
     const UpdArgs &a = upd_args<BATCH>(a0);
     const double *nu0 = BATCH ? a.nu_acc : nu0_;
