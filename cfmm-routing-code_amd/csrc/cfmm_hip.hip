@@ -40,6 +40,7 @@
 #include "phik.hpp"
 #include "update.hpp"
 #include "handoff.hpp"
+#include "solve_plan.hpp"
 
 using namespace cfmm;
 
@@ -3596,251 +3597,383 @@ int cfmm_solve(cfmm_ctx *ctx, const double *nu0, const cfmm_opts *opts_in, cfmm_
     return rc;
 }
 
-static int solve_lbfgs(cfmm_ctx *ctx, const cfmm_opts &o_in, cfmm_stats *out)
-{
-    const int n = ctx->n;
-    drop_barrier(ctx);
-    cfmm_opts o = o_in;
-    // One launch per iteration (iterate.hpp) whenever the update fits the evaluation launch; otherwise the
-    // two-launch iteration (evaluation kernel, single-workgroup update kernel).
-    const EvalArgs ea_tiny = make_eval_args(ctx, false, 0x7fffffff, false);
-    const bool tiny = tiny_applies(ctx, ea_tiny, o);
-    const bool fused = !tiny && fused_applies(ctx, o);
-    if (fused) o.iters_per_graph = (o.iters_per_graph + 2) / 3 * 3;       // the rotation phase t % 3 is baked into captured launches
-    // pool-sharded through RCCL: the chunked scheme polls one chunk behind, so a solve leaves up to two chunks of iterations
-    // -- each with a live collective and RCCL's ~35 us of host time per call -- behind its end: short chunks
-    // (a one-rank communicator's collective is free: there the polls cost more than the idle iterations, 0.79 vs 0.75 ms)
-    if (sharded(ctx) && ctx->n_ranks > 1 && !oneshot_runahead(ctx) && !ctx->multi_graph) o.iters_per_graph = 3;
-    // Single GPU: `iters_per_graph` iterations are replayed from one captured hipGraph.  Pool-sharded
-    // (RCCL all-reduce inside every iteration): the same iterations are enqueued eagerly, the way RCCL
-    // is conventionally driven (CFMM_MULTI_GRAPH=1 opts into capturing them too).
-    static const bool graph_forced = getenv("CFMM_FUSED_GRAPH") && atoi(getenv("CFMM_FUSED_GRAPH")) != 0;     // (A/B: replay the fused launches from a graph)
-    const bool shard = sharded(ctx);
-    const bool use_graph_opt = fused && !shard && graph_forced;
-    const bool use_graph = !tiny && (!shard || (ctx->multi_graph && !ctx->os_ready)) && !ctx->no_graph && (!fused || shard || graph_forced);
-    if (use_graph && (!ctx->g_valid || !same_opts(o, ctx->g_opts))) { int rc = build_graph(ctx, o); if (rc) return rc; }
-    UpdArgs ua = make_upd_args(ctx, o);
-    IterArgs ia = make_iter_args(ctx, o);
-    const size_t aset = acc_set_doubles(ctx);
-    // the start prices: nu_acc, or -- handed over by cfmm_solve without a copy -- the mapped pinned staging vector
-    const double *nu_src = ctx->nu0_deferred ? ctx->hnu0_d : ctx->nu_acc;
-    ctx->nu0_deferred = false;                             // (the start kernel writes nu_acc)
-    // single GPU, one launch per iteration, eager run-ahead: the kernels leave the result in pinned memory themselves
-    static const bool zc_off = getenv("CFMM_ZERO_COPY") && atoi(getenv("CFMM_ZERO_COPY")) == 0;     // (A/B)
-    const bool zero_copy = fused && !shard && !use_graph_opt && !ctx->det && !zc_off;
-    // ... and the host neither synchronises the stream nor records events around the solve: the result is read once a launch behind the
-    // one that stored it has sealed it, progress and seal are told from those of other solves by the epoch, the device time comes from
-    // the launches' own stamps (iterate.hpp: EnvRec).  CFMM_ENVELOPE=classic: the synchronised envelope (A/B)
-    static const bool env_classic = getenv("CFMM_ENVELOPE") && !strcmp(getenv("CFMM_ENVELOPE"), "classic");
-    const bool sealed = zero_copy && !env_classic && o.max_evals < 0xffffff;      // (the words carry 24 bits of evaluation count)
-    unsigned epoch = 0;
-    if (sealed) {
-        if (++ctx->epoch == 0) ++ctx->epoch;
-        epoch = ctx->epoch;
-        ia.env = ctx->env_d; ia.epoch = epoch; ia.hstat = nullptr;
-    } else {
-        // (whatever a sealed solve left in flight: this path resets words and reads records the old way)
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->tail = false;
+// ---- the first-order solve: a plan (solve_plan.hpp), one driver per plan, one result reader -----------------------------------------
+
+// A host loop that polls pinned memory must not hang for ever on a dead device: every 2^20 spins it asks the runtime for an error and
+// the clock for its 120 s (counted from the start of the loop; `progress` restarts the spin count only).
+struct SpinWatch {
+    const std::chrono::steady_clock::time_point since = std::chrono::steady_clock::now();
+    long spins = 0;
+    void progress() { spins = 0; }
+    bool expired()
+    {
+        return (++spins & 0xfffff) == 0 &&
+               (hipGetLastError() != hipSuccess || std::chrono::duration<double>(std::chrono::steady_clock::now() - since).count() > 120.0);
     }
+    static int stalled(cfmm_ctx *ctx, const char *who, int launch, int done)
+    {
+        return fail(ctx, CFMM_E_HIP, "%s: the device stopped reporting progress (launch %d, %d done)", who, launch, done);
+    }
+};
+
+// the largest price of the solution in hsol: the scale cfmm_ctx::nu_max keeps
+static void refresh_nu_max(cfmm_ctx *ctx)
+{
+    double mx = 0.0;
+    for (int j = 0; j < ctx->n; ++j) mx = std::max(mx, ctx->hsol[j]);
+    if (mx > 0.0 && std::isfinite(mx)) ctx->nu_max = mx;
+}
+
+// what a first-order solve reports, from its final state record; false -- and CFMM_E_NUMERIC as the status -- when the dual value is not finite
+static bool stats_from_state(const DevState &st, int n_ranks, int64_t pools, double wall_s, double dev_s, cfmm_stats *s)
+{
+    std::memset(s, 0, sizeof *s);
+    s->evals = st.evals; s->iters = st.iters; s->status = st.status ? st.status : 3;
+    s->n_ranks = n_ranks;
+    s->dual_value = st.f; s->primal_value = st.primal; s->gap = st.gap; s->infeas = st.infeas;
+    s->wall_seconds = wall_s;
+    s->device_seconds = dev_s;
+    s->pg = st.pg;
+    s->pool_subproblems = (int64_t)st.evals * pools;
+    s->method = CFMM_METHOD_LBFGS;
+    if (std::isfinite(st.f)) return true;
+    s->status = CFMM_E_NUMERIC;
+    return false;
+}
+
+// the facts plan_first_order decides on; the three A/B switches are read once per process, here
+static PlanFacts plan_facts(cfmm_ctx *ctx, const EvalArgs &ea_tiny, const cfmm_opts &o)
+{
+    static const bool fused_graph = getenv("CFMM_FUSED_GRAPH") && atoi(getenv("CFMM_FUSED_GRAPH")) != 0;
+    static const bool zero_copy_off = getenv("CFMM_ZERO_COPY") && atoi(getenv("CFMM_ZERO_COPY")) == 0;
+    static const bool envelope_classic = getenv("CFMM_ENVELOPE") && !strcmp(getenv("CFMM_ENVELOPE"), "classic");
+    PlanFacts f;
+    f.tiny_applies = tiny_applies(ctx, ea_tiny, o);
+    f.fused_applies = fused_applies(ctx, o);
+    f.sharded = sharded(ctx); f.n_ranks = ctx->n_ranks; f.oneshot_runahead = oneshot_runahead(ctx);
+    f.multi_graph = ctx->multi_graph; f.os_ready = ctx->os_ready; f.no_graph = ctx->no_graph; f.det = ctx->det;
+    f.iters_per_graph = o.iters_per_graph; f.max_evals = o.max_evals;
+    f.fused_graph = fused_graph; f.zero_copy_off = zero_copy_off; f.envelope_classic = envelope_classic;
+    return f;
+}
+
+// one first-order solve on its way through its driver: what the prologue made, and what the driver leaves for the result reader
+struct FirstOrderRun {
+    cfmm_ctx *ctx;
+    cfmm_opts o;                                   // (iters_per_graph: the plan's -- the key of the graph cache)
+    FirstOrderPlan plan;
+    UpdArgs ua;
+    IterArgs ia;
+    const double *nu_src;                          // the start prices: nu_acc, or -- handed over by cfmm_solve without a copy -- the mapped pinned staging vector
+    unsigned epoch = 0;                            // of a sealed solve
+    std::chrono::steady_clock::time_point t0;      // the timed region: the outer loop (upload and trade read-back excluded)
+};
+
+// The state lives in ONE DevState (two-launch iteration, tiny) or in three rotating ones, of which the newest counts
+struct StateRecords { DevState *host; const DevState *dev; int count; };
+static StateRecords state_records(cfmm_ctx *ctx, bool fused)
+{
+    return fused ? StateRecords{ctx->hst3, ctx->st3, 3} : StateRecords{ctx->hst, ctx->st, 1};
+}
+static const DevState &newest_state(const DevState *h, int count)
+{
+    int b = 0;
+    for (int q = 1; q < count; ++q) if (h[q].evals > h[b].evals) b = q;      // (every update counts one evaluation)
+    return h[b];
+}
+
+// the entry of every solve but a sealed one: whatever a sealed solve left in flight is waited for (this path resets words and reads
+// records the old way) ...
+static int enter_drained(cfmm_ctx *ctx)
+{
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->tail = false;
+    return CFMM_OK;
+}
+// ... and the timed region opens with an event
+static int open_timed(FirstOrderRun &r)
+{
+    r.t0 = std::chrono::steady_clock::now();
+    HIP_TRY(r.ctx, hipEventRecord(r.ctx->ev_t0, r.ctx->stream));
+    *r.ctx->hstat_h = 0;                           // (the stream is idle: nothing can still write the progress word)
+    return CFMM_OK;
+}
+static int begin_synchronised(FirstOrderRun &r)
+{
+    { int rc = enter_drained(r.ctx); if (rc) return rc; }
+    return open_timed(r);
+}
+
+// The first launches of a solve.  start_kernel forms the start point, reading the start prices where they are; for the one-launch
+// iteration it also clears the three accumulator sets and the two spare state records (three fill / copy operations less on the stream
+// per solve) and, in a sealed solve, stamps the device clock.  Then -- unless the one tiny launch follows -- the first evaluation, with
+// the diagonal metric, and whatever sums it over slices and ranks.
+enum class FirstEval { None, TwoLaunch, Fused };
+static int launch_start(FirstOrderRun &r, FirstEval first, long long *t0_stamp)
+{
+    cfmm_ctx *ctx = r.ctx;
+    const int n = ctx->n;
+    UpdArgs &ua = r.ua;
+    const bool fused = first == FirstEval::Fused;
+    const size_t aset = acc_set_doubles(ctx);
+    if (ctx->det) HIP_TRY(ctx, hipMemsetAsync(ctx->acc_l, 0, 6 * (size_t)n * sizeof(unsigned long long), ctx->stream));
+    if (fused) {                                   // launch 0 works in state / accumulator set 0
+        double *x0 = ctx->xs3;
+        ua.s = x0; ua.s_t = x0 + r.ia.xvs; ua.Gs = x0 + 2 * r.ia.xvs; ua.d = x0 + 3 * r.ia.xvs; ua.nu = x0 + 4 * r.ia.xvs; ua.st = ctx->st3;
+    }
+    hipLaunchKernelGGL(start_kernel<false>, dim3(1), dim3(UPD_THREADS), upd_lds_bytes(ctx->ng), ctx->stream, ua, r.nu_src,
+                       fused ? ctx->acc3 : ctx->acc, (long long)(fused ? 3 * aset : aset), fused ? ctx->st3 + 1 : (DevState *)nullptr, fused ? 2 : 0, t0_stamp);
+    if (first == FirstEval::None) return CFMM_OK;
+    if (first == FirstEval::TwoLaunch) return enqueue_iteration<true>(ctx, ua);
+    for (int stable = 0; stable < 2; ++stable) {
+        EvalArgs e0 = make_eval_args(ctx, stable != 0);
+        e0.nu = ua.nu; e0.acc = ctx->acc3;
+        if (stable) launch_eval<true, true>(ctx, e0); else launch_eval<true, false>(ctx, e0);
+    }
+    if (table_pools(ctx) > 0) launch_table_evals<true>(ctx, ua.nu, ctx->acc3);
+    if (ctx->det) return det_finish(ctx, ctx->acc3, ua.nu, true);
+    if (!sharded(ctx)) return CFMM_OK;
+    if (rccl_unfolded(ctx))                        // (every slice whole, metric included: launch 1 sums them itself)
+        return all_reduce(ctx, ctx->acc3, (size_t)ctx->nslices * acc_stride(n), NCCL_FLOAT64, NCCL_SUM);
+    const int len = acc_stride(n);
+    hipLaunchKernelGGL(fold_kernel, dim3((len + 255) / 256), dim3(256), 0, ctx->stream, ctx->acc3, n, ctx->nslices, 1, (const DevState *)nullptr);
+    return all_reduce(ctx, ctx->acc3, (size_t)len, NCCL_FLOAT64, NCCL_SUM);
+}
+
+static int max_chunks(const cfmm_opts &o) { return (o.max_evals + o.iters_per_graph - 1) / o.iters_per_graph + 1; }
+
+// One workgroup, one launch: every evaluation and update of the solve, nothing of it in global memory (tiny.hpp); the device ends it:
+// converged, stalled, or out of budget.  Nothing to poll: the read-back waits for the one launch.
+static int drive_tiny(FirstOrderRun &r, const EvalArgs &ea)
+{
+    cfmm_ctx *ctx = r.ctx;
+    { int rc = begin_synchronised(r); if (rc) return rc; }
+    { int rc = launch_start(r, FirstEval::None, nullptr); if (rc) return rc; }
+    const int threads = 64 * std::min(TINY_THREADS / 64, std::max(1, ea.ntiles));
+    hipLaunchKernelGGL(solve_tiny_kernel<false>, dim3(1), dim3(threads), (size_t)tiny_lds_doubles(ctx->n) * sizeof(double), ctx->stream, ea, r.ua, r.o.max_evals + 1);
+    HIP_TRY(ctx, hipGetLastError());
+    return CFMM_OK;
+}
+
+// {evaluations done, status} as workgroup 0 of the newest finished launch reported them into pinned memory.  Sealed: the word carries
+// its solve's epoch -- one of another epoch is an earlier solve's: nothing reported yet.
+struct Progress { int done, status; };
+static inline Progress read_progress(const cfmm_ctx *ctx, bool sealed, unsigned epoch)
+{
+    if (sealed) {
+        const unsigned long long w = ctx->env_h->prog;
+        const bool cur = (unsigned)(w >> 32) == epoch;
+        return {cur ? (int)(w & 0xffffffu) : 0, cur ? (int)((w >> 24) & 0xffu) : 0};
+    }
+    const unsigned long long w = *ctx->hstat_h;
+    return {(int)(w & 0xffffffffu), (int)(w >> 32)};
+}
+
+// Single GPU (or pool-sharded through the one-shot exchange), one launch per iteration: launches are enqueued eagerly, a few ahead of
+// the device, whose workgroup 0 reports {evals, status} into a pinned host word as it goes (zero-copy: the host polls memory, no API
+// call, no copy engine).  No graph-replay gaps (~19 us per replay), and only `run_ahead` idle launches behind the end.
+// Sealed (single GPU, the kernels store the result in pinned memory themselves): the host neither synchronises the stream nor records
+// events around the solve -- the result is read once a launch behind the one that stored it has sealed it, progress and seal are told
+// from those of other solves by the epoch, the device time comes from the launches' own stamps (iterate.hpp: EnvRec).
+static int drive_eager(FirstOrderRun &r)
+{
+    cfmm_ctx *ctx = r.ctx;
+    const FirstOrderPlan &p = r.plan;
+    const cfmm_opts &o = r.o;
+    IterArgs &ia = r.ia;
+    const int n = ctx->n;
     // (sealed: the one thing of the previous solve that a launch in flight could still write is not this record -- the launch that
     //  stores it ran in front of the seal the host has seen)
-    if (zero_copy) { ia.h_nu_acc = ctx->hsol_d; ia.h_psi_acc = ctx->hsol_d + n; ia.h_final = ctx->hst_d; ctx->hst[0] = DevState{}; }
-
-    // ---- timed region: the outer loop (upload and trade read-back excluded) ----------------
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!sealed) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
-        *ctx->hstat_h = 0;                                 // (the stream is idle: nothing can still write the progress word)
-    }
-    if (ctx->det) HIP_TRY(ctx, hipMemsetAsync(ctx->acc_l, 0, 6 * (size_t)n * sizeof(unsigned long long), ctx->stream));
-    if (fused) {
-        // launch 0: the start point and the first evaluation (with the diagonal metric) into state / accumulator set 0
-        // (the start kernel also clears the three accumulator sets and the two spare state records, and reads the start
-        //  prices where they are: three fill / copy operations less on the stream per solve)
-        double *x0 = ctx->xs3;
-        ua.s = x0; ua.s_t = x0 + ia.xvs; ua.Gs = x0 + 2 * ia.xvs; ua.d = x0 + 3 * ia.xvs; ua.nu = x0 + 4 * ia.xvs; ua.st = ctx->st3;
-        hipLaunchKernelGGL(start_kernel<false>, dim3(1), dim3(UPD_THREADS), upd_lds_bytes(ctx->ng), ctx->stream, ua, nu_src,
-                           ctx->acc3, (long long)(3 * aset), ctx->st3 + 1, 2, sealed ? (long long *)&ctx->env_d->t0 : (long long *)nullptr);
-        for (int stable = 0; stable < 2; ++stable) {
-            EvalArgs e0 = make_eval_args(ctx, stable != 0);
-            e0.nu = ua.nu; e0.acc = ctx->acc3;
-            if (stable) launch_eval<true, true>(ctx, e0); else launch_eval<true, false>(ctx, e0);
-        }
-        if (table_pools(ctx) > 0) launch_table_evals<true>(ctx, ua.nu, ctx->acc3);
-        if (ctx->det) { int rc = det_finish(ctx, ctx->acc3, ua.nu, true); if (rc) return rc; }
-        else if (shard && rccl_unfolded(ctx)) {       // (every slice whole, metric included: launch 1 sums them itself)
-            int rc = all_reduce(ctx, ctx->acc3, (size_t)ctx->nslices * acc_stride(n), NCCL_FLOAT64, NCCL_SUM); if (rc) return rc;
-        } else if (shard) {
-            const int len = acc_stride(n);
-            hipLaunchKernelGGL(fold_kernel, dim3((len + 255) / 256), dim3(256), 0, ctx->stream, ctx->acc3, n, ctx->nslices, 1, (const DevState *)nullptr);
-            int rc = all_reduce(ctx, ctx->acc3, (size_t)len, NCCL_FLOAT64, NCCL_SUM); if (rc) return rc;
-        }
-    } else if (tiny) {
-        // one workgroup, one launch: every evaluation and update of the solve, nothing of it in global memory (tiny.hpp);
-        // the device ends it: converged, stalled, or out of budget
-        hipLaunchKernelGGL(start_kernel<false>, dim3(1), dim3(UPD_THREADS), upd_lds_bytes(ctx->ng), ctx->stream, ua, nu_src,
-                           ctx->acc, (long long)((size_t)ctx->nslices * acc_stride(n)), (DevState *)nullptr, 0);
-        const int threads = 64 * std::min(TINY_THREADS / 64, std::max(1, ea_tiny.ntiles));
-        hipLaunchKernelGGL(solve_tiny_kernel<false>, dim3(1), dim3(threads), (size_t)tiny_lds_doubles(n) * sizeof(double), ctx->stream, ea_tiny, ua, o.max_evals + 1);
+    auto mirror_result = [&] { ia.h_nu_acc = ctx->hsol_d; ia.h_psi_acc = ctx->hsol_d + n; ia.h_final = ctx->hst_d; ctx->hst[0] = DevState{}; };
+    long long *t0_stamp = nullptr;
+    if (p.sealed) {
+        if (++ctx->epoch == 0) ++ctx->epoch;
+        r.epoch = ctx->epoch;
+        ia.env = ctx->env_d; ia.epoch = r.epoch; ia.hstat = nullptr;
+        mirror_result();
+        r.t0 = std::chrono::steady_clock::now();
+        t0_stamp = (long long *)&ctx->env_d->t0;
+        // from the first launch until read_result has seen the seal, launches are in flight that no stream synchronisation has
+        // waited for: every return in between -- the error returns below -- leaves the context saying so (cfmm_ctx::tail)
+        ctx->tail = true;
     } else {
-        hipLaunchKernelGGL(start_kernel<false>, dim3(1), dim3(UPD_THREADS), upd_lds_bytes(ctx->ng), ctx->stream, ua, nu_src,
-                           ctx->acc, (long long)((size_t)ctx->nslices * acc_stride(n)), (DevState *)nullptr, 0);
-        { int rc = enqueue_iteration<true>(ctx, ua); if (rc) return rc; }      // first evaluation also builds the metric
+        { int rc = enter_drained(ctx); if (rc) return rc; }
+        if (p.zero_copy) mirror_result();
+        { int rc = open_timed(r); if (rc) return rc; }
+    }
+    { int rc = launch_start(r, FirstEval::Fused, t0_stamp); if (rc) return rc; }
+    HIP_TRY(ctx, hipGetLastError());
+    SpinWatch watch;
+    int t = 1;
+    Progress at;
+    for (;;) {
+        at = read_progress(ctx, p.sealed, r.epoch);
+        if (at.status != 0) break;
+        if (t > o.max_evals + 1) {                         // every evaluation the budget allows is enqueued: the device ends it (status 3)
+            if (!p.sealed) {
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                break;
+            }                                              // (sealed: the last of them reports the end like any other)
+        } else
+        if (t - at.done <= ctx->run_ahead) {
+            int rc = enqueue_fused_iteration(ctx, ia, t); if (rc) return rc;
+            ++t; watch.progress();
+            continue;
+        }
+        if (watch.expired()) return SpinWatch::stalled(ctx, "solve", t, at.done);
     }
     HIP_TRY(ctx, hipGetLastError());
-    const int max_chunks = (o.max_evals + o.iters_per_graph - 1) / o.iters_per_graph + 1;
-    // the state lives in ONE DevState (two-launch iteration) or in three rotating ones, of which the newest counts
-    auto newest = [&](const DevState *h) -> const DevState & {
-        int b = 0;
-        if (fused) for (int q = 1; q < 3; ++q) if (h[q].evals > h[b].evals) b = q;      // (every update counts one evaluation)
-        return h[b];
-    };
-    const int nst = fused ? 3 : 1;
-    DevState *hring = fused ? ctx->hst3 : ctx->hst;
-    const DevState *dst = fused ? ctx->st3 : ctx->st;
-    int status = 0, t = 1;
-    if (tiny) {
-        // (nothing to enqueue: the read-back below waits for the one launch)
-    } else if (fused && (!shard || oneshot_runahead(ctx)) && !use_graph_opt) {
-        // Single GPU (or pool-sharded through the one-shot exchange), one launch per iteration: launches are enqueued eagerly, a few ahead of the device, whose workgroup 0
-        // reports {evals, status} into a pinned host word as it goes (zero-copy: the host polls memory, no API call, no
-        // copy engine).  No graph-replay gaps (~19 us per replay), and only `run_ahead` idle launches behind the end.
-        const auto spin0 = std::chrono::steady_clock::now();
-        long spins = 0;
-        int done = 0;
-        for (;;) {
-            if (sealed) {                                  // (a word of another epoch is an earlier solve's: nothing reported yet)
-                const unsigned long long w = ctx->env_h->prog;
-                const bool cur = (unsigned)(w >> 32) == epoch;
-                done = cur ? (int)(w & 0xffffffu) : 0;
-                status = cur ? (int)((w >> 24) & 0xffu) : 0;
-            } else {
-                const unsigned long long w = *ctx->hstat_h;
-                done = (int)(w & 0xffffffffu);
-                status = (int)(w >> 32);
-            }
-            if (status != 0) break;
-            if (t > o.max_evals + 1) {                     // every evaluation the budget allows is enqueued: the device ends it (status 3)
-                if (!sealed) {
-                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                    break;
-                }                                          // (sealed: the last of them reports the end like any other)
-            } else
-            if (t - done <= ctx->run_ahead) {
-                int rc = enqueue_fused_iteration(ctx, ia, t); if (rc) return rc;
-                ++t; spins = 0;
-                continue;
-            }
-            if ((++spins & 0xfffff) == 0) {                // (a dead device must not hang the host for ever)
-                if (hipGetLastError() != hipSuccess || std::chrono::duration<double>(std::chrono::steady_clock::now() - spin0).count() > 120.0)
-                    return fail(ctx, CFMM_E_HIP, "solve: the device stopped reporting progress (launch %d, %d done)", t, done);
-            }
-        }
+    // sealed: the launch that ended the solve is launch `done` (every update counts one evaluation); the result it and two other
+    // workgroups stored counts as complete once a launch BEHIND it says so -- if the host had not run that far ahead, one more goes
+    // out to say it
+    if (p.sealed && t < at.done + 2) { int rc = enqueue_fused_iteration(ctx, ia, t); if (rc) return rc; ++t; HIP_TRY(ctx, hipGetLastError()); }
+    return CFMM_OK;
+}
+
+// Pool-sharded through RCCL, one launch per iteration: chunks of `iters_per_graph` launches (each with its collective) enqueued
+// eagerly, the decision to go on taken one chunk behind -- on the progress slot of the LAST launch of the previous chunk, which that
+// launch writes into pinned memory itself (iterate.hpp: IterArgs::hring): the same word on every rank whatever the pace of its
+// device, so all ranks enqueue the same collectives.  Rounds 2-5 copied the state records back and waited on an event per chunk:
+// a blit dispatch on the stream every chunk (~0.9 us per iteration at one rank) and two API calls.
+static int drive_ring_chunks(FirstOrderRun &r)
+{
+    cfmm_ctx *ctx = r.ctx;
+    const cfmm_opts &o = r.o;
+    { int rc = begin_synchronised(r); if (rc) return rc; }
+    { int rc = launch_start(r, FirstEval::Fused, nullptr); if (rc) return rc; }
+    HIP_TRY(ctx, hipGetLastError());
+    volatile unsigned long long *ring = ctx->hstat_h + 8;
+    for (int q = 0; q < ITER_HRING; ++q) ring[q] = 0;      // (the stream is idle)
+    r.ia.hring = ctx->hstat_d + 8;
+    SpinWatch watch;
+    int t = 1;
+    for (int cidx = 0, chunks = max_chunks(o); cidx < chunks; ++cidx) {
+        for (int it = 0; it < o.iters_per_graph; ++it) { int rc = enqueue_fused_iteration(ctx, r.ia, t + it); if (rc) return rc; }
         HIP_TRY(ctx, hipGetLastError());
-        // sealed: the launch that ended the solve is launch `done` (every update counts one evaluation); the result it and two other
-        // workgroups stored counts as complete once a launch BEHIND it says so -- if the host had not run that far ahead, one more goes
-        // out to say it
-        if (sealed && t < done + 2) { int rc = enqueue_fused_iteration(ctx, ia, t); if (rc) return rc; ++t; HIP_TRY(ctx, hipGetLastError()); }
-    } else if (fused && shard && !use_graph) {
-        // Pool-sharded through RCCL, one launch per iteration: chunks of `iters_per_graph` launches (each with its collective) enqueued
-        // eagerly, the decision to go on taken one chunk behind -- on the progress slot of the LAST launch of the previous chunk, which that
-        // launch writes into pinned memory itself (iterate.hpp: IterArgs::hring): the same word on every rank whatever the pace of its
-        // device, so all ranks enqueue the same collectives.  Rounds 2-5 copied the state records back and waited on an event per chunk:
-        // a blit dispatch on the stream every chunk (~0.9 us per iteration at one rank) and two API calls.
-        volatile unsigned long long *ring = ctx->hstat_h + 8;
-        for (int q = 0; q < ITER_HRING; ++q) ring[q] = 0;      // (the stream is idle)
-        ia.hring = ctx->hstat_d + 8;
-        const auto spin0 = std::chrono::steady_clock::now();
-        for (int cidx = 0; cidx < max_chunks; ++cidx) {
-            for (int it = 0; it < o.iters_per_graph; ++it) { int rc = enqueue_fused_iteration(ctx, ia, t + it); if (rc) return rc; }
-            HIP_TRY(ctx, hipGetLastError());
-            t += o.iters_per_graph;
-            if (cidx >= 1) {
-                const int last = t - o.iters_per_graph - 1;    // the last launch of the previous chunk
-                unsigned long long w;
-                long spins = 0;
-                while ((int)((w = ring[last & (ITER_HRING - 1)]) >> 32) != last) {
-                    if ((++spins & 0xfffff) == 0 && (hipGetLastError() != hipSuccess || std::chrono::duration<double>(std::chrono::steady_clock::now() - spin0).count() > 120.0))
-                        return fail(ctx, CFMM_E_HIP, "solve: the device stopped reporting progress (launch %d)", last);
-                }
-                status = (int)((w >> 24) & 0xffu);
-                if (status != 0) break;
-            }
+        t += o.iters_per_graph;
+        if (cidx >= 1) {
+            const int last = t - o.iters_per_graph - 1;    // the last launch of the previous chunk
+            unsigned long long w;
+            watch.progress();
+            while ((int)((w = ring[last & (ITER_HRING - 1)]) >> 32) != last)
+                if (watch.expired()) return SpinWatch::stalled(ctx, "solve", t, last - 1);
+            if ((int)((w >> 24) & 0xffu) != 0) break;
         }
-    } else
-    for (int cidx = 0; cidx < max_chunks; ++cidx) {
-        if (use_graph) {
+    }
+    return CFMM_OK;
+}
+
+// Chunks of `iters_per_graph` iterations -- replayed from the captured graph or enqueued eagerly, the one-launch iteration or the
+// two-launch one (evaluation kernel, single-workgroup update kernel) -- with a copy of the state records and an event behind each.
+static int drive_chunks(FirstOrderRun &r)
+{
+    cfmm_ctx *ctx = r.ctx;
+    const FirstOrderPlan &p = r.plan;
+    const cfmm_opts &o = r.o;
+    { int rc = begin_synchronised(r); if (rc) return rc; }
+    { int rc = launch_start(r, p.fused ? FirstEval::Fused : FirstEval::TwoLaunch, nullptr); if (rc) return rc; }      // (the first evaluation also builds the metric)
+    HIP_TRY(ctx, hipGetLastError());
+    const StateRecords rec = state_records(ctx, p.fused);
+    int t = 1;
+    for (int cidx = 0, chunks = max_chunks(o); cidx < chunks; ++cidx) {
+        if (p.use_graph) {
             HIP_TRY(ctx, hipGraphLaunch(ctx->gexec, ctx->stream));
         } else {
             for (int it = 0; it < o.iters_per_graph; ++it) {
-                int rc = fused ? enqueue_fused_iteration(ctx, ia, t + it) : enqueue_iteration<false>(ctx, ua);
+                int rc = p.fused ? enqueue_fused_iteration(ctx, r.ia, t + it) : enqueue_iteration<false>(ctx, r.ua);
                 if (rc) return rc;
             }
             HIP_TRY(ctx, hipGetLastError());
         }
         t += o.iters_per_graph;
-        HIP_TRY(ctx, hipMemcpyAsync(hring + (cidx & 1) * nst, dst, nst * sizeof(DevState), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(rec.host + (cidx & 1) * rec.count, rec.dev, rec.count * sizeof(DevState), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipEventRecord(ctx->ev[cidx & 1], ctx->stream));
         if (cidx >= 1) {                       // poll one chunk behind: the device never idles
             HIP_TRY(ctx, hipEventSynchronize(ctx->ev[(cidx - 1) & 1]));
-            status = newest(hring + ((cidx - 1) & 1) * nst).status;
-            if (status != 0) break;
+            if (newest_state(rec.host + ((cidx - 1) & 1) * rec.count, rec.count).status != 0) break;
         }
     }
-    if (!sealed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
-    if (zero_copy) {
-        // the kernels have left the result in pinned memory themselves (iterate.hpp: h_nu_acc / h_psi_acc / h_final)
-        bool drained = !sealed;
-        if (sealed) {
+    return CFMM_OK;
+}
+
+// What the driver's launches left: the final state record, the prices and the net trade in hsol, the point published, and the times of
+// the region opened at r.t0.  The kernels of a zero-copy solve have stored all of it in pinned memory themselves (iterate.hpp:
+// h_nu_acc / h_psi_acc / h_final) -- complete once the stream has drained or, sealed, once this solve's seal is seen; the others copy.
+static int read_result(FirstOrderRun &r, DevState &st, double &wall_s, double &dev_s)
+{
+    cfmm_ctx *ctx = r.ctx;
+    const FirstOrderPlan &p = r.plan;
+    const int n = ctx->n;
+    const StateRecords rec = state_records(ctx, p.fused);
+    if (!p.sealed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
+    if (p.zero_copy) {
+        bool drained = !p.sealed;
+        if (p.sealed) {
             // wait for the seal of THIS solve; a device that does not deliver it (an error, 120 s) is asked the old way
-            const auto spin0 = std::chrono::steady_clock::now();
-            long spins = 0;
-            while ((unsigned)(ctx->env_h->seal >> 32) != epoch) {
-                if ((++spins & 0xfffff) == 0 && (hipGetLastError() != hipSuccess || std::chrono::duration<double>(std::chrono::steady_clock::now() - spin0).count() > 120.0)) { drained = true; break; }
-            }
+            SpinWatch watch;
+            while ((unsigned)(ctx->env_h->seal >> 32) != r.epoch)
+                if (watch.expired()) { drained = true; break; }
             std::atomic_thread_fence(std::memory_order_acquire);
             ctx->tail = !drained;                          // (launches behind the sealing one may still be in flight: cfmm_ctx::tail)
         }
         if (drained) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        hring[0] = ctx->hst[0];
-        for (int q = 1; q < nst; ++q) hring[q] = DevState{};
-        if (hring[0].status == 0) {              // (the device ended without a final record: cannot happen -- read it the slow way)
+        rec.host[0] = ctx->hst[0];
+        for (int q = 1; q < rec.count; ++q) rec.host[q] = DevState{};
+        if (rec.host[0].status == 0) {           // (the device ended without a final record: cannot happen -- read it the slow way)
             { int rc = settle(ctx); if (rc) return rc; }
-            HIP_TRY(ctx, hipMemcpy(hring, dst, nst * sizeof(DevState), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(rec.host, rec.dev, rec.count * sizeof(DevState), hipMemcpyDeviceToHost));
             HIP_TRY(ctx, hipMemcpy(ctx->hsol, ctx->nu_acc, n * sizeof(double), hipMemcpyDeviceToHost));
             HIP_TRY(ctx, hipMemcpy(ctx->hsol + n, ctx->psi_acc, n * sizeof(double), hipMemcpyDeviceToHost));
         }
     } else {
-    HIP_TRY(ctx, hipMemcpyAsync(hring, dst, nst * sizeof(DevState), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->hsol, ctx->nu_acc, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->hsol + n, ctx->psi_acc, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(rec.host, rec.dev, rec.count * sizeof(DevState), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->hsol, ctx->nu_acc, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->hsol + n, ctx->psi_acc, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     point_published(ctx, 0.0, false);
-    { double mx = 0.0; for (int j = 0; j < n; ++j) mx = std::max(mx, ctx->hsol[j]); if (mx > 0.0 && std::isfinite(mx)) ctx->nu_max = mx; }
-    const auto t1 = std::chrono::steady_clock::now();
-    float ms = 0.f;
-    double dev_s = 0.0;
-    if (sealed) {                                          // start of the first launch .. start of the launch that found the solve ended
+    refresh_nu_max(ctx);
+    wall_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - r.t0).count();
+    dev_s = 0.0;
+    if (p.sealed) {                                        // start of the first launch .. start of the launch that found the solve ended
         const long long c0 = ctx->env_h->t0, c1 = ctx->env_h->t1;
         if (c1 > c0) dev_s = (double)(c1 - c0) / ctx->wall_clock_hz;
     } else {
+        float ms = 0.f;
         HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1));
         dev_s = ms * 1e-3;
     }
+    st = newest_state(rec.host, rec.count);
+    return CFMM_OK;
+}
 
-    const DevState st = newest(hring);
-    std::memset(out, 0, sizeof *out);
-    out->evals = st.evals; out->iters = st.iters; out->status = st.status ? st.status : 3;
-    out->n_ranks = ctx->n_ranks;
-    out->dual_value = st.f; out->primal_value = st.primal; out->gap = st.gap; out->infeas = st.infeas;
-    out->wall_seconds = std::chrono::duration<double>(t1 - t0).count();
-    out->device_seconds = dev_s;
-    out->pg = st.pg;
-    out->pool_subproblems = (int64_t)st.evals * cfmm_pool_count(ctx);
-    out->method = CFMM_METHOD_LBFGS;
-    if (!std::isfinite(st.f)) { out->status = CFMM_E_NUMERIC; return fail(ctx, CFMM_E_NUMERIC, "solve: dual value is not finite"); }
+static int solve_lbfgs(cfmm_ctx *ctx, const cfmm_opts &o_in, cfmm_stats *out)
+{
+    drop_barrier(ctx);
+    const EvalArgs ea_tiny = make_eval_args(ctx, false, 0x7fffffff, false);
+    FirstOrderRun r;
+    r.ctx = ctx;
+    r.o = o_in;
+    r.plan = plan_first_order(plan_facts(ctx, ea_tiny, o_in));
+    r.o.iters_per_graph = r.plan.iters_per_graph;
+    if (r.plan.use_graph && (!ctx->g_valid || !same_opts(r.o, ctx->g_opts))) { int rc = build_graph(ctx, r.o); if (rc) return rc; }
+    r.ua = make_upd_args(ctx, r.o);
+    r.ia = make_iter_args(ctx, r.o);
+    r.nu_src = ctx->nu0_deferred ? ctx->hnu0_d : ctx->nu_acc;
+    ctx->nu0_deferred = false;                             // (the start kernel writes nu_acc)
+    int rc = CFMM_OK;
+    switch (r.plan.drive) {
+    case Drive::Tiny: rc = drive_tiny(r, ea_tiny); break;
+    case Drive::Eager: rc = drive_eager(r); break;
+    case Drive::RingChunks: rc = drive_ring_chunks(r); break;
+    case Drive::Chunks: rc = drive_chunks(r); break;
+    }
+    if (rc) return rc;
+    DevState st;
+    double wall_s, dev_s;
+    rc = read_result(r, st, wall_s, dev_s);
+    if (rc) return rc;
+    if (!stats_from_state(st, ctx->n_ranks, cfmm_pool_count(ctx), wall_s, dev_s, out)) return fail(ctx, CFMM_E_NUMERIC, "solve: dual value is not finite");
     return CFMM_OK;
 }
 
@@ -4021,8 +4154,7 @@ int cfmm_solve_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu0, co
     HIP_TRY(c0, hipGetLastError());
     int t = 1;
     {
-        const auto spin0 = std::chrono::steady_clock::now();
-        long spins = 0;
+        SpinWatch watch;
         for (;;) {
             int done = 0, running = 0;
             for (int b = 0; b < nb; ++b) {
@@ -4035,13 +4167,10 @@ int cfmm_solve_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu0, co
             if (t - done <= c0->run_ahead) {
                 launch_batch_eval(c0, be, stream, t);
                 launch_update_batch();
-                ++t; spins = 0;
+                ++t; watch.progress();
                 continue;
             }
-            if ((++spins & 0xfffff) == 0) {
-                if (hipGetLastError() != hipSuccess || std::chrono::duration<double>(std::chrono::steady_clock::now() - spin0).count() > 120.0)
-                    return fail(c0, CFMM_E_HIP, "solve_batch: the device stopped reporting progress (launch %d, %d done)", t, done);
-            }
+            if (watch.expired()) return SpinWatch::stalled(c0, "solve_batch", t, done);
         }
         HIP_TRY(c0, hipGetLastError());
     }
@@ -4060,19 +4189,10 @@ int cfmm_solve_batch(cfmm_ctx *const *ctxs, int nb, const double *const *nu0, co
     for (int b = 0; b < nb; ++b) {
         cfmm_ctx *c = ctxs[b];
         point_published(c, 0.0, false);
-        { double mx = 0.0; for (int j = 0; j < n; ++j) mx = std::max(mx, c->hsol[j]); if (mx > 0.0 && std::isfinite(mx)) c->nu_max = mx; }
-        const DevState st = c->hst[0];
-        cfmm_stats *s = out + b;
-        std::memset(s, 0, sizeof *s);
-        s->evals = st.evals; s->iters = st.iters; s->status = st.status ? st.status : 3;
-        s->n_ranks = 1;
-        s->dual_value = st.f; s->primal_value = st.primal; s->gap = st.gap; s->infeas = st.infeas;
-        s->wall_seconds = std::chrono::duration<double>(t1 - t0).count();      // (of the whole batch)
-        s->device_seconds = ms * 1e-3;
-        s->pg = st.pg;
-        s->pool_subproblems = (int64_t)st.evals * cfmm_pool_count(c0);
-        s->method = CFMM_METHOD_LBFGS;
-        if (!std::isfinite(st.f)) { s->status = CFMM_E_NUMERIC; rc_all = fail(c0, CFMM_E_NUMERIC, "solve_batch: dual value of solve %d is not finite", b); }
+        refresh_nu_max(c);
+        // (the times: of the whole batch)
+        if (!stats_from_state(c->hst[0], 1, cfmm_pool_count(c0), std::chrono::duration<double>(t1 - t0).count(), ms * 1e-3, out + b))
+            rc_all = fail(c0, CFMM_E_NUMERIC, "solve_batch: dual value of solve %d is not finite", b);
     }
     return rc_all;
 }

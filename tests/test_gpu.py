@@ -768,9 +768,12 @@ def test_virtual_shards_on_the_gpu_sum_to_the_unsharded_evaluation():
         assert np.abs(ps - psi).max() <= 1e-10 * np.abs(psi).max()
 
 
-def test_eager_iteration_path_matches_graph_path(tmp_path):
+@pytest.mark.parametrize("fused", [None, "0"], ids=["default", "two_launch"])
+def test_eager_iteration_path_matches_graph_path(tmp_path, fused):
     """the pool-sharded build enqueues its iterations eagerly (RCCL between the kernels) instead of
-    replaying a captured graph; CFMM_NO_GRAPH=1 drives the same control flow on one GPU"""
+    replaying a captured graph; CFMM_NO_GRAPH=1 drives the same control flow on one GPU.
+    (On this network the one-launch iteration applies, which is enqueued eagerly whatever CFMM_NO_GRAPH says: `two_launch` sets
+    CFMM_FUSED=0 on both sides, so that the chunk driver replays the graph on one and enqueues on the other.)"""
     import subprocess, sys, json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = ("import sys, json; sys.path[:0] = [%r, %r]; import cfmm; from cfmm import synthetic; "
@@ -779,7 +782,8 @@ def test_eager_iteration_path_matches_graph_path(tmp_path):
             % (root, os.path.join(root, "cfmm-routing-code_amd")))
     out = {}
     for mode in ("0", "1"):
-        r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, CFMM_NO_GRAPH=mode), capture_output=True, text=True, timeout=300)
+        r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, CFMM_NO_GRAPH=mode, **({} if fused is None else {"CFMM_FUSED": fused})),
+                           capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         out[mode] = json.loads(r.stdout.strip().splitlines()[-1])
     assert out["0"]["status"] == out["1"]["status"] == "optimal"

@@ -479,6 +479,81 @@ int main()
     assert abs(rows[-1][2] - lp) <= 1e-8
 
 
+def test_first_order_plan_over_every_combination_of_its_facts(tmp_path):
+    """csrc/solve_plan.hpp: plan_first_order -- which host driver runs a first-order solve, and under which envelope -- is a pure host
+    function of eleven booleans and three integers: compiled for the HOST here and run over every combination of the booleans, crossed
+    with one and two ranks, four chunk lengths and the evaluation budgets around the 24 bits the sealed envelope's words carry.  Every
+    line against the rules restated below (from the design, not from the header)."""
+    import itertools
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc missing")
+    bools = ["tiny_applies", "fused_applies", "sharded", "oneshot_runahead", "multi_graph", "os_ready", "no_graph", "det",
+             "fused_graph", "zero_copy_off", "envelope_classic"]
+    ranks, chunk, budget = (1, 2), (1, 3, 4, 256), (1, 0xfffffe, 0xffffff)
+    src = tmp_path / "plan.cpp"
+    src.write_text(r'''
+#include "solve_plan.hpp"
+#include <cstdio>
+int main()
+{
+    const int ranks[] = {%s}, chunk[] = {%s}, budget[] = {%s};
+    for (unsigned m = 0; m < (1u << %d); ++m)
+        for (int nr : ranks) for (int ipg : chunk) for (int me : budget) {
+            PlanFacts f;
+%s
+            f.n_ranks = nr; f.iters_per_graph = ipg; f.max_evals = me;
+            const FirstOrderPlan p = plan_first_order(f);
+            const char *d = p.drive == Drive::Tiny ? "Tiny" : p.drive == Drive::Eager ? "Eager" : p.drive == Drive::RingChunks ? "RingChunks" : "Chunks";
+            printf("%%u %%d %%d %%d %%s %%d %%d %%d %%d %%d\n", m, nr, ipg, me, d, (int)p.fused, (int)p.use_graph, (int)p.zero_copy, (int)p.sealed, p.iters_per_graph);
+        }
+    return 0;
+}
+''' % (", ".join(map(str, ranks)), ", ".join(map(str, chunk)), ", ".join(map(str, budget)), len(bools),
+       "\n".join(f"            f.{b} = (m >> {i}) & 1u;" for i, b in enumerate(bools))))
+    exe = tmp_path / "plan"
+    r = subprocess.run([hipcc, "-O1", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "cfmm-routing-code_amd", "csrc"), str(src), "-o", str(exe)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    got = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60).stdout.strip().splitlines()
+
+    def plan(f):
+        tiny = f["tiny_applies"]
+        fused = not tiny and f["fused_applies"]
+        ipg = f["iters_per_graph"]
+        if fused:
+            ipg = -(-ipg // 3) * 3
+        if f["sharded"] and f["n_ranks"] > 1 and not f["oneshot_runahead"] and not f["multi_graph"]:
+            ipg = 3
+        graph_opt = fused and not f["sharded"] and f["fused_graph"]
+        use_graph = (not tiny and (not f["sharded"] or (f["multi_graph"] and not f["os_ready"])) and not f["no_graph"]
+                     and (not fused or f["sharded"] or f["fused_graph"]))
+        zero_copy = fused and not f["sharded"] and not graph_opt and not f["det"] and not f["zero_copy_off"]
+        sealed = zero_copy and not f["envelope_classic"] and f["max_evals"] < 0xffffff
+        if tiny:
+            drive = "Tiny"
+        elif fused and (not f["sharded"] or f["oneshot_runahead"]) and not graph_opt:
+            drive = "Eager"
+        elif fused and f["sharded"] and not use_graph:
+            drive = "RingChunks"
+        else:
+            drive = "Chunks"
+        return drive, int(fused), int(use_graph), int(zero_copy), int(sealed), ipg
+
+    want = []
+    for m in range(1 << len(bools)):
+        for nr, ipg, me in itertools.product(ranks, chunk, budget):
+            f = {b: bool((m >> i) & 1) for i, b in enumerate(bools)}
+            f.update(n_ranks=nr, iters_per_graph=ipg, max_evals=me)
+            want.append("%d %d %d %d %s %d %d %d %d %d" % ((m, nr, ipg, me) + plan(f)))
+    assert len(got) == len(want) == (1 << len(bools)) * len(ranks) * len(chunk) * len(budget)
+    bad = [(g, w) for g, w in zip(got, want) if g != w]
+    assert not bad, (len(bad), bad[:5])
+    assert {l.split()[4] for l in got} == {"Tiny", "Eager", "RingChunks", "Chunks"}
+
+
 def test_switch_records_of_a_k_asset_constant_sum_pool_are_rooted_at_the_paying_leg():
     """cfmm/problem.py: _canonical_switches, _split_payers (round 6, pure functions of the records: every rank of a pool-sharded solve
     computes the same).  Three tokens tied for cheapest, found pair by pair in rounds whose cheapest token differed -- records (0, 3) and
