@@ -41,6 +41,7 @@
 #include "update.hpp"
 #include "handoff.hpp"
 #include "solve_plan.hpp"
+#include "newton_rules.hpp"
 
 using namespace cfmm;
 
@@ -1561,6 +1562,39 @@ int wait_io(cfmm_ctx *ctx)
     return fail(ctx, CFMM_E_HIP, "hand-off: the stream drained without the kernel's flag (%llu, expected %llu)", (unsigned long long)*f, want);
 }
 
+// A list of small transfers between the pinned staging and the device that runs either way (CFMM_NEWTON_IO).  lean: ONE launch_io of
+// the list, + wait_io behind a publishing one.  blit: the same bytes as hipMemcpyAsync / hipMemsetAsync calls in list order, + a stream
+// synchronisation where lean publishes.  `pinned`: HOST pointers into the pinned staging.
+struct HandOff {
+    enum Kind { Down, Up, Zero, ZeroLeanOnly };
+    struct Job { Kind kind; void *dst; const void *src; size_t bytes; };
+    cfmm_ctx *ctx;
+    Job j[IO_MAX_JOBS];
+    int nj = 0;
+    explicit HandOff(cfmm_ctx *c) : ctx(c) {}
+    void down(void *dev, const void *pinned, size_t bytes) { j[nj++] = Job{Down, dev, pinned, bytes}; }
+    void up(void *pinned, const void *dev, size_t bytes) { j[nj++] = Job{Up, pinned, dev, bytes}; }
+    void zero(void *dev, size_t bytes) { j[nj++] = Job{Zero, dev, nullptr, bytes}; }
+    void zero_lean_only(void *dev, size_t bytes) { j[nj++] = Job{ZeroLeanOnly, dev, nullptr, bytes}; }      // (blit: the launch behind it zeroes its own buffers)
+    int run(bool publish)
+    {
+        if (ctx->lean_io) {
+            IoList l;
+            for (int i = 0; i < nj; ++i)
+                l.copy(j[i].kind == Up ? pin_device(ctx, j[i].dst) : j[i].dst, j[i].kind == Down ? pin_device(ctx, const_cast<void *>(j[i].src)) : j[i].src, j[i].bytes);
+            const int rc = launch_io(ctx, l, publish);
+            return rc || !publish ? rc : wait_io(ctx);
+        }
+        for (int i = 0; i < nj; ++i) {
+            if (j[i].kind == Down) HIP_TRY(ctx, hipMemcpyAsync(j[i].dst, j[i].src, j[i].bytes, hipMemcpyHostToDevice, ctx->stream));
+            if (j[i].kind == Up) HIP_TRY(ctx, hipMemcpyAsync(j[i].dst, j[i].src, j[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+            if (j[i].kind == Zero) HIP_TRY(ctx, hipMemsetAsync(j[i].dst, 0, j[i].bytes, ctx->stream));
+        }
+        if (publish) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return CFMM_OK;
+    }
+};
+
 int smooth_buffers(cfmm_ctx *ctx, bool hess)
 {
     const int n = ctx->n;
@@ -1714,67 +1748,105 @@ int smooth_eval_host(cfmm_ctx *ctx, const std::vector<double> &nu, double mu, bo
     double *pin_nu = pin, *pin_slo = pin + n, *pin_out = pin + 2 * n;             // [n] | [n] | [n + 2]
     std::memcpy(pin_nu, nu.data(), n * sizeof(double));
     if (slo) std::memcpy(pin_slo, slo->data(), n * sizeof(double));
-    if (ctx->lean_io) {
-        // one launch: prices (and low-order part) down, output and Hessian zeroed; the evaluation; one launch: output up + flag
-        IoList l;
-        l.copy(ctx->nu, pin_device(ctx, pin_nu), n * sizeof(double));
-        if (slo) l.copy(ctx->sm_slo, pin_device(ctx, pin_slo), n * sizeof(double));
-        l.zero(ctx->sm_out, (size_t)(n + 2) * sizeof(double));
-        if (hess && !ctx->h_clean) l.zero(ctx->H, (size_t)hess_ld(n) * hess_nr(n) * sizeof(double));
-        if (hess) ctx->h_clean = false;
-        if ((rc = launch_io(ctx, l, false))) return rc;
-        if ((rc = launch_smooth(ctx, mu, hess, warm, slo != nullptr, true))) return rc;
-        IoList p;
-        p.copy(pin_device(ctx, pin_out), ctx->sm_out, (size_t)(n + 2) * sizeof(double));
-        if ((rc = launch_io(ctx, p, true))) return rc;
-        if ((rc = wait_io(ctx))) return rc;
-    } else {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->nu, pin_nu, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        if (slo) HIP_TRY(ctx, hipMemcpyAsync(ctx->sm_slo, pin_slo, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = launch_smooth(ctx, mu, hess, warm, slo != nullptr))) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(pin_out, ctx->sm_out, (size_t)(n + 2) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    // one launch: prices (and low-order part) down, output and Hessian zeroed; the evaluation; one launch: output up + flag
+    HandOff in(ctx), back(ctx);
+    in.down(ctx->nu, pin_nu, n * sizeof(double));
+    if (slo) in.down(ctx->sm_slo, pin_slo, n * sizeof(double));
+    in.zero_lean_only(ctx->sm_out, (size_t)(n + 2) * sizeof(double));
+    if (hess && !ctx->h_clean) in.zero_lean_only(ctx->H, (size_t)hess_ld(n) * hess_nr(n) * sizeof(double));
+    if (hess) ctx->h_clean = false;
+    if ((rc = in.run(false))) return rc;
+    if ((rc = launch_smooth(ctx, mu, hess, warm, slo != nullptr, /*zeroed=*/ctx->lean_io))) return rc;
+    back.up(pin_out, ctx->sm_out, (size_t)(n + 2) * sizeof(double));
+    if ((rc = back.run(true))) return rc;
     e.psi.assign(pin_out, pin_out + n);
     e.value = pin_out[n]; e.trade = pin_out[n + 1];
     return CFMM_OK;
 }
 
-// the utility table's entries on the host (the second-order loop keeps the utility on the host): the numbers of
-// lbfgs::utility_term (lbfgs_rules.hpp), + nu^2 ubar''(nu) for the Hessian's diagonal in log-prices
-struct HostUtilityTerm { double pstar, ubar, uval, viol, d2; };
-static HostUtilityTerm host_utility_term(int ctype, double c, double h, double nu, double psi)
+// ---- the second-order (barrier path) solve ---------------------------------------------------------------------------------------
+// newton_rules.hpp holds its rules (host only); here are its state, its device traffic and the order of its phases: solve_newton.
+
+// how a phase of the loop ends: on to the next phase / this pass is over, the loop goes round / the loop is over (r.status says why)
+enum class Phase { Go, Again, Stop };
+
+struct NewtonRun {
+    cfmm_ctx *ctx;
+    const cfmm_opts &o;
+    const int n;
+    std::vector<double> s, nu, d, G, Hd, rhs, s2, nu2, psi_x;
+    std::vector<double> slo, slo2;              // low-order log-prices (smooth.hpp: apply_slo)
+    std::vector<double> lob, s_start;
+    std::vector<int> mask, pin;
+    std::vector<char> listed;
+    newton::Tokens tk;                          // the read-only view of the above that the rules take
+    SmoothEval e, e2;                           // at the point, at the line search's trial point
+    struct {
+        bool have_e = false;                    // the accepted line-search point was evaluated already (at this barrier weight) ...
+        bool e_has_h = false;                   // ... together with its Hessian
+    } cache;
+    struct {                                    // the factor the device holds (newton_rules.hpp: chord steps)
+        bool valid = false, chord_bad = false, last_full = false;
+        double mu = 0.0;                        // the barrier weight it was made at
+        int chord_run = 0;
+        double dec_prev = 0.0;                  // the decrement G' H^-1 G of the last accepted step
+        double move_prev = 0.0;                 // ... and its largest log-price move
+    } fac;
+    newton::Schedule sched;
+    bool slo_on = false;
+    struct Pass {                               // one pass of the loop, from its evaluation to its accepted step
+        bool use_chord = false, final_mu = false, slo2_on = false;
+        double gmu = 0.0, dec = 0.0, dmax = 0.0, t = 0.0, t_first = 0.0;
+        int info = 0;
+    } p;
+    const int evals_before;
+    int evals, steps = 0, chord_steps = 0, status = 0, max_newton = 200, chord_max = 3;
+    double arb_x = 0.0;                         // (psi_x, arb_x: the last exact evaluation)
+    double dual = 0.0, primal = 0.0, gap = 1.0, infeas = 1.0;
+    const char *numeric_where = "";
+    const bool trace = getenv("CFMM_NEWTON_TRACE") != nullptr;
+
+    NewtonRun(cfmm_ctx *c, const cfmm_opts &opts, int evals_so_far)
+        : ctx(c), o(opts), n(c->n), s(n), nu(n), d(n), G(n), Hd(n), rhs(n), s2(n), nu2(n), psi_x(n), slo(n, 0.0), slo2(n, 0.0), lob(n),
+          mask(n), pin(n), listed(n), evals_before(evals_so_far), evals(evals_so_far) {}
+    bool inverse_factor() const { return ctx->inverse_factor && ctx->Winv != nullptr; }
+    int numeric(const char *where) { status = CFMM_E_NUMERIC; numeric_where = where; return CFMM_OK; }
+};
+
+static int newton_exact(NewtonRun &r)         // the exact evaluation at r.nu
 {
-    HostUtilityTerm t;
-    if (ctype == CFMM_ULOG) {
-        t.pstar = c / nu - h; t.ubar = c * std::log(c / nu) - c + nu * h;
-        t.viol = std::max(-(psi + h), 0.0); t.uval = c * std::log(std::max(psi + h, 1e-300)); t.d2 = c;
-    } else {
-        t.pstar = h * (c - nu); t.ubar = 0.5 * h * (c - nu) * (c - nu);
-        t.viol = 0.0; t.uval = c * psi - 0.5 * psi * psi / h; t.d2 = h * nu * nu;
-    }
-    return t;
+    ++r.evals;
+    return cfmm_eval_dual(r.ctx, r.nu.data(), &r.arb_x, r.psi_x.data(), nullptr);
 }
 
-// warm_mu: the barrier weight to continue from (that of the previous solve, when cfmm_solve continues from it), or 0
-int solve_newton(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out, int evals_before, double warm_mu)
+// The certificates of the exact evaluation just made, at the START point (round 6).  Prices inside the utility's
+// box at which psi + h is feasible and complementary ARE the optimum -- the no-arbitrage network under a linear utility is the
+// case that matters: at nu = c nothing trades, psi = 0, value 0.  The barrier path has no business there: its smoothed pools trade
+// O(mu) each, the iteration chases rounding around a zero-valued optimum and explicit `CFMM_METHOD_NEWTON` runs ended "stalled" at
+// gaps up to 4.8e-2 (tools/fuzz_table.py seeds 12, 345, 609, 819, 945; fuzz_small.py seed 1434).  Linear-box utilities only.
+// ... and the same test at the prices a run ENDS on without its certificates (stalled / out of steps): with an optimum where nothing
+// trades but the prices had to move to get there (fuzz_small.py seeds 1387, 1434; fuzz_table.py 12, 345), the smoothed point keeps
+// trading O(mu) per pool -- a gap of 1e-5 against a value of zero -- while the EXACT evaluation at the very same prices is the optimum.
+static bool newton_certify_exact(NewtonRun &r, const char *where)
 {
-    const char *why = "";
-    if (!newton_supported(ctx, &why)) return fail(ctx, CFMM_E_UNSUPPORTED, "solve: the second-order method cannot take this problem: %s", why);
-    const int n = ctx->n;
-    int rc = settle(ctx); if (rc) return rc;             // (a first-order prelude may have left its tail in flight)
-    rc = smooth_buffers(ctx, true); if (rc) return rc;
-    const std::vector<double> &c = ctx->hc, &h = ctx->hh;
-    const std::vector<int> &ct = ctx->hctype;
+    const newton::ExactCertificate x = newton::exact_certificate(r.tk, r.nu.data(), r.psi_x.data(), r.arb_x, r.o.tol_gap, r.o.tol_infeas);
+    if (!x.holds) return false;
+    r.status = 1; r.gap = x.gap; r.infeas = x.infeas; r.primal = x.primal; r.dual = x.dual;
+    r.e.psi = r.psi_x; r.e.value = r.arb_x; r.e.trade = r.arb_x;
+    r.sched.mu = 0.0;                           // (an exact point: the tenders are the pools' own, no barrier weight)
+    if (r.trace) fprintf(stderr, "[newton] certified by the exact evaluation %s: dual %.10g gap %.2e infeas %.2e\n", where, x.dual, x.gap, x.infeas);
+    return true;
+}
 
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
-
-    std::vector<double> s(n), nu(n), d(n), G(n), Hd(n), rhs(n), s2(n), nu2(n), psi_x(n);
-    std::vector<int> mask(n), pin(n);
-    std::vector<double> lob(n);                 // lower bound of the log-price: log c for a GE token with c > 0 (handled by projection)
+// The start prices, the tokens' roles, the barrier-term count, the exact evaluation at the start and the first barrier weight.
+// warm_mu: the barrier weight to continue from (that of the previous solve, when cfmm_solve continues from it), or 0
+static int newton_prologue(NewtonRun &r, double warm_mu)
+{
+    cfmm_ctx *ctx = r.ctx;
+    const int n = r.n;
+    int rc;
     if (!pin_scratch(ctx, 8 * (size_t)n + 64 + n + (size_t)acc_stride(n))) return fail(ctx, CFMM_E_HIP, "pinned staging (%d tokens)", n);      // (the loop's part + cfmm_eval_dual's: no regrowth inside the loop)
+    // (the two modes differ in their order here: lean zeroes the warm starts BEFORE the price fetch, blit behind listed_tokens)
     if (ctx->lean_io) {                          // the start prices up; the warm starts of the per-direction solves zeroed (handoff.hpp)
         IoList z;
         for (int k = 0; k < CFMM_POOL_KINDS2; ++k) if (ctx->sm_ws[k]) z.zero(ctx->sm_ws[k], 2 * (size_t)ctx->pools->r2[k].b.m * sizeof(double));
@@ -1782,403 +1854,324 @@ int solve_newton(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out, int evals_b
         IoList p;
         p.copy(pin_device(ctx, ctx->pin), ctx->nu_acc, n * sizeof(double));
         if ((rc = launch_io(ctx, p, true)) || (rc = wait_io(ctx))) return rc;
-        std::memcpy(nu.data(), ctx->pin, n * sizeof(double));
+        std::memcpy(r.nu.data(), ctx->pin, n * sizeof(double));
     } else {
-        HIP_TRY(ctx, hipMemcpyAsync(nu.data(), ctx->nu_acc, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(r.nu.data(), ctx->nu_acc, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     if ((rc = listed_tokens(ctx))) return rc;
-    // flat[j]: the dual does not depend on nu_j at all -- no pool lists the token AND its offset is zero (one of the reference's
-    // linear-box kinds): pinned, and without its barrier term.  (Unlisted with h_j > 0, GE: nu_j h_j - mu log nu_j has its minimum
-    // at mu / h_j and follows the barrier to zero, the free-disposal optimum: left alone.)
-    std::vector<char> listed(n);
-    for (int j = 0; j < n; ++j) listed[j] = !(ct[j] < CFMM_ULOG && !ctx->listed[j] && h[j] == 0.0);
-    long long nbar = 0;
+    long long barrier_tokens = 0;
+    const int unbounded = newton::token_pass(n, ctx->hc.data(), ctx->hh.data(), ctx->hctype.data(), ctx->listed.data(), r.nu.data(), r.listed.data(),
+                                             r.mask.data(), r.lob.data(), r.s.data(), &barrier_tokens);
+    if (unbounded >= 0) return fail(ctx, CFMM_E_ARG, "solve: token %d is unconstrained (CFMM_FREE) with c = 0: unbounded", unbounded);
+    // (the pin mask goes down with every step's right-hand side; nothing reads sm_mask before that)
+    long long nbar = 0;                          // the barrier terms of the pools
     for (int k = 0; k < CFMM_POOL_KINDS2; ++k) nbar += 2 * ctx->pools->r2[k].b.m;
     nbar += 2 * ctx->pools->r2[CFMM_POOL_SUM2].b.m;
     for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) nbar += 3LL * k * ctx->pools->rg[CFMM_POOLK_SUM][k].b.m;      // (phik.hpp: the barrier-smoothed constant-sum entry, 3 K barrier terms)
-    for (int j = 0; j < n; ++j) {
-        mask[j] = ct[j] == CFMM_FREE || !listed[j];              // (a token the dual is flat in: its price stays where it starts)
-        lob[j] = (ct[j] == CFMM_GE && c[j] > 0.0) ? std::log(c[j]) : -INFINITY;
-        if (ct[j] == CFMM_GE && !(c[j] > 0.0) && listed[j]) nbar += 1;
-        double sj = std::log(nu[j]);
-        if (ct[j] == CFMM_FREE) {
-            if (!(c[j] > 0.0)) return fail(ctx, CFMM_E_ARG, "solve: token %d is unconstrained (CFMM_FREE) with c = 0: unbounded", j);
-            sj = std::log(c[j]);
-        } else sj = std::max(sj, lob[j]);
-        s[j] = sj; nu[j] = std::exp(sj);
-    }
-    // (the pin mask goes down with every step's right-hand side; nothing reads sm_mask before that)
-    if (sharded(ctx)) {                     // the barrier terms of the pools of every rank (the utility's are replicated)
-        long long ge = 0;
-        for (int j = 0; j < n; ++j) ge += ct[j] == CFMM_GE && !(c[j] > 0.0) && listed[j];
-        double cnt = (double)(nbar - ge);
+    if (sharded(ctx)) {                          // ... of every rank (the utility's are replicated)
+        double cnt = (double)nbar;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->sm_vec, &cnt, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        { int rc = all_reduce(ctx, ctx->sm_vec, 1, NCCL_FLOAT64, NCCL_SUM); if (rc) return rc; }
+        if ((rc = all_reduce(ctx, ctx->sm_vec, 1, NCCL_FLOAT64, NCCL_SUM))) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(&cnt, ctx->sm_vec, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        nbar = (long long)cnt + ge;
+        nbar = (long long)cnt;
     }
-
-    const std::vector<double> s_start = s;
+    newton::Tokens &tk = r.tk;
+    tk.n = n; tk.c = ctx->hc.data(); tk.h = ctx->hh.data(); tk.ctype = ctx->hctype.data();
+    tk.listed = r.listed.data(); tk.mask = r.mask.data(); tk.lob = r.lob.data();
+    tk.nbar = nbar + barrier_tokens; tk.infeas_floor = 1e-12 * ctx->g_max_reserve;
+    r.s_start = r.s;
     ctx->h_clean = false;
-    int evals = evals_before, steps = 0, status = 0;
-    double arb_x = 0.0;
-    auto exact = [&](const std::vector<double> &p) { ++evals; return cfmm_eval_dual(ctx, p.data(), &arb_x, psi_x.data(), nullptr); };
-    // smoothed dual value and its gradient in log-prices at (s, nu) from one smoothed evaluation
-    auto assemble = [&](const std::vector<double> &p, const SmoothEval &e, double mu, std::vector<double> *grad, std::vector<double> *hdiag) {
-        double g = e.value;
-        for (int j = 0; j < n; ++j) {
-            double Gj, hj = 0.0;
-            if (ct[j] >= CFMM_ULOG) {                     // the utility table: conjugate, gradient nu (psi - P*), nu^2 ubar'' on the diagonal
-                const HostUtilityTerm ut = host_utility_term(ct[j], c[j], h[j], p[j], e.psi[j]);
-                g += ut.ubar;
-                Gj = p[j] * (e.psi[j] - ut.pstar);
-                hj = ut.d2;
-            } else {
-                g += (p[j] - c[j]) * h[j];
-                Gj = p[j] * (e.psi[j] + h[j]);
-            }
-            // (the diagonal's own term: d^2/ds^2 of nu_j (psi_j + h_j) at fixed psi is nu_j (psi_j + h_j) itself -- taken BEFORE the barrier's
-            //  -mu, which is linear in the log-price and has no curvature: with it folded in the entry vanished exactly where a barrier
-            //  token sits at its optimum nu_j = mu / (psi_j + h_j), and a token no pool lists -- nothing else on its row -- made the
-            //  system singular: tools/fuzz_small.py, a swap whose offered token is unlisted)
-            const double Gj_lin = Gj;
-            if (ct[j] == CFMM_GE && !(c[j] > 0.0) && listed[j]) {      // nu_j > 0: the barrier is -mu log nu_j, linear in the log-price
-                g -= mu * std::log(p[j]);
-                Gj -= mu;
-            }
-            if (grad) (*grad)[j] = mask[j] ? 0.0 : Gj;
-            if (hdiag) (*hdiag)[j] = std::max(Gj_lin, 0.0) + hj;
-        }
-        return g;
-    };
-
     if (!ctx->lean_io)
         for (int k = 0; k < CFMM_POOL_KINDS2; ++k)
             if (ctx->sm_ws[k]) HIP_TRY(ctx, hipMemsetAsync(ctx->sm_ws[k], 0, 2 * (size_t)ctx->pools->r2[k].b.m * sizeof(double), ctx->stream));
-    if ((rc = exact(nu))) return rc;
-    double dual = arb_x;
-    for (int j = 0; j < n; ++j) dual += ct[j] >= CFMM_ULOG ? host_utility_term(ct[j], c[j], h[j], nu[j], 0.0).ubar : (nu[j] - c[j]) * h[j];
+    if ((rc = newton_exact(r))) return rc;
+    r.dual = newton::start_dual(tk, r.nu.data(), r.arb_x);
     static const double mu0_scale = getenv("CFMM_NEWTON_MU0") ? atof(getenv("CFMM_NEWTON_MU0")) : 0.1;                      // tuning knob
-    double mu = mu0_scale * std::max(std::fabs(dual), 1e-300) / (double)std::max<long long>(nbar, 1);
     static const double warm_mult = getenv("CFMM_NEWTON_WARM") ? atof(getenv("CFMM_NEWTON_WARM")) : 1e3;                    // tuning knob
-    if (warm_mu > 0.0) mu = std::min(mu, warm_mult * warm_mu);
+    r.sched.mu = newton::first_weight(mu0_scale, r.dual, tk.nbar, warm_mu, warm_mult);
     static const double sigma_env = getenv("CFMM_NEWTON_SHRINK") ? atof(getenv("CFMM_NEWTON_SHRINK")) : 0.0;      // tuning knob (A/B)
-    const double sigma = (sigma_env > 0.0 && sigma_env < 1.0) ? sigma_env : ((o.barrier_shrink > 0.0 && o.barrier_shrink < 1.0) ? o.barrier_shrink : 0.1);
-    const int max_newton = o.max_newton > 0 ? o.max_newton : 200;
-    double gap = 1.0, infeas = 1.0, primal = 0.0, reg = 0.0;
-    const bool trace = getenv("CFMM_NEWTON_TRACE") != nullptr;
-    int stalled = 0, forced_shrinks = 0;
-    bool shrink_now = false;
-    double best_infeas = 1.7976931348623157e308;
-    std::vector<double> slo(n, 0.0), slo2(n, 0.0);       // low-order log-prices (smooth.hpp: apply_slo)
-    bool slo_on = false;
-    SmoothEval e, e2;
-    bool have_e = false;                        // the accepted line-search point was evaluated already (at this barrier weight) ...
-    bool e_has_h = false;                       // ... together with its Hessian
-    // Chord steps (round 4).  A step's direction needs H^-1 G; with the inverse factor W = L^-1 riding the factorisation
-    // (chol.hpp) the factor of an EARLIER step applies to a new gradient in two matrix-vector products (~20 us against ~400 for a
-    // fresh factorisation + solve), and such a step needs no Hessian assembly either.  Between two steps of the path the
-    // ONLY at an unchanged barrier weight: measured on config 5, a factor from the previous weight (10x larger) gives
-    // directions whose full step the Armijo test refuses (t = 1/8 .. 1/16) and the solve takes 20-24 steps instead of 9,
-    // 10.2-12.4 ms instead of 6.3 -- near their peg the stableswap pools' curvature terms kappa = 1 / (mu / D^2 - nu L'') follow
-    // the weight.  At the SAME weight (the centring steps at the final weight, which is where the step count of the path is
-    // decided) the Hessian barely moves: up to `chord_max` such steps in a row reuse the last factor; a chord direction that is not
-    // a descent direction, or whose full step the Armijo test refuses, sends the step back to a fresh factorisation.
-    // Pool-sharded: every rank holds the same all-reduced Hessian, factors it identically (fixed summation orders: chol.hpp) and
-    // takes these decisions on the same numbers -- the ranks stay in step.  CFMM_CHORD=0 switches it off (A/B).
+    r.sched.sigma = (sigma_env > 0.0 && sigma_env < 1.0) ? sigma_env : ((r.o.barrier_shrink > 0.0 && r.o.barrier_shrink < 1.0) ? r.o.barrier_shrink : 0.1);
+    r.max_newton = r.o.max_newton > 0 ? r.o.max_newton : 200;
     static const int chord_max = getenv("CFMM_CHORD") ? atoi(getenv("CFMM_CHORD")) : 3;
-    // ... and only behind a step that was taken in full: where the Armijo test has just cut a fresh Newton step (the shipped
-    // instances' partially filled constant-sum pool: t = 1/4) the iteration is outside the region in which an old Hessian
-    // serves -- chord steps there were cut to 1/8 .. 1/128 and the solve took 34 steps instead of 10.
-    bool fac_valid = false, chord_bad = false, last_full = false;
-    double dec_prev = 0.0;                      // the decrement G' H^-1 G of the last accepted step
-    double move_prev = 0.0;                     // ... and its largest log-price move
-    int chord_run = 0, chord_steps = 0;
-    double fac_mu = 0.0;
-    // The certificates at the START point, from the exact evaluation just made (round 6).  Prices inside the utility's
-    // box at which psi + h is feasible and complementary ARE the optimum -- the no-arbitrage network under a linear utility is the
-    // case that matters: at nu = c nothing trades, psi = 0, value 0.  The barrier path has no business there: its smoothed pools trade
-    // O(mu) each, the iteration chases rounding around a zero-valued optimum and explicit `CFMM_METHOD_NEWTON` runs ended "stalled" at
-    // gaps up to 4.8e-2 (tools/fuzz_table.py seeds 12, 345, 609, 819, 945; fuzz_small.py seed 1434).  Linear-box utilities only.
-    const char *numeric_where = "";
-    // ... and the same test at the prices a run ENDS on without its certificates (stalled / out of steps): with an optimum where nothing
-    // trades but the prices had to move to get there (fuzz_small.py seeds 1387, 1434; fuzz_table.py 12, 345), the smoothed point keeps
-    // trading O(mu) per pool -- a gap of 1e-5 against a value of zero -- while the EXACT evaluation at the very same prices is the optimum.
-    auto certify_exact = [&](const char *where) -> bool {       // (psi_x, arb_x: the exact evaluation at nu)
-        double cs = 0.0, viol = 0.0, scale = 0.0, lin = 0.0, pr = 0.0;
-        for (int j = 0; j < n; ++j) {
-            if (ct[j] >= CFMM_ULOG) return false;
-            const double r = psi_x[j] + h[j];
-            lin += (nu[j] - c[j]) * h[j]; pr += c[j] * psi_x[j]; cs += (nu[j] - c[j]) * r;
-            viol = std::max(viol, ct[j] == CFMM_GE ? std::max(-r, 0.0) : (ct[j] == CFMM_EQ ? std::fabs(r) : 0.0));
-            scale = std::max(scale, std::max(std::fabs(psi_x[j]), std::fabs(h[j])));
-        }
-        const double d0 = lin + arb_x;
-        const double gap0 = std::fabs(cs) / std::max(1.0, std::fabs(d0));
-        const double infeas0 = viol / std::max(std::max(scale, 1e-12 * ctx->g_max_reserve), 1e-300);
-        if (!(std::isfinite(d0) && gap0 <= o.tol_gap && infeas0 <= o.tol_infeas)) return false;
-        status = 1; gap = gap0; infeas = infeas0; primal = pr; dual = d0;
-        e.psi = psi_x; e.value = arb_x; e.trade = arb_x;
-        mu = 0.0;                               // (an exact point: the tenders are the pools' own, no barrier weight)
-        if (trace) fprintf(stderr, "[newton] certified by the exact evaluation %s: dual %.10g gap %.2e infeas %.2e\n", where, d0, gap0, infeas0);
-        return true;
-    };
-    const bool certified_at_start = certify_exact("at the start prices");
-    if (!certified_at_start)
-    for (;;) {
-        // (not in the low-order regime either -- moves below ~1e-10 in log-price, where a partially filled constant-sum pool's
-        //  fill reacts to price changes under the fp64 resolution of the prices: the Hessian changes by orders of magnitude from
-        //  step to step there, and steps on a stale one only feed the stall counter)
-        const bool use_chord = fac_valid && fac_mu == mu && last_full && !slo_on && move_prev > 1e-10 && !chord_bad && chord_run < chord_max && reg == 0.0 && ctx->inverse_factor && ctx->Winv != nullptr;
-        if (!have_e || (!use_chord && !e_has_h)) {
-            if ((rc = smooth_eval_host(ctx, nu, mu, !use_chord, e, true, slo_on ? &slo : nullptr))) return rc;
-            ++evals;
-            e_has_h = !use_chord;
-        }
-        have_e = false;
-        const double gmu = assemble(nu, e, mu, &G, &Hd);
-        if (!std::isfinite(gmu)) { status = CFMM_E_NUMERIC; numeric_where = "the smoothed dual value"; break; }
-        // certificates: exact dual value (an upper bound) against the smoothed, pool-feasible primal point.  Each
-        // barrier term costs at most mu of pool value, so sum_i arb_i(nu) <= nu'(L - D) + mu nbar: while that bound
-        // is still far from the tolerance the exact evaluation is skipped and the bound reported instead.
-        primal = 0.0;
-        double cs = 0.0, viol = 0.0, scale = 0.0, lin = 0.0;
-        for (int j = 0; j < n; ++j) {
-            if (ct[j] >= CFMM_ULOG) {                      // Fenchel-Young gap term of a table entry (lbfgs_rules.hpp)
-                const HostUtilityTerm ut = host_utility_term(ct[j], c[j], h[j], nu[j], e.psi[j]);
-                lin += ut.ubar; primal += ut.uval;
-                cs += ut.ubar + nu[j] * e.psi[j] - ut.uval;
-                viol = std::max(viol, ut.viol);
-                scale = std::max(scale, std::max(std::fabs(e.psi[j]), std::fabs(ut.pstar)));
-                continue;
-            }
-            const double r = e.psi[j] + h[j];
-            lin += (nu[j] - c[j]) * h[j];
-            primal += c[j] * e.psi[j];
-            cs += (nu[j] - c[j]) * r;
-            viol = std::max(viol, ct[j] == CFMM_GE ? std::max(-r, 0.0) : (ct[j] == CFMM_EQ ? std::fabs(r) : 0.0));
-            scale = std::max(scale, std::max(std::fabs(e.psi[j]), std::fabs(h[j])));
-        }
-        // (relative to the larger of trade and offset -- but never to less than 1e-12 of the largest reserve: at a no-arbitrage optimum
-        //  the smoothed point's trades are rounding noise, and noise over noise is not an infeasibility; tools/fuzz_small.py)
-        infeas = viol / std::max(std::max(scale, 1e-12 * ctx->g_max_reserve), 1e-300);
-        // sub = sum_i arb_i(nu) - nu'(L - D) >= 0 is the part of the gap the barrier weight controls (<= mu nbar);
-        // the rest, the complementarity term cs, vanishes with the centring.  The weight stops shrinking as soon as
-        // sub alone fits the tolerance: pushing it further only stiffens the smoothed dual (flows then react to price
-        // changes below fp64 resolution and the feasibility of psi_mu stops improving).
-        double sub = mu * (double)nbar;
-        dual = lin + e.trade + sub;
-        // (the exact evaluation is also skipped while psi_mu is still far from feasible: no certificate can hold at this point,
-        //  and the bound serves the barrier schedule just as well -- three evaluations of ~0.14 ms less per config-5 solve)
-        if (steps == 0 || (sub <= 10.0 * o.tol_gap * std::max(1.0, std::fabs(dual)) && infeas <= 10.0 * o.tol_infeas)) {
-            if (steps > 0 && (rc = exact(nu))) return rc;
-            dual = lin + arb_x;
-            sub = std::max(arb_x - e.trade, 0.0);
-        }
-        gap = (sub + cs) / std::max(1.0, std::fabs(dual));
-        const bool final_mu = sub <= 0.5 * o.tol_gap * std::max(1.0, std::fabs(dual));
-        if (trace) fprintf(stderr, "[newton] step %d evals %d mu %.3e g_mu %.10g dual %.10g primal %.10g gap %.2e infeas %.2e reg %.1e\n",
-                           steps, evals, mu, gmu, dual, primal, gap, infeas, reg);
-        if (std::fabs(gap) <= o.tol_gap && infeas <= o.tol_infeas) { status = 1; break; }
-        if (steps >= max_newton || evals - evals_before >= o.max_evals) { status = 3; break; }
+    r.chord_max = chord_max;
+    return CFMM_OK;
+}
 
-        // Newton direction: (H + diag) d = -G on the unpinned tokens.  Pinned: the CFMM_FREE tokens, and (projected
-        // Newton) every GE token sitting on its bound nu = c with the gradient pushing it further down
-        for (int j = 0; j < n; ++j) {
-            pin[j] = mask[j] || (s[j] + slo[j] <= lob[j] + 1e-13 * std::max(1.0, std::fabs(lob[j])) && G[j] > 0.0);
-            if (pin[j]) G[j] = 0.0;
-            rhs[j] = -G[j]; Hd[j] += reg;
-        }
-        // (through the pinned staging, behind smooth_eval_host's three vectors: [Hd | rhs] in one copy, the pin mask, the direction back)
-        double *pin_vec = ctx->pin + 4 * (size_t)n, *pin_d = ctx->pin + 6 * (size_t)n;
-        int *pin_mask = reinterpret_cast<int *>(ctx->pin + 7 * (size_t)n), *pin_info = pin_mask + n + (n & 1);
-        std::memcpy(pin_mask, pin.data(), n * sizeof(int));
-        std::memcpy(pin_vec, Hd.data(), n * sizeof(double)); std::memcpy(pin_vec + n, rhs.data(), n * sizeof(double));
-        const bool lean = ctx->lean_io;
-        if (lean) {                                // [mask | diagonal | right-hand side] down and the factorisation's flag zeroed: one launch
-            IoList l;
-            l.copy(ctx->sm_mask, pin_device(ctx, pin_mask), n * sizeof(int));
-            l.copy(ctx->sm_vec, pin_device(ctx, pin_vec), 2 * (size_t)n * sizeof(double));
-            if (!use_chord) l.zero(ctx->sm_info, 4 * sizeof(int));
-            if ((rc = launch_io(ctx, l, false))) return rc;
-        } else {
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->sm_mask, pin_mask, n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->sm_vec, pin_vec, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        }
-        auto fetch = [&](bool with_info) -> int {   // the direction (and the factorisation's flag) back
-            if (lean) {
-                IoList p;
-                p.copy(pin_device(ctx, pin_d), ctx->sm_vec + n, n * sizeof(double));
-                if (with_info) p.copy(pin_device(ctx, pin_info), ctx->sm_info, 2 * sizeof(int));
-                int r = launch_io(ctx, p, true);
-                return r ? r : wait_io(ctx);
-            }
-            if (with_info) HIP_TRY(ctx, hipMemcpyAsync(pin_info, ctx->sm_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(pin_d, ctx->sm_vec + n, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            return CFMM_OK;
-        };
-        int info = 0;
-        if (use_chord) {
-            if ((rc = launch_chord(ctx, n, ctx->sm_vec + n, ctx->sm_vec + n))) return rc;
-            if ((rc = fetch(false))) return rc;
-        } else {
-            hipLaunchKernelGGL(hess_finish_kernel, dim3(1024), dim3(256), 0, ctx->stream, ctx->H, n, hess_nr(n), hess_ld(n), (const double *)ctx->sm_vec,
-                               (const int *)ctx->sm_mask, (const double *)(ctx->sm_vec + n));
-            HIP_TRY(ctx, hipGetLastError());
-            if ((rc = launch_cholesky(ctx, n, ctx->sm_vec + n, lean))) return rc;
-            e_has_h = false;                       // (factored in place: the assembled Hessian is gone)
-            if ((rc = fetch(true))) return rc;
-            info = *pin_info;
-            if (lean) {                            // the factor has served (chord steps go through the inverse factor): zero the 8.6 MB for the next
-                IoList z;                          // Hessian NOW, under the host's work on the trial point, instead of in front of that evaluation
-                z.zero(ctx->H, (size_t)hess_ld(n) * hess_nr(n) * sizeof(double));
-                if ((rc = launch_io(ctx, z, false))) return rc;
-                ctx->h_clean = true;
-            }
-            fac_valid = info == 0; fac_mu = mu; chord_run = 0; chord_bad = false;
-        }
-        d.assign(pin_d, pin_d + n);
-        if (info != 0) {                       // not positive definite: shift the diagonal and assemble again
-            double md = 0.0;
-            for (int j = 0; j < n; ++j) md = std::max(md, std::max(Hd[j], std::fabs(G[j])));
-            reg = reg == 0.0 ? 1e-12 * std::max(md, 1e-300) : reg * 100.0;
-            if (!(reg < 1e300)) { status = CFMM_E_NUMERIC; numeric_where = "the diagonal shift of a system that never became positive definite"; break; }
-            have_e = true;                         // (same point, same weight: only the Hessian has to be assembled again)
-            continue;
-        }
-        if (use_chord) {                           // the old factor must still give a descent direction on the free tokens
-            double dc = 0.0;
-            bool fin = true;
-            for (int j = 0; j < n; ++j) { if (!pin[j]) dc -= G[j] * d[j]; fin = fin && std::isfinite(d[j]); }
-            // ... and the iteration must be contracting fast under it: a chord step shrinks the decrement by the square of its
-            // contraction factor, so "at least a hundredfold since the last step" = a factor <= 0.1 per step.  The shipped
-            // instances' final centring (a partially filled constant-sum pool, steps below the resolution of the log-prices)
-            // contracts only 3x per chord step where ONE fresh Newton step finishes: 30 steps instead of 24 without this test.
-            if (!fin || !(dc > 0.0) || !(dc <= 1e-2 * dec_prev)) { chord_bad = true; have_e = true; continue; }      // back to a fresh factorisation, at this point
-        }
-        ++steps;
-        reg = reg > 0.0 ? 0.1 * reg : 0.0;      // a singular Hessian (tokens no pool connects) tends to stay singular: keep most of the shift
-        double dec = 0.0, dmax = 0.0;
-        for (int j = 0; j < n; ++j) { if (pin[j]) d[j] = 0.0; dec -= G[j] * d[j]; dmax = std::max(dmax, std::fabs(d[j])); }
-        if (!std::isfinite(dec) || !std::isfinite(dmax)) {
-            int bad_d = 0, bad_g = 0;
-            for (int j = 0; j < n; ++j) { bad_d += !std::isfinite(d[j]); bad_g += !std::isfinite(G[j]); }
-            static thread_local char buf[200];
-            snprintf(buf, sizeof buf, "the Newton direction (%d of %d entries non-finite, gradient %d, %s step, factorisation flag %d)", bad_d, n, bad_g,
-                     use_chord ? "chord" : "fresh", info);
-            status = CFMM_E_NUMERIC; numeric_where = buf; break;
-        }
-        if (final_mu) {                        // centring at the final weight: give up (before moving, so that nu, psi and the
-            // certificates stay those of one point) once the Newton decrement is at rounding level and the feasibility of
-            // psi_mu has stopped improving all the same
-            if (infeas < 0.5 * best_infeas) { best_infeas = infeas; stalled = 0; }
-            else if (dec <= 1e-13 * std::max(1.0, std::fabs(gmu))) {
-                // centred, feasible, and the gap a hair over the tolerance (1.01e-7 against 1e-7: tools/fuzz_table.py seeds 733, 757): what
-                // is left of it is the complementarity term, which scales with the weight like the barrier's own share -- the weight
-                // was final by that share alone.  One more decade of it (at most three) instead of four idle steps and "stalled".
-                if (infeas <= o.tol_infeas && std::fabs(gap) > o.tol_gap && forced_shrinks < 3) { shrink_now = true; ++forced_shrinks; }
-                else ++stalled;
-            }
-            if (stalled >= 4) { status = 2; break; }
-        }
-        // step length: cap on the log-price move, fraction to the boundary nu > c, Armijo back-tracking on the smoothed dual
-        double t = std::min(1.0, o.max_step / std::max(dmax, 1e-300));
-        const double t_first = t;
-        bool moved = false;
-        bool slo2_on = false;
-        for (int ls = 0; ls < 40; ++ls) {
-            // steps below the fp64 resolution of the log-prices go into their low-order part (smooth.hpp: apply_slo)
-            double lo_max = 0.0;
-            for (int j = 0; j < n; ++j) lo_max = std::max(lo_max, std::fabs(slo[j] + t * d[j]));
-            const bool small = final_mu && t * dmax < 1e-11 && lo_max < 1e-10;
-            double gd = 0.0;                    // G'(projected move): the Armijo slope of the projected step
-            for (int j = 0; j < n; ++j) {
-                if (small) { s2[j] = s[j]; nu2[j] = nu[j]; slo2[j] = mask[j] ? 0.0 : std::max(slo[j] + t * d[j], lob[j] - s[j]); }
-                else { s2[j] = std::max(s[j] + slo[j] + t * d[j], lob[j]); nu2[j] = mask[j] ? nu[j] : std::exp(s2[j]); slo2[j] = 0.0; }
-                gd += G[j] * ((s2[j] + slo2[j]) - (s[j] + slo[j]));
-            }
-            slo2_on = small;
-            // the first trial is nearly always taken: when the barrier weight stays as it is, the next step starts with exactly
-            // this evaluation plus the Hessian -- so ask for the Hessian now (+50%) and save that evaluation and its round trip
-            // (a next step that reuses this step's factor -- a chord step -- needs no Hessian: the plain evaluation serves it)
-            const bool stay = final_mu || !(dec < 10.0 * mu * (double)nbar);
-            const bool next_chord = ls == 0 && stay && !slo2_on && t * dmax > 1e-10 && fac_valid && fac_mu == mu && chord_run + (use_chord ? 1 : 0) < chord_max && reg == 0.0 && ctx->inverse_factor && ctx->Winv != nullptr;
-            const bool with_h = ls == 0 && stay && !next_chord;
-            if ((rc = smooth_eval_host(ctx, nu2, mu, with_h, e2, true, slo2_on ? &slo2 : nullptr))) return rc;
-            ++evals;
-            const double g2 = assemble(nu2, e2, mu, nullptr, nullptr);
-            // (the value carries a few units of rounding of its own -- fp64 atomics over tens of thousands of pools: at the final weight the
-            //  required decrease armijo * gd falls BELOW one ulp of g_mu, and whether the full Newton step passed was decided by summation
-            //  noise: the same state took t = 1 and converged in one run and backed off to t = 1/16 and stalled in the next; round 5)
-            if (g2 <= gmu + o.armijo * gd + 2e-15 * std::fabs(gmu) || dec <= 1e-13 * std::fabs(gmu)) {
-                moved = true;
-                have_e = stay && (with_h || next_chord);           // reusable where the weight stays: with its Hessian, or for a chord step
-                e_has_h = with_h;
-                if (use_chord && ls > 0) chord_bad = true;         // the old factor's full step was refused: factor afresh next time
-                break;
-            }
-            t *= 0.5;
-        }
-        if (trace) fprintf(stderr, "[newton]    dec %.3e |d| %.3e t %.3e (first %.3e) moved %d%s\n", dec, dmax, t, t_first, (int)moved, use_chord ? " (chord)" : "");
-        if (!moved && use_chord) {                     // the old factor gave no acceptable step at all: this step again, with a fresh one
-            chord_bad = true; have_e = true; --steps;
-            continue;
-        }
-        if (!moved) { status = 2; break; }
-        if (use_chord) { ++chord_run; ++chord_steps; }
-        last_full = t == t_first;
-        dec_prev = dec; move_prev = t * dmax;
-        s = s2; nu = nu2; slo = slo2; slo_on = slo2_on;
-        if (have_e) std::swap(e, e2);
-        {                                       // a price that has collapsed by e^-60 since the start: a token that must be traded away
-            bool collapsed = false;             // but that no pool takes (the program is infeasible); no point in going on
-            for (int j = 0; j < n; ++j) collapsed = collapsed || (!mask[j] && s[j] < s_start[j] - 60.0);
-            if (collapsed) { status = 2; break; }
-        }
-        if (shrink_now) { shrink_now = false; mu *= sigma; have_e = false; continue; }
-        if (final_mu) continue;                                        // the weight is small enough: finish centring at it
-        if (dec < 10.0 * mu * (double)nbar && (t == t_first || dec < 1e-3 * mu * (double)nbar)) { mu *= sigma; have_e = false; }      // (an evaluation belongs to its weight)
+// phase 1: may this pass reuse the factor (a chord step)?  The smoothed evaluation at the point, unless the line search left it
+static int newton_evaluate(NewtonRun &r)
+{
+    r.p = NewtonRun::Pass{};
+    r.p.use_chord = newton::chord_allowed({r.fac.valid, r.fac.mu, r.sched.mu, r.fac.last_full, r.slo_on, r.fac.move_prev, r.fac.chord_bad,
+                                           r.fac.chord_run, r.chord_max, r.sched.reg, r.inverse_factor()});
+    if (!r.cache.have_e || (!r.p.use_chord && !r.cache.e_has_h)) {
+        int rc = smooth_eval_host(r.ctx, r.nu, r.sched.mu, !r.p.use_chord, r.e, true, r.slo_on ? &r.slo : nullptr); if (rc) return rc;
+        ++r.evals;
+        r.cache.e_has_h = !r.p.use_chord;
     }
-    if (status == 2 || status == 3) {
+    r.cache.have_e = false;
+    return CFMM_OK;
+}
+
+// phase 2: gradient and diagonal, the certificates of the point, the stop tests
+static int newton_certificates(NewtonRun &r, Phase &next)
+{
+    const cfmm_opts &o = r.o;
+    const double mu = r.sched.mu;
+    next = Phase::Stop;
+    r.p.gmu = newton::assemble(r.tk, r.nu.data(), r.e.psi.data(), r.e.value, mu, r.G.data(), r.Hd.data());
+    if (!std::isfinite(r.p.gmu)) return r.numeric("the smoothed dual value");
+    // certificates: exact dual value (an upper bound) against the smoothed, pool-feasible primal point.  Each
+    // barrier term costs at most mu of pool value, so sum_i arb_i(nu) <= nu'(L - D) + mu nbar: while that bound
+    // is still far from the tolerance the exact evaluation is skipped and the bound reported instead.
+    const newton::Certificate k = newton::certificate(r.tk, r.nu.data(), r.e.psi.data());
+    r.primal = k.primal;
+    r.infeas = k.infeas(r.tk);
+    double sub = mu * (double)r.tk.nbar;
+    r.dual = k.lin + r.e.trade + sub;
+    if (newton::exact_due(r.steps, sub, r.dual, r.infeas, o.tol_gap, o.tol_infeas)) {
+        if (r.steps > 0) { int rc = newton_exact(r); if (rc) return rc; }      // (step 0: the prologue's evaluation is this point's)
+        r.dual = k.lin + r.arb_x;
+        sub = std::max(r.arb_x - r.e.trade, 0.0);
+    }
+    r.gap = (sub + k.cs) / std::max(1.0, std::fabs(r.dual));
+    r.p.final_mu = newton::weight_is_final(sub, r.dual, o.tol_gap);
+    if (r.trace) fprintf(stderr, "[newton] step %d evals %d mu %.3e g_mu %.10g dual %.10g primal %.10g gap %.2e infeas %.2e reg %.1e\n",
+                         r.steps, r.evals, mu, r.p.gmu, r.dual, r.primal, r.gap, r.infeas, r.sched.reg);
+    if (std::fabs(r.gap) <= o.tol_gap && r.infeas <= o.tol_infeas) { r.status = 1; return CFMM_OK; }
+    if (r.steps >= r.max_newton || r.evals - r.evals_before >= o.max_evals) { r.status = 3; return CFMM_OK; }
+    next = Phase::Go;
+    return CFMM_OK;
+}
+
+// phase 3: the direction -- mask, diagonal and right-hand side down, a fresh factorisation or the old factor (chord), the direction back
+static int newton_direction(NewtonRun &r, Phase &next)
+{
+    cfmm_ctx *ctx = r.ctx;
+    const int n = r.n;
+    const bool use_chord = r.p.use_chord, lean = ctx->lean_io;
+    int rc;
+    newton::pin_and_right_hand_side(r.tk, r.s.data(), r.slo.data(), r.sched.reg, r.G.data(), r.Hd.data(), r.pin.data(), r.rhs.data());
+    // (through the pinned staging, behind smooth_eval_host's three vectors: [Hd | rhs] in one copy, the pin mask, the direction back)
+    double *pin_vec = ctx->pin + 4 * (size_t)n, *pin_d = ctx->pin + 6 * (size_t)n;
+    int *pin_mask = reinterpret_cast<int *>(ctx->pin + 7 * (size_t)n), *pin_info = pin_mask + n + (n & 1);
+    std::memcpy(pin_mask, r.pin.data(), n * sizeof(int));
+    std::memcpy(pin_vec, r.Hd.data(), n * sizeof(double)); std::memcpy(pin_vec + n, r.rhs.data(), n * sizeof(double));
+    HandOff down(ctx);                             // [mask | diagonal | right-hand side] down and the factorisation's flag zeroed: one launch
+    down.down(ctx->sm_mask, pin_mask, n * sizeof(int));
+    down.down(ctx->sm_vec, pin_vec, 2 * (size_t)n * sizeof(double));
+    if (!use_chord) down.zero_lean_only(ctx->sm_info, 4 * sizeof(int));       // (blit: launch_cholesky zeroes it)
+    if ((rc = down.run(false))) return rc;
+    // the direction (and the factorisation's flag) back.  (The two modes list the two in opposite orders, and lean takes both
+    // words of the flag: an explicit pair.)
+    auto fetch = [&](bool with_info) -> int {
+        if (lean) {
+            IoList p;
+            p.copy(pin_device(ctx, pin_d), ctx->sm_vec + n, n * sizeof(double));
+            if (with_info) p.copy(pin_device(ctx, pin_info), ctx->sm_info, 2 * sizeof(int));
+            int rl = launch_io(ctx, p, true);
+            return rl ? rl : wait_io(ctx);
+        }
+        if (with_info) HIP_TRY(ctx, hipMemcpyAsync(pin_info, ctx->sm_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(pin_d, ctx->sm_vec + n, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return CFMM_OK;
+    };
+    if (use_chord) {
+        if ((rc = launch_chord(ctx, n, ctx->sm_vec + n, ctx->sm_vec + n))) return rc;
+        if ((rc = fetch(false))) return rc;
+    } else {
+        hipLaunchKernelGGL(hess_finish_kernel, dim3(1024), dim3(256), 0, ctx->stream, ctx->H, n, hess_nr(n), hess_ld(n), (const double *)ctx->sm_vec,
+                           (const int *)ctx->sm_mask, (const double *)(ctx->sm_vec + n));
+        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = launch_cholesky(ctx, n, ctx->sm_vec + n, lean))) return rc;
+        r.cache.e_has_h = false;                   // (factored in place: the assembled Hessian is gone)
+        if ((rc = fetch(true))) return rc;
+        r.p.info = *pin_info;
+        if (lean) {                                // the factor has served (chord steps go through the inverse factor): zero the 8.6 MB for the next
+            IoList z;                              // Hessian NOW, under the host's work on the trial point, instead of in front of that evaluation
+            z.zero(ctx->H, (size_t)hess_ld(n) * hess_nr(n) * sizeof(double));
+            if ((rc = launch_io(ctx, z, false))) return rc;
+            ctx->h_clean = true;
+        }
+        r.fac.valid = r.p.info == 0; r.fac.mu = r.sched.mu; r.fac.chord_run = 0; r.fac.chord_bad = false;
+    }
+    r.d.assign(pin_d, pin_d + n);
+    next = Phase::Again;
+    if (r.p.info != 0) {                           // not positive definite: shift the diagonal and assemble again
+        double md = 0.0;
+        for (int j = 0; j < n; ++j) md = std::max(md, std::max(r.Hd[j], std::fabs(r.G[j])));
+        if (!newton::raise_shift(r.sched, md)) { next = Phase::Stop; return r.numeric("the diagonal shift of a system that never became positive definite"); }
+        r.cache.have_e = true;                     // (same point, same weight: only the Hessian has to be assembled again)
+        return CFMM_OK;
+    }
+    if (use_chord) {
+        double dc = 0.0;
+        bool fin = true;
+        for (int j = 0; j < n; ++j) { if (!r.pin[j]) dc -= r.G[j] * r.d[j]; fin = fin && std::isfinite(r.d[j]); }
+        if (!newton::chord_direction_serves(fin, dc, r.fac.dec_prev)) { r.fac.chord_bad = true; r.cache.have_e = true; return CFMM_OK; }      // back to a fresh factorisation, at this point
+    }
+    next = Phase::Go;
+    return CFMM_OK;
+}
+
+// phase 4: the step counts; its decrement, and at the final weight the stall test
+static int newton_decrement(NewtonRun &r, Phase &next)
+{
+    const int n = r.n;
+    ++r.steps;
+    newton::relax_shift(r.sched);
+    double dec = 0.0, dmax = 0.0;
+    for (int j = 0; j < n; ++j) { if (r.pin[j]) r.d[j] = 0.0; dec -= r.G[j] * r.d[j]; dmax = std::max(dmax, std::fabs(r.d[j])); }
+    r.p.dec = dec; r.p.dmax = dmax;
+    next = Phase::Stop;
+    if (!std::isfinite(dec) || !std::isfinite(dmax)) {
+        int bad_d = 0, bad_g = 0;
+        for (int j = 0; j < n; ++j) { bad_d += !std::isfinite(r.d[j]); bad_g += !std::isfinite(r.G[j]); }
+        static thread_local char buf[200];
+        snprintf(buf, sizeof buf, "the Newton direction (%d of %d entries non-finite, gradient %d, %s step, factorisation flag %d)", bad_d, n, bad_g,
+                 r.p.use_chord ? "chord" : "fresh", r.p.info);
+        return r.numeric(buf);
+    }
+    if (r.p.final_mu && newton::final_weight_stalls(r.sched, r.infeas, dec, r.p.gmu, r.gap, r.o.tol_gap, r.o.tol_infeas)) { r.status = 2; return CFMM_OK; }
+    next = Phase::Go;
+    return CFMM_OK;
+}
+
+// phase 5: step length -- cap on the log-price move, fraction to the boundary nu > c, Armijo back-tracking on the smoothed dual
+static int newton_line_search(NewtonRun &r, Phase &next)
+{
+    NewtonRun::Pass &p = r.p;
+    const double mu = r.sched.mu;
+    p.t = p.t_first = newton::first_step_length(r.o.max_step, p.dmax);
+    bool moved = false;
+    // the first trial is nearly always taken: when the barrier weight stays as it is, the next step starts with exactly
+    // this evaluation plus the Hessian -- so ask for the Hessian now (+50%) and save that evaluation and its round trip
+    // (a next step that reuses this step's factor -- a chord step -- needs no Hessian: the plain evaluation serves it)
+    const bool stay = newton::weight_stays(p.final_mu, p.dec, mu, r.tk.nbar);
+    for (int ls = 0; ls < newton::LINE_SEARCH_PASSES; ++ls) {
+        const newton::Trial tr = newton::trial_point(r.tk, r.s.data(), r.nu.data(), r.slo.data(), r.d.data(), r.G.data(), p.t, p.dmax, p.final_mu,
+                                                     r.s2.data(), r.nu2.data(), r.slo2.data());
+        p.slo2_on = tr.small;
+        const bool next_chord = stay && newton::chord_allowed({r.fac.valid, r.fac.mu, mu, ls == 0, tr.small, p.t * p.dmax, r.fac.chord_bad,
+                                                               r.fac.chord_run + (p.use_chord ? 1 : 0), r.chord_max, r.sched.reg, r.inverse_factor()});
+        const bool with_h = ls == 0 && stay && !next_chord;
+        int rc = smooth_eval_host(r.ctx, r.nu2, mu, with_h, r.e2, true, p.slo2_on ? &r.slo2 : nullptr); if (rc) return rc;
+        ++r.evals;
+        const double g2 = newton::assemble(r.tk, r.nu2.data(), r.e2.psi.data(), r.e2.value, mu, nullptr, nullptr);
+        if (newton::trial_accepted(g2, p.gmu, r.o.armijo, tr.gd, p.dec)) {
+            moved = true;
+            r.cache.have_e = stay && (with_h || next_chord);      // reusable where the weight stays: with its Hessian, or for a chord step
+            r.cache.e_has_h = with_h;
+            if (p.use_chord && ls > 0) r.fac.chord_bad = true;    // the old factor's full step was refused: factor afresh next time
+            break;
+        }
+        p.t *= 0.5;
+    }
+    if (r.trace) fprintf(stderr, "[newton]    dec %.3e |d| %.3e t %.3e (first %.3e) moved %d%s\n", p.dec, p.dmax, p.t, p.t_first, (int)moved, p.use_chord ? " (chord)" : "");
+    if (!moved && p.use_chord) {                   // the old factor gave no acceptable step at all: this step again, with a fresh one
+        r.fac.chord_bad = true; r.cache.have_e = true; --r.steps;
+        next = Phase::Again;
+        return CFMM_OK;
+    }
+    if (!moved) { r.status = 2; next = Phase::Stop; return CFMM_OK; }
+    next = Phase::Go;
+    return CFMM_OK;
+}
+
+// phase 6: the trial point becomes the point; the barrier weight for the next pass
+static int newton_accept(NewtonRun &r, Phase &next)
+{
+    const NewtonRun::Pass &p = r.p;
+    if (p.use_chord) { ++r.fac.chord_run; ++r.chord_steps; }
+    r.fac.last_full = p.t == p.t_first;
+    r.fac.dec_prev = p.dec; r.fac.move_prev = p.t * p.dmax;
+    r.s = r.s2; r.nu = r.nu2; r.slo = r.slo2; r.slo_on = p.slo2_on;
+    if (r.cache.have_e) std::swap(r.e, r.e2);
+    if (newton::price_collapsed(r.tk, r.s.data(), r.s_start.data())) { r.status = 2; next = Phase::Stop; return CFMM_OK; }
+    next = Phase::Go;
+    newton::Schedule &sc = r.sched;
+    if (sc.shrink_now) { sc.shrink_now = false; sc.mu *= sc.sigma; r.cache.have_e = false; }                 // (an evaluation belongs to its weight)
+    else if (newton::weight_shrinks(p.final_mu, p.dec, sc.mu, r.tk.nbar, p.t == p.t_first)) { sc.mu *= sc.sigma; r.cache.have_e = false; }
+    return CFMM_OK;
+}
+
+// The exact certificate at a stalled end; the point where the read-backs expect it; the statistics.
+static int newton_epilogue(NewtonRun &r, cfmm_stats *out, std::chrono::steady_clock::time_point t0)
+{
+    cfmm_ctx *ctx = r.ctx;
+    const int n = r.n;
+    const std::vector<double> &nu = r.nu, &psi = r.e.psi;
+    int rc;
+    if (r.status == 2 || r.status == 3) {
         // (the low-order log-prices are below the resolution of the prices the exact evaluation takes: the exact point is the one AT nu)
-        if ((rc = exact(nu))) return rc;
-        if (certify_exact("at the prices the barrier path stalled on")) slo_on = false;
+        if ((rc = newton_exact(r))) return rc;
+        if (newton_certify_exact(r, "at the prices the barrier path stalled on")) r.slo_on = false;
     }
-    if (trace) fprintf(stderr, "[newton] %d steps, %d of them chord steps (no factorisation)\n", steps, chord_steps);
+    if (r.trace) fprintf(stderr, "[newton] %d steps, %d of them chord steps (no factorisation)\n", r.steps, r.chord_steps);
     HIP_TRY(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
     // leave the solution where the read-backs expect it: prices, the smoothed psi, the barrier weight for the tenders
+    // (an explicit pair: lean sends all three through the pinned staging in one launch; blit copies from the vectors themselves,
+    //  and the low-order part only behind point_published)
+    const bool have_psi = (int)psi.size() == n;
     if (ctx->lean_io) {
         IoList l;
         std::memcpy(ctx->pin, nu.data(), n * sizeof(double));
         l.copy(ctx->nu_acc, pin_device(ctx, ctx->pin), n * sizeof(double));
-        if ((int)e.psi.size() == n) { std::memcpy(ctx->pin + 2 * (size_t)n, e.psi.data(), n * sizeof(double)); l.copy(ctx->psi_acc, pin_device(ctx, ctx->pin + 2 * (size_t)n), n * sizeof(double)); }
-        if (slo_on) { std::memcpy(ctx->pin + n, slo.data(), n * sizeof(double)); l.copy(ctx->sm_slo, pin_device(ctx, ctx->pin + n), n * sizeof(double)); }
+        if (have_psi) { std::memcpy(ctx->pin + 2 * (size_t)n, psi.data(), n * sizeof(double)); l.copy(ctx->psi_acc, pin_device(ctx, ctx->pin + 2 * (size_t)n), n * sizeof(double)); }
+        if (r.slo_on) { std::memcpy(ctx->pin + n, r.slo.data(), n * sizeof(double)); l.copy(ctx->sm_slo, pin_device(ctx, ctx->pin + n), n * sizeof(double)); }
         if ((rc = launch_io(ctx, l, false))) return rc;
     } else {
         HIP_TRY(ctx, hipMemcpyAsync(ctx->nu_acc, nu.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        if ((int)e.psi.size() == n) HIP_TRY(ctx, hipMemcpyAsync(ctx->psi_acc, e.psi.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        if (have_psi) HIP_TRY(ctx, hipMemcpyAsync(ctx->psi_acc, psi.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::memcpy(ctx->hsol, nu.data(), n * sizeof(double));
-    if ((int)e.psi.size() == n) std::memcpy(ctx->hsol + n, e.psi.data(), n * sizeof(double));
-    point_published(ctx, mu, slo_on);
-    if (slo_on && !ctx->lean_io) { HIP_TRY(ctx, hipMemcpyAsync(ctx->sm_slo, slo.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream)); HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); }
+    if (have_psi) std::memcpy(ctx->hsol + n, psi.data(), n * sizeof(double));
+    point_published(ctx, r.sched.mu, r.slo_on);
+    if (r.slo_on && !ctx->lean_io) { HIP_TRY(ctx, hipMemcpyAsync(ctx->sm_slo, r.slo.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream)); HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); }
     const auto t1 = std::chrono::steady_clock::now();
     float ms = 0.f;
     HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1));
     std::memset(out, 0, sizeof *out);
-    out->evals = evals; out->iters = steps; out->status = status;
+    out->evals = r.evals; out->iters = r.steps; out->status = r.status;
     out->n_ranks = ctx->n_ranks;
-    out->dual_value = dual; out->primal_value = primal; out->gap = gap; out->infeas = infeas;
+    out->dual_value = r.dual; out->primal_value = r.primal; out->gap = r.gap; out->infeas = r.infeas;
     out->wall_seconds = std::chrono::duration<double>(t1 - t0).count();
     out->device_seconds = ms * 1e-3;
-    out->pool_subproblems = (int64_t)evals * cfmm_pool_count(ctx);
-    out->barrier_mu = mu; out->newton_steps = steps; out->method = CFMM_METHOD_NEWTON;
-    if (status == CFMM_E_NUMERIC) return fail(ctx, CFMM_E_NUMERIC, "solve: non-finite value in the second-order iteration: %s", numeric_where);
+    out->pool_subproblems = (int64_t)r.evals * cfmm_pool_count(ctx);
+    out->barrier_mu = r.sched.mu; out->newton_steps = r.steps; out->method = CFMM_METHOD_NEWTON;
+    if (r.status == CFMM_E_NUMERIC) return fail(ctx, CFMM_E_NUMERIC, "solve: non-finite value in the second-order iteration: %s", r.numeric_where);
     return CFMM_OK;
+}
+
+// warm_mu: the barrier weight to continue from (that of the previous solve, when cfmm_solve continues from it), or 0
+int solve_newton(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out, int evals_before, double warm_mu)
+{
+    const char *why = "";
+    if (!newton_supported(ctx, &why)) return fail(ctx, CFMM_E_UNSUPPORTED, "solve: the second-order method cannot take this problem: %s", why);
+    int rc = settle(ctx); if (rc) return rc;             // (a first-order prelude may have left its tail in flight)
+    rc = smooth_buffers(ctx, true); if (rc) return rc;
+
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
+
+    NewtonRun r(ctx, o, evals_before);
+    if ((rc = newton_prologue(r, warm_mu))) return rc;
+    if (!newton_certify_exact(r, "at the start prices"))
+        for (;;) {
+            Phase ph = Phase::Go;
+            if ((rc = newton_evaluate(r))) return rc;
+            if ((rc = newton_certificates(r, ph))) return rc;
+            if (ph == Phase::Go && (rc = newton_direction(r, ph))) return rc;
+            if (ph == Phase::Go && (rc = newton_decrement(r, ph))) return rc;
+            if (ph == Phase::Go && (rc = newton_line_search(r, ph))) return rc;
+            if (ph == Phase::Go && (rc = newton_accept(r, ph))) return rc;
+            if (ph == Phase::Stop) break;
+        }
+    return newton_epilogue(r, out, t0);
 }
 
 }  // namespace
@@ -3278,20 +3271,12 @@ int cfmm_eval_dual(cfmm_ctx *ctx, const double *nu, double *arb_sum, double *psi
     std::memcpy(pin_nu, nu, n * sizeof(double));
     { double mx = 0.0; for (int j = 0; j < n; ++j) mx = std::max(mx, nu[j]); ctx->nu_max = mx; }
     if (ctx->det && sharded(ctx)) { int rc = refresh_global_counts(ctx); if (rc) return rc; }      // (the fixed-point exponent is a global quantity)
-    const bool lean = ctx->lean_io;
-    if (lean) {                                  // prices down, accumulators zeroed: one launch (handoff.hpp)
-        IoList l;
-        l.copy(ctx->nu, pin_device(ctx, pin_nu), n * sizeof(double));
-        l.zero(ctx->nu + n, sizeof(double));
-        l.zero(ctx->acc, (size_t)ctx->nslices * acc_stride(n) * sizeof(double));
-        if (ctx->det) l.zero(ctx->acc_l, 6 * (size_t)n * sizeof(unsigned long long));
-        int rc = launch_io(ctx, l, false); if (rc) return rc;
-    } else {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->nu, pin_nu, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->nu + n, 0, sizeof(double), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->acc, 0, (size_t)ctx->nslices * acc_stride(n) * sizeof(double), ctx->stream));
-        if (ctx->det) HIP_TRY(ctx, hipMemsetAsync(ctx->acc_l, 0, 6 * (size_t)n * sizeof(unsigned long long), ctx->stream));
-    }
+    HandOff in(ctx), back(ctx);                  // prices down, accumulators zeroed: one launch (handoff.hpp)
+    in.down(ctx->nu, pin_nu, n * sizeof(double));
+    in.zero(ctx->nu + n, sizeof(double));
+    in.zero(ctx->acc, (size_t)ctx->nslices * acc_stride(n) * sizeof(double));
+    if (ctx->det) in.zero(ctx->acc_l, 6 * (size_t)n * sizeof(unsigned long long));
+    { int rc = in.run(false); if (rc) return rc; }
     if (diag) launch_all_evals<true>(ctx); else launch_all_evals<false>(ctx);
     if (ctx->det) { int rc = det_finish(ctx, ctx->acc, ctx->nu, diag != nullptr); if (rc) return rc; }
     else hipLaunchKernelGGL(fold_kernel, dim3((len + 255) / 256), dim3(256), 0, ctx->stream, ctx->acc, n, ctx->nslices, 1, (const DevState *)nullptr);
@@ -3299,17 +3284,9 @@ int cfmm_eval_dual(cfmm_ctx *ctx, const double *nu, double *arb_sum, double *psi
     if (sharded(ctx) && !ctx->det) {            // pool-sharded (a communicator of one rank runs the same path)
         int rc = all_reduce(ctx, ctx->acc, (size_t)len, NCCL_FLOAT64, NCCL_SUM); if (rc) return rc;
     }
-    if (lean) {                                  // the folded slice up, then zeroed (same element -> thread mapping), + flag: one launch
-        IoList p;
-        p.copy(pin_device(ctx, pin_acc), ctx->acc, len * sizeof(double));
-        p.zero(ctx->acc, (size_t)len * sizeof(double));
-        int rc = launch_io(ctx, p, true); if (rc) return rc;
-        if ((rc = wait_io(ctx))) return rc;
-    } else {
-        HIP_TRY(ctx, hipMemcpyAsync(pin_acc, ctx->acc, len * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->acc, 0, (size_t)len * sizeof(double), ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    back.up(pin_acc, ctx->acc, len * sizeof(double));      // the folded slice up, then zeroed (same element -> thread mapping), + flag: one launch
+    back.zero(ctx->acc, (size_t)len * sizeof(double));
+    { int rc = back.run(true); if (rc) return rc; }
     if (psi) std::memcpy(psi, pin_acc, n * sizeof(double));
     if (arb_sum) *arb_sum = pin_acc[acc_arb(n)];
     if (diag) std::memcpy(diag, pin_acc + acc_diag(n), n * sizeof(double));

@@ -536,3 +536,37 @@ def test_second_order_solves_of_processes_sharing_the_device(tmp_path):
     for q, o in zip(procs, outs):
         assert q.returncode == 0, o[-2000:]
         assert "BAD []" in o, o[-2000:]
+
+
+def _path_record_cases():
+    import json
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if os.path.join(root, "tools") not in sys.path:
+        sys.path.insert(0, os.path.join(root, "tools"))
+    import newton_path_records
+    with open(os.path.join(root, "tests", "golden", "newton_path_records.json")) as f:
+        want = json.load(f)
+    cases = dict(newton_path_records.cases())
+    assert sorted(cases) == sorted(want)
+    return [(name, cases[name], want[name]) for name in sorted(want)]
+
+
+@pytest.mark.parametrize("name,run,want", [pytest.param(*c, id=c[0]) for c in _path_record_cases()])
+def test_second_order_path_takes_the_recorded_branches(name, run, want, monkeypatch):
+    """tools/newton_path_records.py: explicit second-order solves of the shipped instances, small random ones, the mixed network, config 5
+    at a tenth (cold, and warm from its own point), tokens no pool lists, an unsellable token, a no-arbitrage network from nu = c and
+    from perturbed prices, a log utility, a table network, a capped solve and three fuzz seeds -- under both hand-off modes.  The golden
+    file holds what the build BEFORE solve_newton was divided into rules (newton_rules.hpp) and phases recorded in three agreeing runs:
+    the status, the steps, the evaluations and the chord steps are those exactly, the final barrier weight to 1e-12 and the value to 1e-9
+    relative (run-to-run order of the evaluation's fp64 atomics).  Between them the instances reach a chord step, a refused one, a
+    diagonal shift, the low-order regime, a forced shrink, both exact certificates and the ends "stalled" and "out of steps"."""
+    for io in ("lean", "blit"):
+        monkeypatch.setenv("CFMM_NEWTON_IO", io)
+        got, _ = run()
+        w = want[io]
+        print(name, io, got, w)
+        for k in ("status", "newton_steps", "evals", "chord_steps"):
+            assert got[k] == w[k], (name, io, k, got, w)
+        assert abs(got["barrier_mu"] - w["barrier_mu"]) <= 1e-12 * abs(w["barrier_mu"]), (name, io, got, w)
+        assert abs(got["value"] - w["value"]) <= 1e-9 * abs(w["value"]), (name, io, got, w)

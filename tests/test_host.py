@@ -554,6 +554,274 @@ int main()
     assert {l.split()[4] for l in got} == {"Tiny", "Eager", "RingChunks", "Chunks"}
 
 
+def _newton_rules_program(tmp_path, name, body):
+    """a stand-alone HOST program over csrc/newton_rules.hpp (nothing of HIP in it): compiled -Wall -Werror, run, its output lines"""
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc missing")
+    src = tmp_path / f"{name}.cpp"
+    src.write_text('#include "newton_rules.hpp"\n#include <cstdio>\n#include <vector>\nusing namespace newton;\n'
+                   'inline void row(const char *k, const double *v, int n) { printf("%s", k); for (int i = 0; i < n; ++i) printf(" %.17g", v[i]); printf("\\n"); }\n'
+                   "int main()\n{\n" + body + "\n    return 0;\n}\n")
+    exe = tmp_path / name
+    r = subprocess.run([hipcc, "-O1", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "cfmm-routing-code_amd", "csrc"), str(src), "-o", str(exe)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return subprocess.run([str(exe)], capture_output=True, text=True, timeout=60).stdout.strip().splitlines()
+
+
+def _same_numbers(got, want, rel=1e-15):
+    got = [float(x) for x in got]
+    assert len(got) == len(want), (got, want)
+    for g, w in zip(got, want):
+        assert g == w or abs(g - w) <= rel * abs(w), (g, w, got, want)
+
+
+def test_second_order_chord_rule_over_every_combination_of_its_facts(tmp_path):
+    """csrc/newton_rules.hpp: chord_allowed -- may a step reuse the factor the device holds.  One rule for "this step" and for "the step
+    behind this trial": every combination of its boolean facts, the run of chord steps at 0, one under and at its cap, the move either
+    side of 1e-10.  Against the rule restated from the design: a valid factor, made at this weight, behind a full step, outside the
+    low-order regime, a move above 1e-10, not refused since, the run under its cap, no diagonal shift, the inverse factor kept."""
+    import itertools
+    bools = ["fac_valid", "same_weight", "full_step", "slo", "chord_bad", "shifted", "inverse_factor"]
+    chord_max, runs, moves = 3, (0, 2, 3), (0.99e-10, 1.01e-10)
+    got = _newton_rules_program(tmp_path, "chord", r'''
+    const int runs[] = {%s}; const double moves[] = {%s};
+    for (unsigned m = 0; m < (1u << %d); ++m) for (int run : runs) for (double mv : moves) {
+        ChordFacts f;
+        f.fac_valid = m & 1u; f.fac_mu = 1e-5; f.mu = (m >> 1) & 1u ? 1e-5 : 1e-6; f.full_step = (m >> 2) & 1u; f.slo = (m >> 3) & 1u;
+        f.chord_bad = (m >> 4) & 1u; f.reg = (m >> 5) & 1u ? 1e-12 : 0.0; f.inverse_factor = (m >> 6) & 1u;
+        f.chord_run = run; f.chord_max = %d; f.move = mv;
+        printf("%%u %%d %%.17g %%d\n", m, run, mv, (int)chord_allowed(f));
+    }''' % (", ".join(map(str, runs)), ", ".join(repr(x) for x in moves), len(bools), chord_max))
+    want = []
+    for m in range(1 << len(bools)):
+        for run, mv in itertools.product(runs, moves):
+            f = {b: bool((m >> i) & 1) for i, b in enumerate(bools)}
+            ok = (f["fac_valid"] and f["same_weight"] and f["full_step"] and not f["slo"] and mv > 1e-10 and not f["chord_bad"]
+                  and run < chord_max and not f["shifted"] and f["inverse_factor"])
+            want.append((m, run, mv, int(ok)))
+    assert len(got) == len(want) == (1 << len(bools)) * 6
+    for g, w in zip(got, want):
+        g = g.split()
+        assert (int(g[0]), int(g[1]), float(g[2]), int(g[3])) == w, (g, w)
+    assert sum(w[3] for w in want) == 2          # (one combination of the booleans, the two runs under the cap, the larger move)
+
+
+def test_second_order_schedule_rules_either_side_of_their_thresholds(tmp_path):
+    """csrc/newton_rules.hpp: the barrier schedule (first weight, when the exact evaluation is due, the final weight, "the weight stays",
+    the shrink behind an accepted step, the stall counter with its forced shrinks, the diagonal shift), the chord direction's test and
+    the line search's acceptance -- each at values either side of its threshold, against the rules restated from the design."""
+    lo, hi = 1.0 - 1e-9, 1.0 + 1e-9
+    tol = 1e-7
+    calls, want = [], []
+
+    def call(expr, value):
+        calls.append(f'    {{ const double v[] = {{(double)({expr})}}; row("r", v, 1); }}')
+        want.append(float(value))
+    # the first weight: 0.1 |dual| / nbar, no barrier terms counting as one; a warm start caps it at a multiple of the last weight
+    for dual, nbar, warm in ((-40.0, 8, 0.0), (0.0, 8, 0.0), (3.0, 0, 0.0), (3.0, 8, 1e-6), (3.0, 8, 1.0)):
+        mu = 0.1 * max(abs(dual), 1e-300) / max(nbar, 1)
+        call(f"first_weight(0.1, {dual!r}, {nbar}, {warm!r}, 1e3)", min(mu, 1e3 * warm) if warm > 0 else mu)
+    for dual in (0.3, -40.0):
+        s = max(1.0, abs(dual))
+        for f in (lo, hi):
+            call(f"weight_is_final({0.5 * tol * s * f!r}, {dual!r}, {tol!r})", 0.5 * tol * s * f <= 0.5 * tol * s)
+            for steps in (0, 1):
+                call(f"exact_due({steps}, {10 * tol * s * f!r}, {dual!r}, 0.0, {tol!r}, {tol!r})", steps == 0 or 10 * tol * s * f <= 10 * tol * s)
+                call(f"exact_due({steps}, 0.0, {dual!r}, {10 * tol * f!r}, {tol!r}, {tol!r})", steps == 0 or 10 * tol * f <= 10 * tol)
+    mu, nbar = 3e-6, 7
+    for final in (False, True):
+        for dec in (10 * mu * nbar * lo, 10 * mu * nbar * hi, 1e-3 * mu * nbar * lo, 1e-3 * mu * nbar * hi):
+            stays = final or not dec < 10 * mu * nbar
+            call(f"weight_stays({int(final)}, {dec!r}, {mu!r}, {nbar})", stays)
+            for full in (False, True):
+                call(f"weight_shrinks({int(final)}, {dec!r}, {mu!r}, {nbar}, {int(full)})", not stays and (full or dec < 1e-3 * mu * nbar))
+    # the stall counter at the final weight: (best infeasibility, stalled, forced shrinks) before -> after, the forced shrink, "stalled"
+    gmu = -25.0
+    for best, stalled, forced, infeas, dec, gap in (
+            (1e-3, 2, 0, 0.5e-3 * lo, 1.0, 1.0), (1e-3, 2, 0, 0.5e-3 * hi, 1.0, 1.0),                       # halves the best: counter reset
+            (1e-9, 1, 0, 1e-9, 25e-13 * hi, 2 * tol), (1e-9, 1, 0, 1e-9, 25e-13 * lo, 2 * tol),            # decrement at rounding level or not
+            (1e-9, 1, 2, 1e-9, 1e-14, tol * hi), (1e-9, 1, 2, 1e-9, 1e-14, tol * lo), (1e-9, 1, 3, 1e-9, 1e-14, 2 * tol),
+            (2 * tol, 1, 0, tol * hi, 1e-14, 2 * tol), (2 * tol, 1, 0, tol * lo, 1e-14, 2 * tol), (1e-9, 3, 3, 1e-9, 1e-14, -2 * tol)):
+        calls.append(f"    {{ Schedule sc; sc.best_infeas = {best!r}; sc.stalled = {stalled}; sc.forced_shrinks = {forced};\n"
+                     f"      const bool end = final_weight_stalls(sc, {infeas!r}, {dec!r}, {gmu!r}, {gap!r}, {tol!r}, {tol!r});\n"
+                     f'      const double v[] = {{(double)end, sc.best_infeas, (double)sc.stalled, (double)sc.forced_shrinks, (double)sc.shrink_now}}; row("s", v, 5); }}')
+        shrink = False
+        if infeas < 0.5 * best:
+            best, stalled = infeas, 0
+        elif dec <= 1e-13 * max(1.0, abs(gmu)):
+            if infeas <= tol and abs(gap) > tol and forced < 3:
+                shrink, forced = True, forced + 1
+            else:
+                stalled += 1
+        want.append((float(stalled >= 4), best, float(stalled), float(forced), float(shrink)))
+    # the diagonal shift: 1e-12 of the largest entry at first, x 100 per further refusal, out of range at 1e300; x 0.1 per step taken
+    for reg, md in ((0.0, 5.0), (0.0, 0.0), (1e-6, 5.0), (1e299, 5.0)):
+        calls.append(f'    {{ Schedule sc; sc.reg = {reg!r}; const bool ok = raise_shift(sc, {md!r}); const double v[] = {{(double)ok, sc.reg}}; row("s", v, 2); }}')
+        new = 1e-12 * max(md, 1e-300) if reg == 0.0 else reg * 100.0
+        want.append((float(new < 1e300), new))
+    for reg in (1e-4, 0.0):
+        calls.append(f'    {{ Schedule sc; sc.reg = {reg!r}; relax_shift(sc); const double v[] = {{sc.reg}}; row("s", v, 1); }}')
+        want.append((0.1 * reg if reg > 0 else 0.0,))
+    dec_prev = 4e-3
+    for fin, dc in ((1, 1e-2 * dec_prev * lo), (1, 1e-2 * dec_prev * hi), (1, 0.0), (1, -1e-9), (0, 1e-2 * dec_prev * lo), (1, float("nan"))):
+        call(f"chord_direction_serves({fin}, {'NAN' if dc != dc else repr(dc)}, {dec_prev!r})", bool(fin) and dc > 0.0 and dc <= 1e-2 * dec_prev)
+    armijo, gd = 1e-4, -2.0
+    bound = gmu + armijo * gd + 2e-15 * abs(gmu)
+    for g2, dec in ((bound, 1.0), (bound + 1e-14, 1.0), (bound + 1.0, 1e-13 * abs(gmu) * lo), (bound + 1.0, 1e-13 * abs(gmu) * hi)):
+        call(f"trial_accepted({g2!r}, {gmu!r}, {armijo!r}, {gd!r}, {dec!r})", g2 <= bound or dec <= 1e-13 * abs(gmu))
+    for max_step, dmax in ((2.0, 1.0), (2.0, 8.0), (2.0, 0.0)):
+        call(f"first_step_length({max_step!r}, {dmax!r})", min(1.0, max_step / max(dmax, 1e-300)))
+    got = _newton_rules_program(tmp_path, "schedule", "\n".join(calls))
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        _same_numbers(g.split()[1:], w if isinstance(w, tuple) else (w,))
+
+
+def test_second_order_token_rules_on_one_token_of_each_kind(tmp_path):
+    """csrc/newton_rules.hpp on a 7-token vector -- GE with c > 0, GE with c = 0 that a pool lists (a barrier token), the same unlisted
+    with h = 0 (flat: pinned, no barrier term), EQ, FREE, ULOG, UQUAD: the prologue's token pass, the start dual (the pools' value plus
+    the terms in token order), assemble, the certificate sums (1e-15 relative against the same sums restated here, in token order), the
+    exact certificate (refused because of the table entries, accepted with them replaced), and the line search's trial point in both
+    regimes with token 0 on its lower bound."""
+    import math
+    GE, EQ, FREE, ULOG, UQUAD = 0, 1, 2, 3, 4
+    ct = [GE, GE, GE, EQ, FREE, ULOG, UQUAD]
+    c = [1.2, 0.0, 0.0, 0.9, 1.1, 0.8, 1.3]
+    h = [0.3, 0.5, 0.0, 0.4, 0.1, 2.0, 5.0]
+    pools = [1, 1, 0, 1, 1, 1, 1]
+    nu0 = [1.0, 0.7, 0.6, 0.95, 3.0, 0.5, 1.25]            # (token 0 starts under its bound c: projected; the FREE token goes to c)
+    psi = [-0.2, -0.45, 0.0, -0.41, 0.3, -1.5, 0.2]
+    n, mu, value, arb, floor = 7, 3e-3, 0.37, 0.41, 1e-12 * 5e4
+    d = [-0.3, 0.2, 0.5, -0.1, 0.4, 0.05, -0.25]
+    vec = lambda name, a, t="double": f"    const {t} {name}[] = {{{', '.join(repr(x) for x in a)}}};"
+    body = "\n".join([vec("ct", ct, "int"), vec("c", c), vec("h", h), vec("pools", pools, "char"), vec("psi", psi), vec("d", d), vec("nu0", nu0)]) + r'''
+    const int n = 7; const double mu = %r, value = %r, arb = %r;
+    std::vector<double> nu(nu0, nu0 + n), lob(n), s(n), G(n), Hd(n), rhs(n), slo(n, 0.0), s2(n), nu2(n), slo2(n);
+    std::vector<int> mask(n), pin(n); std::vector<char> listed(n);
+    long long nb = 0;
+    double v[8];
+    v[0] = token_pass(n, c, h, ct, pools, nu.data(), listed.data(), mask.data(), lob.data(), s.data(), &nb); v[1] = (double)nb; row("pass", v, 2);
+    for (int j = 0; j < n; ++j) v[j] = listed[j]; row("listed", v, n);
+    for (int j = 0; j < n; ++j) v[j] = mask[j]; row("mask", v, n);
+    row("lob", lob.data(), n); row("s", s.data(), n); row("nu", nu.data(), n);
+    { double cz[] = {1.2, 0.0, 0.0, 0.9, 0.0, 0.8, 1.3}; std::vector<double> p(nu0, nu0 + n);
+      v[0] = token_pass(n, cz, h, ct, pools, p.data(), listed.data(), mask.data(), lob.data(), s.data(), &nb); row("unbounded", v, 1);
+      token_pass(n, c, h, ct, pools, p.data(), listed.data(), mask.data(), lob.data(), s.data(), &nb); }
+    Tokens tk; tk.n = n; tk.c = c; tk.h = h; tk.ctype = ct; tk.listed = listed.data(); tk.mask = mask.data(); tk.lob = lob.data(); tk.nbar = 4 + nb; tk.infeas_floor = %r;
+    for (int j = 0; j < n; ++j) v[j] = tk.barrier_token(j); row("barrier", v, n);
+    v[0] = start_dual(tk, nu.data(), arb); row("start_dual", v, 1);
+    v[0] = assemble(tk, nu.data(), psi, value, mu, G.data(), Hd.data()); row("g", v, 1); row("G", G.data(), n); row("Hd", Hd.data(), n);
+    v[0] = assemble(tk, nu.data(), psi, value, mu, nullptr, nullptr); row("g_only", v, 1);
+    { const Certificate k = certificate(tk, nu.data(), psi); const double w[] = {k.lin, k.primal, k.cs, k.viol, k.scale, k.infeas(tk)}; row("cert", w, 6); }
+    { const ExactCertificate x = exact_certificate(tk, nu.data(), psi, arb, 1e-6, 1e-6); v[0] = x.holds; row("exact_table", v, 1); }
+    { const int ct2[] = {0, 0, 0, 1, 2, 0, 0}; Tokens t2 = tk; t2.ctype = ct2;
+      double px[7]; for (int j = 0; j < n; ++j) px[j] = -h[j];
+      ExactCertificate x = exact_certificate(t2, nu.data(), px, arb, 1e-6, 1e-6); const double w[] = {(double)x.holds, x.dual, x.gap, x.infeas, x.primal}; row("exact_holds", w, 5);
+      x = exact_certificate(t2, nu.data(), psi, arb, 1e-6, 1e-6); const double w2[] = {(double)x.holds, x.dual, x.gap, x.infeas, x.primal}; row("exact_fails", w2, 5);
+      t2.ctype = ct; x = exact_certificate(t2, nu.data(), px, arb, 1e-6, 1e-6); v[0] = x.holds; row("exact_table_feasible", v, 1); }
+    G[0] = 0.25;                                   // (pushing token 0, on its bound, further down: pinned by the projection)
+    pin_and_right_hand_side(tk, s.data(), slo.data(), 1e-9, G.data(), Hd.data(), pin.data(), rhs.data());
+    for (int j = 0; j < n; ++j) v[j] = pin[j]; row("pin", v, n); row("rhs", rhs.data(), n); row("Hd_shifted", Hd.data(), n);
+    G[0] = 0.25;
+    for (int pass = 0; pass < 3; ++pass) {
+        if (pass == 2) slo[1] = 2e-10;             // (a low-order part already too large for the regime)
+        const Trial tr = trial_point(tk, s.data(), nu.data(), slo.data(), d, G.data(), pass == 0 ? 0.5 : 1e-13, 0.5, pass != 0, s2.data(), nu2.data(), slo2.data());
+        v[0] = tr.small; v[1] = tr.gd; row("trial", v, 2); row("s2", s2.data(), n); row("nu2", nu2.data(), n); row("slo2", slo2.data(), n);
+    }
+    { std::vector<double> st(s); v[0] = price_collapsed(tk, s.data(), st.data()); st[1] = s[1] + 60.5; v[1] = price_collapsed(tk, s.data(), st.data());
+      st[1] = s[1]; st[2] = s[2] + 61.0; v[2] = price_collapsed(tk, s.data(), st.data()); row("collapsed", v, 3); }''' % (mu, value, arb, floor)
+    got = {}
+    for line in _newton_rules_program(tmp_path, "tokens", body):
+        k, *vals = line.split()
+        got.setdefault(k, []).append(vals)
+
+    # ---- the same, restated
+    listed = [not (ct[j] < ULOG and not pools[j] and h[j] == 0.0) for j in range(n)]
+    mask = [ct[j] == FREE or not listed[j] for j in range(n)]
+    lob = [math.log(c[j]) if ct[j] == GE and c[j] > 0 else -math.inf for j in range(n)]
+    barrier = [ct[j] == GE and not c[j] > 0 and listed[j] for j in range(n)]
+    s = [math.log(c[j]) if ct[j] == FREE else max(math.log(nu0[j]), lob[j]) for j in range(n)]
+    nu = [math.exp(x) for x in s]
+    assert [float(x) for x in got["pass"][0]] == [-1.0, 1.0] and [float(x) for x in got["unbounded"][0]] == [4.0]
+    assert [float(x) for x in got["listed"][0]] == [1, 1, 0, 1, 1, 1, 1] == [float(x) for x in listed]
+    assert [float(x) for x in got["mask"][0]] == [0, 0, 1, 0, 1, 0, 0] == [float(x) for x in mask]
+    assert [float(x) for x in got["barrier"][0]] == [0, 1, 0, 0, 0, 0, 0] == [float(x) for x in barrier]
+    _same_numbers(got["lob"][0], lob); _same_numbers(got["s"][0], s); _same_numbers(got["nu"][0], nu)
+    assert s[0] == lob[0] and nu[4] == math.exp(math.log(c[4]))
+
+    def table(j, p, q):                  # (P*, conjugate, utility of q, violation, nu^2 ubar'')
+        if ct[j] == ULOG:
+            return c[j] / p - h[j], c[j] * math.log(c[j] / p) - c[j] + p * h[j], c[j] * math.log(max(q + h[j], 1e-300)), max(-(q + h[j]), 0.0), c[j]
+        return h[j] * (c[j] - p), 0.5 * h[j] * (c[j] - p) * (c[j] - p), c[j] * q - 0.5 * q * q / h[j], 0.0, h[j] * p * p
+    dual = arb
+    for j in range(n):
+        dual += table(j, nu[j], 0.0)[1] if ct[j] >= ULOG else (nu[j] - c[j]) * h[j]
+    _same_numbers(got["start_dual"][0], [dual])
+    g, G, Hd = value, [0.0] * n, [0.0] * n
+    for j in range(n):
+        if ct[j] >= ULOG:
+            pstar, ubar, _, _, d2 = table(j, nu[j], psi[j])
+            g += ubar; Gj = nu[j] * (psi[j] - pstar); hj = d2
+        else:
+            g += (nu[j] - c[j]) * h[j]; Gj = nu[j] * (psi[j] + h[j]); hj = 0.0
+        Hd[j] = max(Gj, 0.0) + hj
+        if barrier[j]:
+            g -= mu * math.log(nu[j]); Gj -= mu
+        G[j] = 0.0 if mask[j] else Gj
+    _same_numbers(got["g"][0], [g]); _same_numbers(got["g_only"][0], [g]); _same_numbers(got["G"][0], G); _same_numbers(got["Hd"][0], Hd)
+
+    def sums(kinds, q):
+        lin = primal = cs = viol = scale = 0.0
+        for j in range(n):
+            if kinds[j] >= ULOG:
+                pstar, ubar, uval, vio, _ = table(j, nu[j], q[j])
+                lin += ubar; primal += uval; cs += ubar + nu[j] * q[j] - uval
+                viol = max(viol, vio); scale = max(scale, abs(q[j]), abs(pstar))
+                continue
+            r = q[j] + h[j]
+            lin += (nu[j] - c[j]) * h[j]; primal += c[j] * q[j]; cs += (nu[j] - c[j]) * r
+            viol = max(viol, max(-r, 0.0) if kinds[j] == GE else (abs(r) if kinds[j] == EQ else 0.0))
+            scale = max(scale, abs(q[j]), abs(h[j]))
+        return lin, primal, cs, viol, scale, viol / max(scale, floor, 1e-300)
+    _same_numbers(got["cert"][0], sums(ct, psi))
+    assert float(got["exact_table"][0][0]) == 0.0 and float(got["exact_table_feasible"][0][0]) == 0.0     # (the table entries alone refuse it)
+    ct2, px = [GE, GE, GE, EQ, FREE, GE, GE], [-x for x in h]
+    for key, q in (("exact_holds", px), ("exact_fails", psi)):
+        lin, primal, cs, viol, scale, infeas = sums(ct2, q)
+        d0 = lin + arb
+        gap0 = abs(cs) / max(1.0, abs(d0))
+        _same_numbers(got[key][0], [float(gap0 <= 1e-6 and infeas <= 1e-6), d0, gap0, infeas, primal])
+    assert float(got["exact_holds"][0][0]) == 1.0 and float(got["exact_fails"][0][0]) == 0.0
+    # pinned: the masked tokens, and token 0 -- on its bound, the gradient pushing it down
+    G[0] = 0.25
+    pin = [bool(mask[j] or (s[j] <= lob[j] + 1e-13 * max(1.0, abs(lob[j])) and G[j] > 0.0)) for j in range(n)]
+    assert pin == [True, False, True, False, True, False, False]
+    Gp = [0.0 if pin[j] else G[j] for j in range(n)]
+    _same_numbers(got["pin"][0], [float(x) for x in pin]); _same_numbers(got["rhs"][0], [-x for x in Gp]); _same_numbers(got["Hd_shifted"][0], [x + 1e-9 for x in Hd])
+    Gt = list(Gp); Gt[0] = 0.25
+    slo = [0.0] * n
+    for i, (t, final_mu, want_small) in enumerate(((0.5, False, False), (1e-13, True, True), (1e-13, True, False))):
+        if i == 2:
+            slo[1] = 2e-10
+        small = final_mu and t * 0.5 < 1e-11 and max(abs(slo[j] + t * d[j]) for j in range(n)) < 1e-10
+        assert small == want_small
+        s2, nu2, slo2, gd = [0.0] * n, [0.0] * n, [0.0] * n, 0.0
+        for j in range(n):
+            if small:
+                s2[j], nu2[j], slo2[j] = s[j], nu[j], (0.0 if mask[j] else max(slo[j] + t * d[j], lob[j] - s[j]))
+            else:
+                s2[j] = max(s[j] + slo[j] + t * d[j], lob[j]); nu2[j] = nu[j] if mask[j] else math.exp(s2[j]); slo2[j] = 0.0
+            gd += Gt[j] * ((s2[j] + slo2[j]) - (s[j] + slo[j]))
+        _same_numbers(got["trial"][i], [float(small), gd])
+        _same_numbers(got["s2"][i], s2); _same_numbers(got["nu2"][i], nu2); _same_numbers(got["slo2"][i], slo2)
+        assert (s2[0] + slo2[0]) == lob[0] and nu2[2] == nu[2] and nu2[4] == nu[4]      # (the bound holds token 0; pinned prices stay)
+    assert [float(x) for x in got["collapsed"][0]] == [0.0, 1.0, 0.0]                  # (60 e-foldings under the start; a pinned token does not count)
+
+
 def test_switch_records_of_a_k_asset_constant_sum_pool_are_rooted_at_the_paying_leg():
     """cfmm/problem.py: _canonical_switches, _split_payers (round 6, pure functions of the records: every rank of a pool-sharded solve
     computes the same).  Three tokens tied for cheapest, found pair by pair in rounds whose cheapest token differed -- records (0, 3) and
