@@ -40,6 +40,16 @@ class Opts(C.Structure):
 
 
 METHODS = {"auto": 0, "lbfgs": 1, "newton": 2}
+FEE_MODES = {"pool": 0, "aside": 1}     # include/cfmm.h: CFMM_FEES_TO_POOL, CFMM_FEES_ASIDE
+
+
+class ApplyInfo(C.Structure):
+    """cfmm_apply_info: what cfmm_apply_trades moved, or the first pool it refused"""
+    _fields_ = [("pools_moved", C.c_int64), ("pools_refused", C.c_int64), ("first_family", C.c_int32), ("first_kind", C.c_int32),
+                ("first_k", C.c_int32), ("_pad", C.c_int32), ("first_pos", C.c_int64), ("max_reserve", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "_pad"}
 
 
 class Stats(C.Structure):
@@ -61,7 +71,7 @@ assert _STATS_STRUCT.size == C.sizeof(Stats)
 
 def build(force=False):
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp", "update.hpp", "solve_plan.hpp", "newton_rules.hpp")]
+    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp", "update.hpp", "apply.hpp", "solve_plan.hpp", "newton_rules.hpp")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "cfmm.h"))
     if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _CSRC, "-s"])
@@ -71,7 +81,8 @@ def build(force=False):
 _lib = None
 
 SYMBOLS = ["cfmm_create", "cfmm_clone", "cfmm_destroy", "cfmm_last_error", "cfmm_backend", "cfmm_default_opts",
-           "cfmm_upload_pools2", "cfmm_upload_poolsN", "cfmm_upload_poolsG", "cfmm_update_pools2", "cfmm_update_poolsN", "cfmm_update_poolsG", "cfmm_set_pool_flags", "cfmm_set_pool_flagsG", "cfmm_set_utility",
+           "cfmm_upload_pools2", "cfmm_upload_poolsN", "cfmm_upload_poolsG", "cfmm_update_pools2", "cfmm_update_poolsN", "cfmm_update_poolsG",
+           "cfmm_apply_trades", "cfmm_get_reserves2", "cfmm_get_reservesN", "cfmm_get_reservesG", "cfmm_apply_timers", "cfmm_set_pool_flags", "cfmm_set_pool_flagsG", "cfmm_set_utility",
            "cfmm_set_ties", "cfmm_set_deterministic", "cfmm_debug_eval_limbs", "cfmm_eval_dual", "cfmm_eval_smooth", "cfmm_debug_cholesky", "cfmm_debug_cholesky_apply", "cfmm_time_xcd_handoff", "cfmm_solve", "cfmm_solve_batch", "cfmm_eval_dual_batch", "cfmm_batch_capacity", "cfmm_solve_sweep", "cfmm_get_nu", "cfmm_set_nu", "cfmm_get_psi",
            "cfmm_get_solution", "cfmm_get_trades2", "cfmm_get_tradesN", "cfmm_get_tradesG", "cfmm_comm_unique_id", "cfmm_comm_init",
            "cfmm_oneshot_export", "cfmm_oneshot_import", "cfmm_oneshot_attach", "cfmm_oneshot_mailbox", "cfmm_oneshot_enable",
@@ -100,6 +111,11 @@ def lib():
     L.cfmm_update_pools2.argtypes = [vp, C.c_int, C.c_int64, ip, dp, dp, dp]
     L.cfmm_update_poolsN.argtypes = [vp, C.c_int, C.c_int64, ip, dp]
     L.cfmm_update_poolsG.argtypes = [vp, C.c_int, C.c_int, C.c_int64, ip, dp, dp]
+    L.cfmm_apply_trades.argtypes = [vp, C.c_int, C.POINTER(ApplyInfo)]
+    L.cfmm_get_reserves2.argtypes = [vp, C.c_int, dp, dp, dp]
+    L.cfmm_get_reservesN.argtypes = [vp, C.c_int, dp]
+    L.cfmm_get_reservesG.argtypes = [vp, C.c_int, C.c_int, dp, dp]
+    L.cfmm_apply_timers.argtypes = [vp, C.c_int, dp]
     L.cfmm_set_pool_flags.argtypes = [vp, C.c_int, ip]
     L.cfmm_set_pool_flagsG.argtypes = [vp, C.c_int, ip]
     L.cfmm_set_utility.argtypes = [vp, dp, dp, ip]
@@ -252,6 +268,41 @@ class Context:
         if cnt != len(pos) or (param is not None and len(param) != cnt):
             raise CfmmError(f"update_poolsG: {len(pos)} positions but {cnt} reserve columns" + ("" if param is None else f", {len(param)} parameters"))
         self._chk(self.L.cfmm_update_poolsG(self.h, kind, k, cnt, _i(pos), _d(R), _d(param)))
+
+    def apply_trades(self, fee_mode=0, check=True):
+        """commit the tenders cfmm_get_trades* would return now to the resident pools (cfmm_apply_trades); fee_mode: FEE_MODES or its
+        value.  Returns the info record as a dict; check=False: (return code, dict) instead of raising on a refusal"""
+        info = ApplyInfo()
+        rc = self.L.cfmm_apply_trades(self.h, FEE_MODES.get(fee_mode, fee_mode), C.byref(info))
+        if not check:
+            return int(rc), info.asdict()
+        self._chk(rc)
+        return info.asdict()
+
+    def apply_timers(self, on=True):
+        """(seconds of the checking pass, of the writing pass) of the last apply_trades, by HIP events; switches the events on / off"""
+        out = np.zeros(2)
+        self._chk(self.L.cfmm_apply_timers(self.h, 1 if on else 0, _d(out)))
+        return float(out[0]), float(out[1])
+
+    def get_reserves2(self, kind, m, with_param=False):
+        """resident reserves (Ra, Rb[, param]) of a two-asset bucket of m pools, in upload order"""
+        Ra = np.zeros(m); Rb = np.zeros(m); param = np.zeros(m) if with_param else None
+        if m:
+            self._chk(self.L.cfmm_get_reserves2(self.h, kind, _d(Ra), _d(Rb), _d(param)))
+        return (Ra, Rb, param) if with_param else (Ra, Rb)
+
+    def get_reservesN(self, k, m):
+        R = np.zeros((k, m))
+        if m:
+            self._chk(self.L.cfmm_get_reservesN(self.h, k, _d(R)))
+        return R
+
+    def get_reservesG(self, kind, k, m, with_param=False):
+        R = np.zeros((k, m)); param = np.zeros(m) if with_param else None
+        if m:
+            self._chk(self.L.cfmm_get_reservesG(self.h, kind, k, _d(R), _d(param)))
+        return (R, param) if with_param else R
 
     def set_pool_flags(self, kind, flags):
         flags = i32(flags)

@@ -244,6 +244,25 @@ def route_updates(net, where, pools, reserves, params=None):
     return out
 
 
+def post_trade_reserves(R, delta, lam, fee, fees="pool"):
+    """Reserves of pools after their tenders are executed: R' = (R + g delta) - lam, every operation individually rounded -- the
+    expression cfmm_apply_trades evaluates on the device (docs/apply_trades.md).  g = 1 with fees="pool" (the fee stays in the
+    reserves: Uniswap v2, Balancer, Curve), g = the pool's fee factor gamma with fees="aside" (the fee is collected outside the pool:
+    phi(R') = phi(R)).  R, delta, lam: [k][m] slot-major (or [m]); fee: [m].  Gross tenders (a leg that both receives and pays, as
+    after a second-order solve) are taken as they are, in this order."""
+    if fees not in _lib.FEE_MODES:
+        raise ValueError(f"fees {fees!r}: expected one of {sorted(_lib.FEE_MODES)}")
+    R, delta, lam = (np.asarray(a, dtype=np.float64) for a in (R, delta, lam))
+    g = 1.0 if fees == "pool" else np.asarray(fee, dtype=np.float64)
+    return (R + g * delta) - lam
+
+
+def apply_path(theta, dev_ties, sharded):
+    """where Problem.apply_trades forms the new reserves: "device" (cfmm_apply_trades: no host leg) unless fills are held on the
+    host (`theta`: the Python kink loop's), price ties / tie flags sit on the device, or the pools are sharded -- then "host\""""
+    return "host" if (theta or dev_ties or sharded) else "device"
+
+
 def _bucket_of(net, key):
     """(bucket dict, 'two' | 'gn' | 'gk') of a bucket key as bucket_trades takes it"""
     if isinstance(key, str):
@@ -985,16 +1004,105 @@ class Problem:
             b["R"][:, pos] = R
         if param is not None:
             cur[pos] = param
-        # what was derived from the old reserves: start-price relations (and the start prices memoised on them), the largest reserve,
-        # the read-back caches -- of this Problem and of its clones, through the generation stamp on the network they share
+        self._reserves_changed()
+
+    def _reserves_changed(self):
+        """what was derived from the old reserves goes: start-price relations (and the start prices memoised on them), the largest
+        reserve, the read-back caches -- of this Problem and of its clones, through the generation stamp on the network they share"""
+        net = self._net
         for kk in ("_price_relations", "_potentials"):
-            self.net.pop(kk, None)
-        self.net["_generation"] = self.net.get("_generation", 0) + 1
+            net.pop(kk, None)
+        net["_generation"] = net.get("_generation", 0) + 1
         self._pools_seen()
+
+    # -- the router's own trades applied to the pools (include/cfmm.h: cfmm_apply_trades; docs/apply_trades.md) -----------------
+    @property
+    def net(self):
+        """the packed network; a host copy that apply_trades(sync_host=False) left behind the device is refreshed on first use"""
+        n = self._net
+        if n.get("_stale") and self.ctx is not None and self._uploaded:
+            self._refresh_net()
+        return n
+
+    @net.setter
+    def net(self, network):
+        self._net = network
+
+    def _apply_path(self):
+        return apply_path(self._theta, self._dev_ties, self._host is not None or self._comm is not None)
+
+    def bucket_reserves(self, key):
+        """resident reserves [k][m] (slot-major, upload order; k = 2 for the two-asset buckets) of one bucket, read back from the device"""
+        b, fam = _bucket_of(self._net, key)
+        ctx = self._ensure_ctx()
+        if fam == "two":
+            return np.stack(ctx.get_reserves2(KIND2[key], len(b["Ra"])))
+        if fam == "gn":
+            return ctx.get_reservesN(int(key), b["R"].shape[1])
+        return ctx.get_reservesG(_lib.POOLK[key[0]], key[1], b["R"].shape[1])
+
+    def reserves(self):
+        """{bucket key: resident reserves [k][m]} of every bucket, read back from the device (keys as bucket_trades takes them)"""
+        net = self._net
+        keys = [k for k in KIND2 if k in net] + list(net.get("gn", {})) + list(net.get("gk", {}))
+        return {key: self.bucket_reserves(key) for key in keys}
+
+    def _refresh_net(self):
+        net = self._net
+        net.pop("_stale", None)
+        for key, R in self.reserves().items():
+            b, fam = _bucket_of(net, key)
+            if fam == "two":
+                b["Ra"][:] = R[0]; b["Rb"][:] = R[1]
+            else:
+                b["R"][:] = R
+
+    def apply_trades(self, fees="pool", sync_host=True):
+        """Execute the route: every pool's tenders at the accepted prices (what deltas / lambdas / bucket_trades return now) are
+        committed to the resident reserves, R' = (R + g delta) - lam with g = 1 (fees="pool": the fee stays in the pool) or the pool's
+        gamma (fees="aside").  All or nothing: a pool that would be drained (a constant-sum pool traded at its vertex) raises ValueError
+        and neither the device nor self.net changes.  Sequential orders, each seeing the pools as the previous one left them:
+
+            for order in orders:
+                p.set_utility(order); p.solve(warm_start=True); p.apply_trades()
+
+        Without host-held fills, device ties or sharding the reserves move on the device (no host leg) and self.net is refreshed from
+        there -- at once, or with sync_host=False on its first use; otherwise they are formed here from the tenders, fills included, and
+        sent through update_bucket.  Returns the number of pools that moved."""
+        if fees not in _lib.FEE_MODES:
+            raise ValueError(f"fees {fees!r}: expected one of {sorted(_lib.FEE_MODES)}")
+        ctx = self._ensure_ctx()
+        self._pools_seen()
+        if self._apply_path() == "device":
+            rc, info = ctx.apply_trades(fees, check=False)
+            if rc == _lib.E_UNSUPPORTED and info["pools_refused"] > 0:
+                raise ValueError(ctx.L.cfmm_last_error(ctx.h).decode())
+            ctx._chk(rc)
+            self._net["_stale"] = True
+            self._reserves_changed()
+            if sync_host:
+                self._refresh_net()
+            return int(info["pools_moved"])
+        net = self.net
+        new = {}
+        for key, (d, l) in self._trades().items():          # (every bucket is checked before the first write)
+            b, fam = _bucket_of(net, key)
+            R = np.stack([b["Ra"], b["Rb"]]) if fam == "two" else b["R"]
+            Rn = post_trade_reserves(R, d, l, b["fee"], fees)
+            bad = ~(np.isfinite(Rn) & (Rn > 0)).all(axis=0)
+            if bad.any():
+                raise ValueError(f"bucket {key!r}: pool {int(np.flatnonzero(bad)[0])} would be left with a reserve that is not positive and finite; nothing was changed")
+            pos = np.flatnonzero(((d != 0) | (l != 0)).any(axis=0))
+            new[key] = (pos, np.ascontiguousarray(Rn[:, pos]))
+        sharded = self._host is not None or self._comm is not None
+        for key, (pos, Rn) in new.items():
+            if len(pos) or sharded:                          # (pool-sharded: every rank makes the call)
+                self.update_bucket(key, pos, Rn)
+        return int(sum(len(pos) for pos, _ in new.values()))
 
     def _pools_seen(self):
         """drop what was derived from reserves that an update through this Problem or a clone (they share self.net) has replaced"""
-        g = self.net.get("_generation", 0)
+        g = self._net.get("_generation", 0)
         if getattr(self, "_net_generation", 0) != g:
             self._net_generation = g
             self._rmax = None

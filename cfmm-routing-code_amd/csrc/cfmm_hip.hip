@@ -39,6 +39,7 @@
 #include "chol2.hpp"
 #include "phik.hpp"
 #include "update.hpp"
+#include "apply.hpp"
 #include "handoff.hpp"
 #include "solve_plan.hpp"
 #include "newton_rules.hpp"
@@ -156,6 +157,9 @@ struct Point {
     bool tr_ovr_valid = false;         // what cfmm_get_trades2 returns while set
 };
 
+// records of cfmm_apply_trades' first pass: one per slot of PoolStore::r2 | rn | rg[0] | rg[1]
+constexpr int APPLY_RECS = CFMM_POOL_KINDS2 + (CFMM_MAX_POOL_SIZE + 1) + CFMM_POOLK_KINDS * (CFMM_MAX_POOL_SIZE + 1);
+
 struct cfmm_ctx {
     int device = 0, n = 0, ng = 0;
     int cus = 256;
@@ -174,6 +178,12 @@ struct cfmm_ctx {
     int *flagsG[CFMM_MAX_POOL_SIZE + 1] = {};      // per-leg tie flags of the table's constant-sum buckets (cfmm_set_pool_flagsG), pool-major
     double *trade_buf = nullptr;       // grow-only scratch for cfmm_get_trades* (delta | lambda)
     size_t trade_cap = 0;
+    // cfmm_apply_trades (apply.hpp): one ApplyRec per bucket record on the device; pinned [2][APPLY_RECS]: their start values | read back
+    // (pieces of the two arenas below)
+    ApplyRec *apply_dev = nullptr, *apply_host = nullptr;
+    double *apply_ovr = nullptr; size_t apply_ovr_cap = 0;     // grow-only device copy of the kink loop's tenders (Point::tr_ovr)
+    bool apply_timed = false;          // cfmm_apply_timers: HIP events around each pass's launches
+    double apply_sec[2] = {0.0, 0.0};  // ... of the last apply: the pass that checks, the pass that writes
 
     // tokens / state (device)
     double *c = nullptr, *h = nullptr, *off = nullptr, *glo = nullptr, *ghi = nullptr;
@@ -2276,6 +2286,7 @@ int cfmm_create(int device, int n_tokens, cfmm_ctx **out)
         want(&ctx->st3, 3);
         want(&ctx->acc_l, 6 * (size_t)n + 4);
         want(&ctx->ts, 64 + 8 * 4096 + 2048);
+        want(&ctx->apply_dev, APPLY_RECS);
         size_t total = 0;
         for (auto &pc : pieces) total += (pc.bytes + 16 + 255) & ~(size_t)255;
         TRY_C(hipMalloc((void **)&ctx->dev_arena, total));
@@ -2283,10 +2294,11 @@ int cfmm_create(int device, int n_tokens, cfmm_ctx **out)
         size_t off = 0;
         for (auto &pc : pieces) { *pc.dst = ctx->dev_arena + off; off += (pc.bytes + 16 + 255) & ~(size_t)255; }
         ctx->util_span = (size_t)((char *)ctx->off - (char *)ctx->c);
-        const size_t hb[5] = {2 * sizeof(DevState), 6 * sizeof(DevState), 2 * (size_t)n * sizeof(double), (size_t)n * sizeof(double), ctx->util_span};
-        size_t ho[6] = {0, 0, 0, 0, 0, 0};
-        for (int q = 0; q < 5; ++q) ho[q + 1] = ho[q] + ((hb[q] + 255) & ~(size_t)255);
-        TRY_C(hipHostMalloc((void **)&ctx->host_arena, ho[5], hipHostMallocDefault));      // (pinned, host-cached, and reachable from the device through hipHostGetDevicePointer)
+        const size_t hb[6] = {2 * sizeof(DevState), 6 * sizeof(DevState), 2 * (size_t)n * sizeof(double), (size_t)n * sizeof(double), ctx->util_span,
+                              2 * APPLY_RECS * sizeof(ApplyRec)};
+        size_t ho[7] = {0, 0, 0, 0, 0, 0, 0};
+        for (int q = 0; q < 6; ++q) ho[q + 1] = ho[q] + ((hb[q] + 255) & ~(size_t)255);
+        TRY_C(hipHostMalloc((void **)&ctx->host_arena, ho[6], hipHostMallocDefault));      // (pinned, host-cached, and reachable from the device through hipHostGetDevicePointer)
         ctx->hst = (DevState *)(ctx->host_arena + ho[0]); ctx->hst3 = (DevState *)(ctx->host_arena + ho[1]);
         ctx->hsol = (double *)(ctx->host_arena + ho[2]); ctx->hnu0 = (double *)(ctx->host_arena + ho[3]);
         {
@@ -2296,6 +2308,8 @@ int cfmm_create(int device, int n_tokens, cfmm_ctx **out)
         }
         ctx->util_h = ctx->host_arena + ho[4];
         std::memset(ctx->util_h, 0, ctx->util_span);
+        ctx->apply_host = (ApplyRec *)(ctx->host_arena + ho[5]);
+        for (int q = 0; q < APPLY_RECS; ++q) ctx->apply_host[q] = ApplyRec{0ull, 0ull, ~0ull, 0ull};
     }
     lap("device + pinned arenas");
     TRY_C(hipHostMalloc((void **)&ctx->hstat_h, 64 + ITER_HRING * sizeof(unsigned long long) + 64, hipHostMallocMapped));      // (8 progress words | the per-launch ring | the envelope record)
@@ -2392,6 +2406,7 @@ int cfmm_destroy(cfmm_ctx *ctx)
     if (ctx->flags2) (void)hipFree(ctx->flags2);
     for (int *q : ctx->flagsG) if (q) (void)hipFree(q);
     if (ctx->trade_buf) (void)hipFree(ctx->trade_buf);
+    if (ctx->apply_ovr) (void)hipFree(ctx->apply_ovr);
     for (void *p : {(void *)ctx->sm_out, (void *)ctx->sm_vec, (void *)ctx->H, (void *)ctx->Dinv, (void *)ctx->Winv, (void *)ctx->Rinv, (void *)ctx->chord_y, (void *)ctx->sm_ws[0], (void *)ctx->sm_ws[1], (void *)ctx->sm_ws[3], (void *)ctx->sm_ws[4], (void *)ctx->sm_slo, (void *)ctx->sm_mask, (void *)ctx->sm_info}) if (p) (void)hipFree(p);
     if (ctx->dev_arena) (void)hipFree(ctx->dev_arena);
     if (ctx->host_arena) (void)hipHostFree(ctx->host_arena);
@@ -4756,6 +4771,216 @@ int cfmm_get_tradesN(cfmm_ctx *ctx, int k, double *delta, double *lambda)
     return read_back(ctx, "get_tradesN", (size_t)k * b.m, delta, lambda, [&](double *dd, double *dl) {
         with_int<3, 8>(k, [&](auto K) { hipLaunchKernelGGL(tradesn_kernel<K>, grid, blk, 0, ctx->stream, b, nu, slo, dd, dl); });
     });
+}
+
+// ---- resident reserves back in upload order (apply.hpp: plain gathers through perm) ---------------------------------------------------
+namespace {
+// `cols` columns of `m` doubles each gathered by launch(scratch) into the read-back scratch, then host[q] <- column q (NULL: skipped)
+extern "C++" template <class Launch> int reserves_back(cfmm_ctx *ctx, const char *who, size_t m, int cols, double *const *host, Launch &&launch)
+{
+    double *d0 = nullptr, *d1 = nullptr;
+    { int rc = trade_scratch(ctx, ((size_t)cols * m + 1) / 2, &d0, &d1); if (rc) return rc; }
+    launch(d0);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, CFMM_E_HIP, "%s -> %s", who, hipGetErrorString(e));
+    for (int q = 0; q < cols; ++q)
+        if (host[q]) { int rc = download_staged(ctx, host[q], d0 + (size_t)q * m, m * sizeof(double)); if (rc) return rc; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CFMM_OK;
+}
+unsigned apply_grid(int64_t m) { return (unsigned)((m + AP_THREADS - 1) / AP_THREADS); }
+}  // namespace
+
+int cfmm_get_reserves2(cfmm_ctx *ctx, int kind, double *Ra, double *Rb, double *param)
+{
+    if (!ctx || kind < 0 || kind >= CFMM_POOL_KINDS2) return CFMM_E_ARG;
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
+    const Bucket2 b = ctx->pools->r2[kind].b;
+    if (b.m == 0) return CFMM_OK;
+    if (!b.param) param = nullptr;
+    double *const host[3] = {Ra, Rb, param};
+    const size_t m = (size_t)b.m;
+    return reserves_back(ctx, "get_reserves2", m, 3, host, [&](double *d) {
+        hipLaunchKernelGGL(reserves2_kernel, dim3(apply_grid(b.m)), dim3(AP_THREADS), 0, ctx->stream, b, d, d + m, param ? d + 2 * m : nullptr);
+    });
+}
+
+int cfmm_get_reservesN(cfmm_ctx *ctx, int k, double *R)
+{
+    if (!ctx || k < 3 || k > CFMM_MAX_POOL_SIZE) return CFMM_E_ARG;
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
+    const BucketN b = ctx->pools->rn[k].b;
+    if (b.m == 0) return CFMM_OK;
+    double *const host[1] = {R};
+    return reserves_back(ctx, "get_reservesN", (size_t)k * b.m, 1, host, [&](double *d) {
+        hipLaunchKernelGGL(reservesK_kernel, dim3(apply_grid(b.m)), dim3(AP_THREADS), 0, ctx->stream, b.R, b.perm, b.m, k, d, (const double *)nullptr, (double *)nullptr);
+    });
+}
+
+int cfmm_get_reservesG(cfmm_ctx *ctx, int kind, int k, double *R, double *param)
+{
+    if (!ctx || kind < 0 || kind >= CFMM_POOLK_KINDS || k < 2 || k > CFMM_MAX_POOL_SIZE) return CFMM_E_ARG;
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
+    const BucketG b = ctx->pools->rg[kind][k].b;
+    if (b.m == 0) return CFMM_OK;
+    if (!b.param) param = nullptr;
+    const size_t m = (size_t)b.m;
+    double *d0 = nullptr, *d1 = nullptr;
+    { int rc = trade_scratch(ctx, ((size_t)(k + 1) * m + 1) / 2, &d0, &d1); if (rc) return rc; }
+    hipLaunchKernelGGL(reservesK_kernel, dim3(apply_grid(b.m)), dim3(AP_THREADS), 0, ctx->stream, b.R, (const int *)nullptr, b.m, k, d0, b.param, param ? d0 + (size_t)k * m : nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    if (R) { int rc = download_staged(ctx, R, d0, (size_t)k * m * sizeof(double)); if (rc) return rc; }
+    if (param) { int rc = download_staged(ctx, param, d0 + (size_t)k * m, m * sizeof(double)); if (rc) return rc; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CFMM_OK;
+}
+
+// ---- the solve's trades applied to the resident pools (apply.hpp) -----------------------------------------------------------------------
+// Two passes over every bucket on this context's stream, ONE copy and ONE synchronisation each (not one per bucket: the per-call cost is
+// the lesson of the in-place update).  The first writes no pool and fills one ApplyRec per bucket; if any pool is refused the call ends
+// there and nothing has changed.  The second writes.  Sharing and ordering are the update's: the store's lock, the wait on every sharer's
+// enqueued work, the refusal while a sharer reads, one bump of the generation.
+namespace {
+inline int apply_rec2(int kind) { return kind; }
+inline int apply_recN(int k) { return CFMM_POOL_KINDS2 + k; }
+inline int apply_recG(int kind, int k) { return CFMM_POOL_KINDS2 + (CFMM_MAX_POOL_SIZE + 1) * (1 + kind) + k; }
+
+extern "C++" template <bool WRITE> int apply_pass(cfmm_ctx *ctx, int aside, const double *ovr)
+{
+    PoolStore &ps = *ctx->pools;
+    const double *nu = ctx->nu_acc;
+    const double mu = ctx->pt.mu_last > 0.0 ? ctx->pt.mu_last : 0.0;
+    const double *slo = (mu > 0.0 && ctx->pt.slo_active) ? ctx->sm_slo : nullptr;
+    const dim3 blk(AP_THREADS);
+    size_t off = 0;
+    for (int kind = 0; kind < CFMM_POOL_KINDS2; ++kind) {
+        const Bucket2 b = ps.r2[kind].b;                // (no tie flags: the call refuses while any are set)
+        if (b.m == 0) continue;
+        const double *ov = ovr ? ovr + off : nullptr;
+        off += 4 * (size_t)b.m;
+        ApplyRec *rec = ctx->apply_dev + apply_rec2(kind);
+        with_int<0, 4>(kind, [&](auto K) { hipLaunchKernelGGL((apply2_kernel<K, WRITE>), dim3(apply_grid(b.m)), blk, 0, ctx->stream, b, nu, slo, mu, aside, ov, rec); });
+    }
+    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) {
+        const BucketN b = ps.rn[k].b;
+        if (b.m == 0) continue;
+        ApplyRec *rec = ctx->apply_dev + apply_recN(k);
+        with_int<3, 8>(k, [&](auto K) { hipLaunchKernelGGL((applyN_kernel<K, WRITE>), dim3(apply_grid(b.m)), blk, 0, ctx->stream, b, nu, slo, aside, rec); });
+    }
+    for (int kind = 0; kind < CFMM_POOLK_KINDS; ++kind)
+        for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) {
+            const BucketG b = ps.rg[kind][k].b;
+            if (b.m == 0) continue;
+            ApplyRec *rec = ctx->apply_dev + apply_recG(kind, k);
+            with_int<CFMM_POOLK_STABLE, CFMM_POOLK_SUM>(kind, [&](auto KIND) {
+                with_int<2, 8>(k, [&](auto K) { hipLaunchKernelGGL((applyG_kernel<KIND, K, WRITE>), dim3(apply_grid(b.m)), blk, 0, ctx->stream, b, nu, slo, mu, aside, rec); });
+            });
+        }
+    HIP_TRY(ctx, hipGetLastError());
+    return CFMM_OK;
+}
+}  // namespace
+
+int cfmm_apply_trades(cfmm_ctx *ctx, int fee_mode, cfmm_apply_info *info)
+{
+    const char *who = "apply_trades";
+    if (!ctx) return CFMM_E_ARG;
+    if (info) { std::memset(info, 0, sizeof *info); info->first_family = info->first_kind = info->first_k = -1; info->first_pos = -1; }
+    if (fee_mode != CFMM_FEES_TO_POOL && fee_mode != CFMM_FEES_ASIDE) return fail(ctx, CFMM_E_ARG, "%s: fee mode %d", who, fee_mode);
+    if (sharded(ctx)) return fail(ctx, CFMM_E_UNSUPPORTED, "%s: pool-sharded contexts are not served", who);
+    PoolEntry entry(ctx, false); HIP_TRY(ctx, entry.device);
+    PoolStore &ps = entry.ps;
+    if (!ctx->pt.have_nu) return fail(ctx, CFMM_E_STATE, "%s: no prices yet (cfmm_set_nu or a solve first)", who);
+    bool tied = ctx->flags2 != nullptr || ctx->ng != ctx->n;
+    for (int *q : ctx->flagsG) tied |= q != nullptr;
+    if (tied) return fail(ctx, CFMM_E_UNSUPPORTED, "%s: tie flags or price ties are set by the caller, who then holds the tied pools' fills", who);
+    std::unique_lock<std::mutex> lock(ps.mu);
+    if (ps.readers > 0) return fail(ctx, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve, evaluation or read-back", who);
+    // the kink loop's own tenders (two-asset buckets, partial fills included) travel to the device once; both passes read them there
+    const double *ovr = nullptr;
+    if (ctx->pt.tr_ovr_valid) {
+        size_t len = 0;
+        for (int k = 0; k < CFMM_POOL_KINDS2; ++k) len += 4 * (size_t)ps.r2[k].b.m;
+        if (ctx->pt.tr_ovr.size() < len) return fail(ctx, CFMM_E_STATE, "%s: the kink loop's tenders do not match the resident buckets", who);
+        if (len > ctx->apply_ovr_cap) {
+            if (ctx->apply_ovr) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->apply_ovr); ctx->apply_ovr = nullptr; ctx->apply_ovr_cap = 0; }
+            HIP_TRY(ctx, hipMalloc((void **)&ctx->apply_ovr, len * sizeof(double)));
+            ctx->apply_ovr_cap = len;
+        }
+        if (len) HIP_TRY(ctx, hipMemcpyAsync(ctx->apply_ovr, ctx->pt.tr_ovr.data(), len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        ovr = ctx->apply_ovr;
+    }
+    for (cfmm_ctx *s : ps.sharers) {
+        if (s == ctx) continue;
+        HIP_TRY(ctx, hipEventRecord(s->ev_pool, s->stream));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s->ev_pool, 0));
+    }
+    const int aside = fee_mode == CFMM_FEES_ASIDE ? 1 : 0;
+    const bool timed = ctx->apply_timed;
+    float ms = 0.f;
+    ApplyRec *res = ctx->apply_host + APPLY_RECS;
+    // pass 1: nothing is written
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->apply_dev, ctx->apply_host, APPLY_RECS * sizeof(ApplyRec), hipMemcpyHostToDevice, ctx->stream));
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
+    { int rc = apply_pass<false>(ctx, aside, ovr); if (rc) return rc; }
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(res, ctx->apply_dev, APPLY_RECS * sizeof(ApplyRec), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (timed) { HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1)); ctx->apply_sec[0] = ms * 1e-3; ctx->apply_sec[1] = 0.0; }
+    int64_t moved = 0, refused = 0;
+    int first = -1;
+    for (int q = 0; q < APPLY_RECS; ++q) {
+        moved += (int64_t)res[q].moved; refused += (int64_t)res[q].refused;
+        if (first < 0 && res[q].refused) first = q;
+    }
+    if (info) { info->pools_moved = moved; info->pools_refused = refused; }
+    if (refused) {
+        int fam = 0, kind = first, k = 2;
+        if (first >= apply_recG(0, 0)) { fam = 2; kind = (first - apply_recG(0, 0)) / (CFMM_MAX_POOL_SIZE + 1); k = (first - apply_recG(0, 0)) % (CFMM_MAX_POOL_SIZE + 1); }
+        else if (first >= apply_recN(0)) { fam = 1; kind = 0; k = first - apply_recN(0); }
+        if (info) { info->first_family = fam; info->first_kind = kind; info->first_k = k; info->first_pos = (int64_t)res[first].first; }
+        return fail(ctx, CFMM_E_UNSUPPORTED, "%s: %lld pools would be left with a reserve that is not positive and finite (first: family %d, kind %d, %d assets, pool %lld); nothing was changed",
+                    who, (long long)refused, fam, kind, k, (long long)res[first].first);
+    }
+    // pass 2: the writes
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
+    { int rc = apply_pass<true>(ctx, aside, ovr); if (rc) return rc; }
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
+    const Bucket2 bs = ps.r2[CFMM_POOL_SUM2].b;
+    const bool host_sum = bs.m > 0 && (int64_t)ps.hs_Ra.size() == bs.m;           // the store's host copy of the constant-sum bucket follows
+    if (host_sum) {
+        double *d0 = nullptr, *d1 = nullptr;
+        { int rc = trade_scratch(ctx, (size_t)bs.m, &d0, &d1); if (rc) return rc; }
+        hipLaunchKernelGGL(reserves2_kernel, dim3(apply_grid(bs.m)), dim3(AP_THREADS), 0, ctx->stream, bs, d0, d1, (double *)nullptr);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(ps.hs_Ra.data(), d0, (size_t)bs.m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ps.hs_Rb.data(), d1, (size_t)bs.m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (timed) { HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1)); ctx->apply_sec[1] = ms * 1e-3; }
+    // every bucket's largest reserve, exact (pass 1 visited every pool), as a fresh upload would record it
+    double mx_all = 0.0;
+    auto record = [&](auto &r, int q) {
+        if (r.b.m == 0) return;
+        double d; std::memcpy(&d, &res[q].maxbits, sizeof d);
+        r.mxr = d; mx_all = std::max(mx_all, d);
+    };
+    for (int kind = 0; kind < CFMM_POOL_KINDS2; ++kind) record(ps.r2[kind], apply_rec2(kind));
+    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) record(ps.rn[k], apply_recN(k));
+    for (int kind = 0; kind < CFMM_POOLK_KINDS; ++kind) for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) record(ps.rg[kind][k], apply_recG(kind, k));
+    if (info) info->max_reserve = mx_all;
+    ps.gen.fetch_add(1, std::memory_order_acq_rel);
+    lock.unlock();
+    pools_seen(ctx);           // this context too drops what it derived from the old reserves (solution, kink tenders, barrier warm start, captured launches); prices, utility and ties stay
+    return CFMM_OK;
+}
+
+int cfmm_apply_timers(cfmm_ctx *ctx, int on, double *out2)
+{
+    if (!ctx) return CFMM_E_ARG;
+    ctx->apply_timed = on != 0;
+    if (out2) { out2[0] = ctx->apply_sec[0]; out2[1] = ctx->apply_sec[1]; }
+    return CFMM_OK;
 }
 
 int cfmm_comm_unique_id(void *uid128)

@@ -1055,8 +1055,10 @@ eval_batch_heavy_kernel(EvalArgs a, BatchArgs bt)
 // ------------------------------------------------------------------------------------------
 // trade materialisation (once per solve): Delta = max(-y,0), Lambda = max(y,0), slot-major
 // ------------------------------------------------------------------------------------------
-template <int KIND>
-__device__ __forceinline__ void trades2_body(const Bucket2 &b, long long i, const double *__restrict__ nu, double *__restrict__ delta, double *__restrict__ lambda)
+// one pool's exact tenders, handed to sink(Delta_a, Delta_b, Lambda_a, Lambda_b): shared by the read-back below and the apply passes
+// (apply.hpp), which must commit exactly what the read-back returns
+template <int KIND, class Sink>
+__device__ __forceinline__ void trades2_pool(const Bucket2 &b, long long i, const double *__restrict__ nu, Sink &&sink)
 {
     const double Ra = b.Ra[i], Rb = b.Rb[i], g = b.fee[i];
     const double pa = nu[b.ia[i]], pb = nu[b.ib[i]];
@@ -1066,9 +1068,16 @@ __device__ __forceinline__ void trades2_body(const Bucket2 &b, long long i, cons
     else if (KIND == 2) { y = pool_sum2(Ra, Rb, g, pa, pb); if (b.flags && b.flags[i]) { y.ya = 0.0; y.yb = 0.0; } }
     else if (KIND == 3) y = pool_curve2(Ra, Rb, g, b.param[i], pa, pb);
     else y = pool_generic2<(KIND >= 4 ? KIND : 4)>(Ra, Rb, g, b.param[i], pa, pb);
-    const long long o = b.perm ? b.perm[i] : i;          // (the tenders go out in the caller's pool order)
-    delta[o] = fmax(-y.ya, 0.0);  delta[b.m + o] = fmax(-y.yb, 0.0);
-    lambda[o] = fmax(y.ya, 0.0);  lambda[b.m + o] = fmax(y.yb, 0.0);
+    sink(fmax(-y.ya, 0.0), fmax(-y.yb, 0.0), fmax(y.ya, 0.0), fmax(y.yb, 0.0));
+}
+template <int KIND>
+__device__ __forceinline__ void trades2_body(const Bucket2 &b, long long i, const double *__restrict__ nu, double *__restrict__ delta, double *__restrict__ lambda)
+{
+    trades2_pool<KIND>(b, i, nu, [&](double Da, double Db, double La, double Lb) {
+        const long long o = b.perm ? b.perm[i] : i;          // (the tenders go out in the caller's pool order)
+        delta[o] = Da;  delta[b.m + o] = Db;
+        lambda[o] = La;  lambda[b.m + o] = Lb;
+    });
 }
 template <int KIND>
 __global__ void __launch_bounds__(256)
@@ -1091,8 +1100,9 @@ trades2_sweep_kernel(Bucket2 b, const double *__restrict__ nu, int nu_stride, do
     trades2_body<KIND>(b, i, nu + p * nu_stride, delta + p * out_stride, lambda + p * out_stride);
 }
 
-template <int K>
-__device__ __forceinline__ void tradesn_body(const BucketN &b, long long i, const double *__restrict__ nu, const double *__restrict__ slo, double *__restrict__ delta, double *__restrict__ lambda)
+// one pool's tenders, leg by leg: sink(j, R_j, Delta_j, Lambda_j)  (the read-back below; apply.hpp)
+template <int K, class Sink>
+__device__ __forceinline__ void tradesn_pool(const BucketN &b, long long i, const double *__restrict__ nu, const double *__restrict__ slo, Sink &&sink)
 {
     double R[K], w[K], p[K], y[K];
     int tok[K];
@@ -1122,12 +1132,17 @@ __device__ __forceinline__ void tradesn_body(const BucketN &b, long long i, cons
             }
         }
     }
-    const long long o = b.perm ? b.perm[i] : i;
 #pragma unroll
-    for (int j = 0; j < K; ++j) {                      // results slot-major and in the caller's pool order, as the C-ABI hands them out
-        delta[(size_t)j * b.m + o] = fmax(-y[j], 0.0);
-        lambda[(size_t)j * b.m + o] = fmax(y[j], 0.0);
-    }
+    for (int j = 0; j < K; ++j) sink(j, R[j], fmax(-y[j], 0.0), fmax(y[j], 0.0));
+}
+template <int K>
+__device__ __forceinline__ void tradesn_body(const BucketN &b, long long i, const double *__restrict__ nu, const double *__restrict__ slo, double *__restrict__ delta, double *__restrict__ lambda)
+{
+    const long long o = b.perm ? b.perm[i] : i;
+    tradesn_pool<K>(b, i, nu, slo, [&](int j, double, double D, double L) {      // results slot-major and in the caller's pool order, as the C-ABI hands them out
+        delta[(size_t)j * b.m + o] = D;
+        lambda[(size_t)j * b.m + o] = L;
+    });
 }
 template <int K>
 __global__ void __launch_bounds__(256)

@@ -961,12 +961,10 @@ gk_sum_newton_kernel(BucketG b, const double *__restrict__ nu, const double *__r
 
 // tenders at the accepted prices, slot-major [K][m] as the C-ABI hands them out (two-asset.py:94,98); flags: as tileg_sum;
 // slo: the low-order log-prices a second-order solve ended with (the tenders must be those of the same point as psi)
-template <int KIND, int K>
-__global__ void __launch_bounds__(GK_THREADS)
-tradesg_kernel(BucketG b, const int *flags, const double *__restrict__ nu, const double *__restrict__ slo, double mu, double *__restrict__ delta, double *__restrict__ lambda)
+// (one pool, leg by leg: sink(j, R_j, Delta_j, Lambda_j) -- the read-back kernel below and the apply passes, apply.hpp)
+template <int KIND, int K, class Sink>
+__device__ __forceinline__ void tradesg_pool(const BucketG &b, long long i, const int *flags, const double *__restrict__ nu, const double *__restrict__ slo, double mu, Sink &&sink)
 {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= b.m) return;
     double R[K], p[K], y[K];
     for (int j = 0; j < K; ++j) { R[j] = b.R[i * K + j]; p[j] = nu[b.idx[i * K + j]]; }
     if (KIND == 1 && mu > 0.0) {
@@ -984,7 +982,7 @@ tradesg_kernel(BucketG b, const int *flags, const double *__restrict__ nu, const
         for (int j = 0; j < K; ++j) {
             const double dl = o.L[j] + o.kap[j] * (dp[j] - dtau);
             const double dd = o.D[j] - o.D[j] * o.D[j] / mu * (dp[j] - g * dtau);
-            delta[(size_t)j * b.m + i] = fmax(dd, 0.0); lambda[(size_t)j * b.m + i] = fmax(dl, 0.0);
+            sink(j, R[j], fmax(dd, 0.0), fmax(dl, 0.0));
         }
         return;
     }
@@ -1002,10 +1000,17 @@ tradesg_kernel(BucketG b, const int *flags, const double *__restrict__ nu, const
         for (int j = 1; j < K; ++j) if (p[j] < p[lo]) lo = j;
         for (int j = 0; j < K; ++j) if (j != lo && flags[i * K + j] && y[j] != 0.0) { y[lo] += y[j] / b.fee[i]; y[j] = 0.0; }
     }
-    for (int j = 0; j < K; ++j) {
-        delta[(size_t)j * b.m + i] = fmax(-y[j], 0.0);
-        lambda[(size_t)j * b.m + i] = fmax(y[j], 0.0);
-    }
+    for (int j = 0; j < K; ++j) sink(j, R[j], fmax(-y[j], 0.0), fmax(y[j], 0.0));
+}
+template <int KIND, int K>
+__global__ void __launch_bounds__(GK_THREADS)
+tradesg_kernel(BucketG b, const int *flags, const double *__restrict__ nu, const double *__restrict__ slo, double mu, double *__restrict__ delta, double *__restrict__ lambda)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= b.m) return;
+    tradesg_pool<KIND, K>(b, i, flags, nu, slo, mu, [&](int j, double, double D, double L) {
+        delta[(size_t)j * b.m + i] = D; lambda[(size_t)j * b.m + i] = L;
+    });
 }
 
 // self-test (cfmm_selftest): the stableswap entry's own search against the function-agnostic two-level search above, on the device

@@ -434,23 +434,31 @@ gn_newton_kernel(BucketN b, const double *__restrict__ nu, const double *__restr
 // tenders of the smoothed solution, slot-major [2][m] like trades2_kernel: what cfmm_get_trades2 returns after a
 // second-order solve -- the primal point the certificates were computed on.  Both directions are (slightly) open,
 // so a pool both tenders and receives each token, as the reference's Delta_i, Lambda_i >= 0 allow (arbitrage.py:51-52).
+// (one pool, handed to sink(Delta_a, Delta_b, Lambda_a, Lambda_b): the read-back kernel below and the apply passes, apply.hpp)
+template <int KIND, class Sink>
+__device__ __forceinline__ void smooth_trades_pool(const Bucket2 &b, long long i, const double *__restrict__ nu, const double *__restrict__ slo, double mu, Sink &&sink)
+{
+    Branch ab, ba;
+    ab.D = ab.L = ba.D = ba.L = 0.0;
+    if (!(KIND == 2 && b.flags && b.flags[i])) {
+        const int ia = b.ia[i], ib = b.ib[i];
+        const double pa = nu[ia], pb = nu[ib];
+        smooth_pool<KIND>(b, i, pa, pb, mu, ab, ba);
+        if (slo) { apply_slo(ab, pa, -ab.L1 * pb, slo[ia], slo[ib]); apply_slo(ba, pb, -ba.L1 * pa, slo[ib], slo[ia]); }
+    }
+    sink(ab.D, ba.D, ba.L, ab.L);
+}
 template <int KIND>
 __global__ void __launch_bounds__(256)
 smooth_trades_kernel(Bucket2 b, const double *__restrict__ nu, const double *__restrict__ slo, double mu,
                      double *__restrict__ delta, double *__restrict__ lambda)
 {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < b.m; i += (long long)gridDim.x * blockDim.x) {
-        Branch ab, ba;
-        ab.D = ab.L = ba.D = ba.L = 0.0;
-        if (!(KIND == 2 && b.flags && b.flags[i])) {
-            const int ia = b.ia[i], ib = b.ib[i];
-            const double pa = nu[ia], pb = nu[ib];
-            smooth_pool<KIND>(b, i, pa, pb, mu, ab, ba);
-            if (slo) { apply_slo(ab, pa, -ab.L1 * pb, slo[ia], slo[ib]); apply_slo(ba, pb, -ba.L1 * pa, slo[ib], slo[ia]); }
-        }
-        const long long o = b.perm ? b.perm[i] : i;
-        delta[o] = ab.D;   delta[b.m + o] = ba.D;
-        lambda[o] = ba.L;  lambda[b.m + o] = ab.L;
+        smooth_trades_pool<KIND>(b, i, nu, slo, mu, [&](double Da, double Db, double La, double Lb) {
+            const long long o = b.perm ? b.perm[i] : i;
+            delta[o] = Da;   delta[b.m + o] = Db;
+            lambda[o] = La;  lambda[b.m + o] = Lb;
+        });
     }
 }
 

@@ -189,6 +189,44 @@ int cfmm_update_pools2(cfmm_ctx *ctx, int kind, int64_t count, const int32_t *po
 int cfmm_update_poolsN(cfmm_ctx *ctx, int k, int64_t count, const int32_t *pos, const double *R /* [k][count] */);
 int cfmm_update_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t count, const int32_t *pos,
                        const double *R /* [k][count] */, const double *param /* NULL = unchanged */);
+/* The router's own trades applied to the resident pools, on the device (docs/apply_trades.md): commits exactly the tenders
+ * cfmm_get_trades2 / N / G would return at the moment of the call -- every bucket, at the context's accepted prices: the exact pool
+ * solutions after a first-order solve or cfmm_set_nu, the gross smoothed tenders after a second-order solve (a leg may both receive and
+ * pay), the tenders with their partial fills after CFMM_METHOD_AUTO's own kink loop -- as
+ *      R' = (R + g Delta) - Lambda,   every operation individually rounded (what NumPy gives on the read-back tenders),
+ * and recomputes what the upload derives from the reserves with the same device code: an applied pool is bitwise the pool a fresh upload
+ * of the new reserves would have made, and every bucket's largest reserve is exact.
+ *   - all or nothing across all buckets: a first pass writes nothing and computes every pool's new reserves; if any leg would not stay
+ *     positive and finite (in practice a constant-sum pool traded at its LP vertex: Lambda = R_out) the call returns CFMM_E_UNSUPPORTED
+ *     with the count and the first offender in `info`, and the pools, the generation and every context are bit for bit as they were;
+ *   - sharing and ordering are those of cfmm_update_pools*: behind the work every context of the set has enqueued, CFMM_E_STATE while
+ *     another one is inside a solve, evaluation, batch or read-back, seen by every clone on its next call.  The calling context keeps its
+ *     prices, utility and ties and drops its cached solution, the kink loop's tenders, the barrier warm start and captured launches;
+ *   - refusals: no prices yet -> CFMM_E_STATE; tie flags or price ties set by the caller (cfmm_set_pool_flags / G, cfmm_set_ties: the
+ *     fills then live with the caller) or a pool-sharded context -> CFMM_E_UNSUPPORTED; another fee_mode -> CFMM_E_ARG. */
+enum { CFMM_FEES_TO_POOL = 0,   /* R' = (R + Delta) - Lambda        : the fee stays in the reserves (Uniswap v2, Balancer, Curve) */
+       CFMM_FEES_ASIDE   = 1 }; /* R' = (R + gamma * Delta) - Lambda: the fee is collected outside the pool; phi(R') = phi(R)      */
+
+typedef struct {
+    int64_t pools_moved;     /* pools with at least one non-zero tender                                          */
+    int64_t pools_refused;   /* pools with a leg that would not stay positive and finite; 0 on success           */
+    int32_t first_family;    /* of the first refused pool, in bucket order (two-asset kinds 0.., geo-mean sizes   */
+    int32_t first_kind;      /*   3..8, table buckets): 0 two-asset, 1 geo-mean, 2 table; kind; size k;          */
+    int32_t first_k;         /*   position in UPLOAD order  (-1 each when no pool is refused)                    */
+    int32_t _pad;
+    int64_t first_pos;
+    double  max_reserve;     /* largest reserve resident after the call                                          */
+} cfmm_apply_info;
+
+int cfmm_apply_trades(cfmm_ctx *ctx, int fee_mode, cfmm_apply_info *info /* or NULL */);
+/* the resident reserves in upload order (the order cfmm_get_trades* reports in), and the parameter column where the kind has one
+ * (NULL, or a kind without one: not written); an empty bucket is CFMM_OK and writes nothing */
+int cfmm_get_reserves2(cfmm_ctx *ctx, int kind, double *Ra, double *Rb, double *param /* or NULL */);   /* [m], upload order */
+int cfmm_get_reservesN(cfmm_ctx *ctx, int k, double *R /* [k][m] slot-major */);
+int cfmm_get_reservesG(cfmm_ctx *ctx, int kind, int k, double *R /* [k][m] */, double *param /* or NULL */);
+/* measurement hook (tools/apply_timing.py): with `on`, every cfmm_apply_trades brackets each pass's launches with HIP events;
+ * out2 (or NULL) receives the seconds of the last apply's checking pass and writing pass */
+int cfmm_apply_timers(cfmm_ctx *ctx, int on, double *out2);
 /* constant-sum pools sitting on their kink are `tied` (flag 1): they are skipped by the
  * kernels and their fill fraction is assigned by the host's primal recovery */
 int cfmm_set_pool_flags(cfmm_ctx *ctx, int kind, const int32_t *flags /* [m] or NULL */);
