@@ -43,6 +43,7 @@
 #include "handoff.hpp"
 #include "solve_plan.hpp"
 #include "newton_rules.hpp"
+#include "sweep_rules.hpp"
 
 using namespace cfmm;
 
@@ -148,6 +149,22 @@ struct PoolStore {
 };
 
 // Where the context's prices and solution are, and what the read-backs may return: assigned only by the transitions next to pools_changed
+// the per-point layout of the tenders cfmm_solve_sweep hands out (and Point::tr_ovr keeps): for every bucket in the order two-asset
+// kinds 0.., then K = 3..8: delta [k][m] | lambda [k][m]
+struct TradeLayout {
+    size_t off2[CFMM_POOL_KINDS2], offn[CFMM_MAX_POOL_SIZE + 1], stride;      // a bucket's first double; doubles per point
+    size_t two_asset() const { return offn[3]; }                                // doubles of the two-asset kinds, which come first
+};
+static TradeLayout trade_layout(const PoolStore &ps)
+{
+    TradeLayout t = {};
+    size_t off = 0;
+    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) { t.off2[k] = off; off += 4 * (size_t)ps.r2[k].b.m; }
+    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) { t.offn[k] = off; off += 2 * (size_t)k * ps.rn[k].b.m; }
+    t.stride = off;
+    return t;
+}
+
 struct Point {
     bool have_nu = false;              // nu_acc holds prices: the caller's or a solve's
     bool hsol_valid = false;           // hsol holds nu | psi of the last solve
@@ -182,6 +199,8 @@ struct cfmm_ctx {
     // (pieces of the two arenas below)
     ApplyRec *apply_dev = nullptr, *apply_host = nullptr;
     double *apply_ovr = nullptr; size_t apply_ovr_cap = 0;     // grow-only device copy of the kink loop's tenders (Point::tr_ovr)
+    // cfmm_solve_sweep: grow-only slab (device, and its pinned twin) of the points' arguments, inputs, results and state; their tenders
+    struct { char *dev = nullptr, *host = nullptr; size_t cap = 0; double *tr_dev = nullptr; size_t tr_cap = 0; } sweep;
     bool apply_timed = false;          // cfmm_apply_timers: HIP events around each pass's launches
     double apply_sec[2] = {0.0, 0.0};  // ... of the last apply: the pass that checks, the pass that writes
 
@@ -1301,26 +1320,8 @@ int bounds_into_mirror(cfmm_ctx *ctx)
 {
     const int n = ctx->n, ng = ctx->ng;
     double *lo = (double *)(ctx->util_h + ((char *)ctx->glo - (char *)ctx->c)), *hi = (double *)(ctx->util_h + ((char *)ctx->ghi - (char *)ctx->c));
-    for (int r = 0; r < ng; ++r) { lo[r] = -INFINITY; hi[r] = INFINITY; }
-    // A price the utility does not bound (c = 0; an equality) is still kept within e^+-100 of the utility's own scale: a WORTHLESS token's
-    // log-price otherwise runs off until nu underflows to zero and the pool arithmetic turns it into NaNs -- "dual value is not finite"
-    // instead of a stalled solve the caller can classify (tools/fuzz_table.py: a liquidation whose target no pool lists)
-    double cmax = 0.0;
-    for (int j = 0; j < n; ++j) if (ctx->hctype[j] < CFMM_ULOG) cmax = std::max(cmax, ctx->hc[j]);
-    const double mid = cmax > 0.0 ? std::log(cmax) : 0.0, span = 100.0;
-    for (int j = 0; j < n; ++j) {
-        const int r = ctx->hgrp[j];
-        double l = mid - span, u = mid + span;
-        if (ctx->hctype[j] >= CFMM_ULOG) { l = -INFINITY; u = INFINITY; }       // (the utility table's entries: no bound; their conjugates hold the price)
-        if (ctx->hctype[j] == CFMM_GE) { l = ctx->hc[j] > 0.0 ? std::log(ctx->hc[j]) : mid - span; u = INFINITY; }
-        else if (ctx->hctype[j] == CFMM_FREE) {
-            if (!(ctx->hc[j] > 0.0)) return fail(ctx, CFMM_E_ARG, "token %d: CFMM_FREE needs c > 0", j);
-            l = u = std::log(ctx->hc[j]);
-        }
-        l -= ctx->hoff[j]; u -= ctx->hoff[j];
-        if (l > lo[r]) lo[r] = l;
-        if (u < hi[r]) hi[r] = u;
-    }
+    const int j = sweep::group_bounds(n, ctx->hc.data(), ctx->hctype.data(), ctx->hgrp.data(), ctx->hoff.data(), ng, lo, hi);
+    if (j >= 0) return fail(ctx, CFMM_E_ARG, "token %d: CFMM_FREE needs c > 0", j);
     return CFMM_OK;
 }
 
@@ -2191,7 +2192,6 @@ int solve_newton(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out, int evals_b
 extern "C" {
 
 static void pools_ready(cfmm_ctx *ctx);     // (the pending token-block orderings: reorder.hpp)
-static void sweep_release(cfmm_ctx *ctx);   // (the buffers of cfmm_solve_sweep)
 static void release_landed(cfmm_ctx *ctx);
 
 void cfmm_default_opts(cfmm_opts *o)
@@ -2407,6 +2407,9 @@ int cfmm_destroy(cfmm_ctx *ctx)
     for (int *q : ctx->flagsG) if (q) (void)hipFree(q);
     if (ctx->trade_buf) (void)hipFree(ctx->trade_buf);
     if (ctx->apply_ovr) (void)hipFree(ctx->apply_ovr);
+    if (ctx->sweep.dev) (void)hipFree(ctx->sweep.dev);
+    if (ctx->sweep.host) (void)hipHostFree(ctx->sweep.host);
+    if (ctx->sweep.tr_dev) (void)hipFree(ctx->sweep.tr_dev);
     for (void *p : {(void *)ctx->sm_out, (void *)ctx->sm_vec, (void *)ctx->H, (void *)ctx->Dinv, (void *)ctx->Winv, (void *)ctx->Rinv, (void *)ctx->chord_y, (void *)ctx->sm_ws[0], (void *)ctx->sm_ws[1], (void *)ctx->sm_ws[3], (void *)ctx->sm_ws[4], (void *)ctx->sm_slo, (void *)ctx->sm_mask, (void *)ctx->sm_info}) if (p) (void)hipFree(p);
     if (ctx->dev_arena) (void)hipFree(ctx->dev_arena);
     if (ctx->host_arena) (void)hipHostFree(ctx->host_arena);
@@ -2429,7 +2432,6 @@ int cfmm_destroy(cfmm_ctx *ctx)
         auto &fl = g_free_streams[ctx->device & 63];
         if (fl.size() < 16) fl.push_back(ctx->stream); else (void)hipStreamDestroy(ctx->stream);      // (idle: synchronised above)
     }
-    sweep_release(ctx);
     delete ctx;
     return CFMM_OK;
 }
@@ -3420,10 +3422,8 @@ static int solve_tiny_kinks(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out)
         HIP_TRY(ctx, hipMemcpyAsync(nu0.data(), ctx->nu_acc, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
-    size_t tr_len = 0;
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) tr_len += 4 * (size_t)ctx->pools->r2[k].b.m;
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) tr_len += 2 * (size_t)k * ctx->pools->rn[k].b.m;
-    std::vector<double> nu(n), psi(n), theta(msum), tr(tr_len);
+    const TradeLayout T = trade_layout(*ctx->pools);
+    std::vector<double> nu(n), psi(n), theta(msum), tr(T.stride);
     std::vector<int32_t> tsgn(msum), ct(ctx->hctype.begin(), ctx->hctype.begin() + n);
     cfmm_opts os = o;
     os.method = CFMM_METHOD_LBFGS;
@@ -3435,28 +3435,12 @@ static int solve_tiny_kinks(cfmm_ctx *ctx, const cfmm_opts &o, cfmm_stats *out)
                               ctx->pools->hs_Ra.data(), ctx->pools->hs_Rb.data(), &os, 0.0, 0, nu.data(), psi.data(), theta.data(), tsgn.data(), tr.data(), &st, &rounds);
     if (rc == CFMM_E_NUMERIC || rc == CFMM_E_UNSUPPORTED) { ctx->nu0_deferred = deferred; return 0; }
     if (rc) return rc;
-    // psi_total = psi + sum theta d, the tied pools' tenders = theta x their full fill (cfmm.h: cfmm_solve_sweep)
-    size_t off_sum = 0;
-    for (int k = 0; k < CFMM_POOL_SUM2; ++k) off_sum += 4 * (size_t)ctx->pools->r2[k].b.m;
-    double *dS = tr.data() + off_sum, *lS = dS + 2 * msum;                                  // delta [2][m] | lambda [2][m]
-    for (int64_t i = 0; i < msum; ++i) {
-        if (!std::isfinite(theta[i])) continue;
-        const double ya = (tsgn[i] > 0 ? -ctx->pools->hs_Rb[i] / ctx->pools->hs_fee[i] : ctx->pools->hs_Ra[i]) * theta[i];
-        const double yb = (tsgn[i] > 0 ? ctx->pools->hs_Rb[i] : -ctx->pools->hs_Ra[i] / ctx->pools->hs_fee[i]) * theta[i];
-        psi[ctx->pools->hs_ia[i]] += ya; psi[ctx->pools->hs_ib[i]] += yb;
-        dS[i] = std::max(-ya, 0.0); dS[msum + i] = std::max(-yb, 0.0);
-        lS[i] = std::max(ya, 0.0); lS[msum + i] = std::max(yb, 0.0);
-    }
-    // the certificates of the whole point (as cfmm/problem.py: _solve_sweep computes them)
-    double value = 0.0, cs = 0.0, dual = 0.0, viol = 0.0, scale = 0.0;
-    for (int j = 0; j < n; ++j) {
-        const double c = ctx->hc[j], h = ctx->hh[j], r = psi[j] + h;
-        value += c * psi[j]; cs += (nu[j] - c) * r; dual += (nu[j] - c) * h + nu[j] * psi[j];
-        viol = std::max(viol, ct[j] == CFMM_GE ? std::max(-r, 0.0) : (ct[j] == CFMM_EQ ? std::fabs(r) : 0.0));
-        scale = std::max(scale, std::max(std::fabs(psi[j]), std::fabs(h)));
-    }
-    const double gap = std::fabs(cs) / std::max(1.0, std::fabs(dual));
-    const double infeas = viol / std::max(std::max(scale, 1e-12 * ctx->g_max_reserve), 1e-300);
+    const PoolStore &ps = *ctx->pools;
+    const sweep::SumCols sc{msum, ps.hs_ia.data(), ps.hs_ib.data(), ps.hs_fee.data(), ps.hs_Ra.data(), ps.hs_Rb.data()};
+    double *dS = tr.data() + T.off2[CFMM_POOL_SUM2];                                         // delta [2][m] | lambda [2][m]
+    sweep::fold_fills(sc, theta.data(), tsgn.data(), psi.data(), dS, dS + 2 * msum);
+    const sweep::PointCertificates k = sweep::point_certificates(n, nu.data(), psi.data(), ctx->hc.data(), ctx->hh.data(), ct.data(), ctx->g_max_reserve);
+    const double value = k.value, dual = k.dual, gap = k.gap, infeas = k.infeas;
     if (!(gap <= o.tol_gap * (1.0 + 1e-6) + 1e-15 && infeas <= o.tol_infeas * (1.0 + 1e-6) + 1e-15)) { ctx->nu0_deferred = deferred; return 0; }
     // the point is certified: leave it where the read-backs expect it
     std::memcpy(ctx->hsol, nu.data(), n * sizeof(double));
@@ -4248,188 +4232,12 @@ int cfmm_batch_capacity(int n_tokens) { return n_tokens < 1 ? 0 : batch_capacity
 // now smooth reduced dual, recover the fill fractions, release ties whose fill leaves (0, 1)) runs HERE, in lock-step over the
 // points, between the rounds: one H2D copy, two launches and one D2H copy per round for the whole sweep, no Python in between.
 // Round 4 ran the sweep as 50 x ~3 sequential one-workgroup launches with the kink logic in Python: 13 ms.
+// The loop's decisions are host-only rules (sweep_rules.hpp); what follows lays out the slab, moves the bytes and launches.
 // ---------------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-// weighted union-find over the tokens of a tiny network: log nu_j = s[group(j)] + off[j]   (problem.py: _Ties)
-struct SweepTies {
-    int parent[TINY_N]; double off[TINY_N]; int n;
-    void init(int n_) { n = n_; for (int j = 0; j < n; ++j) { parent[j] = j; off[j] = 0.0; } }
-    int find(int j)
-    {
-        int path[TINY_N], np = 0;
-        while (parent[j] != j) { path[np++] = j; j = parent[j]; }
-        const int root = j;
-        for (int q = np - 1; q >= 0; --q) {            // from the top of the path down: the parent's offset is already relative to the root
-            const int node = path[q], p = parent[node];
-            if (p != root) off[node] += off[p];
-            parent[node] = root;
-        }
-        return root;
-    }
-    bool tie(int a, int b, double delta)               // log nu_a - log nu_b = delta; false if it contradicts the ties so far
-    {
-        const int ra = find(a), rb = find(b);
-        if (ra == rb) return std::fabs((off[a] - off[b]) - delta) < 1e-12;
-        off[ra] = delta + off[b] - off[a];
-        parent[ra] = rb;
-        return true;
-    }
-    int groups(int *grp)                               // group ids in the order of the (sorted) roots, as np.unique numbers them
-    {
-        int root[TINY_N]; bool is_root[TINY_N] = {};
-        for (int j = 0; j < n; ++j) { root[j] = find(j); is_root[root[j]] = true; }
-        int id[TINY_N], ng = 0;
-        for (int j = 0; j < n; ++j) if (is_root[j]) id[j] = ng++;
-        for (int j = 0; j < n; ++j) grp[j] = id[root[j]];
-        return ng;
-    }
-};
-
-struct SweepTie { int sgn; bool loose; };
-struct SumCols { int64_t m; const int32_t *ia, *ib; const double *fee, *Ra, *Rb; };
-
-// least squares  min |A th - b|  over th in [0, 1]^K for a handful of tied pools (A: R x K, row-major): the unconstrained solution
-// where it lies inside the box; otherwise the best of the 3^K assignments {free, at 0, at 1} whose free part stays inside (exact for
-// a convex problem: the optimum is one of them, and none of the others can beat it); beyond 7 unknowns the clipped solution
-bool small_lsq(const std::vector<double> &A, const std::vector<double> &b, int R, int K, const std::vector<int> &freev, const std::vector<double> &fixed,
-               std::vector<double> &th)
-{
-    // free variables by the normal equations (a whiff of ridge: a rank-deficient system gets the small-norm solution, as lstsq does)
-    const int F = (int)freev.size();
-    th = fixed;
-    if (F == 0) return true;
-    std::vector<double> N((size_t)F * F, 0.0), g(F, 0.0), rb(b);
-    for (int r = 0; r < R; ++r) for (int k = 0; k < K; ++k) rb[r] -= A[(size_t)r * K + k] * fixed[k];
-    double tr = 0.0;
-    for (int i = 0; i < F; ++i) {
-        for (int j = 0; j <= i; ++j) {
-            double v = 0.0;
-            for (int r = 0; r < R; ++r) v += A[(size_t)r * K + freev[i]] * A[(size_t)r * K + freev[j]];
-            N[(size_t)i * F + j] = N[(size_t)j * F + i] = v;
-        }
-        for (int r = 0; r < R; ++r) g[i] += A[(size_t)r * K + freev[i]] * rb[r];
-        tr += N[(size_t)i * F + i];
-    }
-    const double ridge = 1e-14 * (tr > 0.0 ? tr / F : 1.0);
-    for (int i = 0; i < F; ++i) N[(size_t)i * F + i] += ridge;
-    for (int i = 0; i < F; ++i) {                       // Cholesky, in place
-        for (int j = 0; j <= i; ++j) {
-            double v = N[(size_t)i * F + j];
-            for (int q = 0; q < j; ++q) v -= N[(size_t)i * F + q] * N[(size_t)j * F + q];
-            if (i == j) { if (!(v > 0.0)) return false; N[(size_t)i * F + i] = std::sqrt(v); }
-            else N[(size_t)i * F + j] = v / N[(size_t)j * F + j];
-        }
-    }
-    for (int i = 0; i < F; ++i) { double v = g[i]; for (int q = 0; q < i; ++q) v -= N[(size_t)i * F + q] * g[q]; g[i] = v / N[(size_t)i * F + i]; }
-    for (int i = F - 1; i >= 0; --i) { double v = g[i]; for (int q = i + 1; q < F; ++q) v -= N[(size_t)q * F + i] * g[q]; g[i] = v / N[(size_t)i * F + i]; }
-    for (int i = 0; i < F; ++i) th[freev[i]] = g[i];
-    return true;
-}
-void box_lsq(const std::vector<double> &A, const std::vector<double> &b, int R, int K, std::vector<double> &th)
-{
-    std::vector<int> all(K);
-    for (int k = 0; k < K; ++k) all[k] = k;
-    std::vector<double> zero(K, 0.0);
-    if (!small_lsq(A, b, R, K, all, zero, th)) { th.assign(K, 0.5); return; }
-    bool inside = true;
-    for (double v : th) inside = inside && v >= 0.0 && v <= 1.0;
-    if (inside) return;
-    if (K > 7) { for (double &v : th) v = std::min(1.0, std::max(0.0, v)); return; }
-    auto resid = [&](const std::vector<double> &t) { double s2 = 0.0; for (int r = 0; r < R; ++r) { double v = -b[r]; for (int k = 0; k < K; ++k) v += A[(size_t)r * K + k] * t[k]; s2 += v * v; } return s2; };
-    std::vector<double> best(th);
-    for (double &v : best) v = std::min(1.0, std::max(0.0, v));
-    double best_r = resid(best);
-    int total = 1; for (int k = 0; k < K; ++k) total *= 3;
-    std::vector<int> fr; std::vector<double> fx(K), cand;
-    for (int code = 1; code < total; ++code) {           // (code 0 = all free: done above)
-        fr.clear();
-        int c = code;
-        for (int k = 0; k < K; ++k, c /= 3) { const int m3 = c % 3; fx[k] = m3 == 2 ? 1.0 : 0.0; if (m3 == 0) fr.push_back(k); }
-        if (!small_lsq(A, b, R, K, fr, fx, cand)) continue;
-        bool ok = true;
-        for (int k : fr) ok = ok && cand[k] >= 0.0 && cand[k] <= 1.0;
-        if (!ok) continue;
-        const double rr = resid(cand);
-        if (rr < best_r) { best_r = rr; best = cand; }
-    }
-    th = best;
-}
-
-// fill fractions of the tied constant-sum pools (problem.py: Problem._recover_fills): theta in [0, 1]^K with
-// (psi + h + sum_k theta_k d_k)_j = 0 on every token that must balance, >= 0 on GE tokens at their bound
-bool sweep_recover_fills(int n, const double *nu, const double *psi, const double *c, const double *h, const int32_t *ctype, const SumCols &sc,
-                         const std::map<int, SweepTie> &tied, double tol, std::vector<double> &th)
-{
-    const int K = (int)tied.size();
-    std::vector<double> D((size_t)n * K, 0.0);
-    int k = 0;
-    for (auto &kv : tied) {
-        const int i = kv.first, a = sc.ia[i], b = sc.ib[i];
-        const double g = sc.fee[i];
-        if (kv.second.sgn > 0) { D[(size_t)a * K + k] = -sc.Rb[i] / g; D[(size_t)b * K + k] = sc.Rb[i]; }      // tender a, drain b
-        else { D[(size_t)b * K + k] = -sc.Ra[i] / g; D[(size_t)a * K + k] = sc.Ra[i]; }
-        ++k;
-    }
-    std::vector<double> A, rhs;
-    std::vector<char> must(n), atb(n);
-    int R = 0;
-    for (int j = 0; j < n; ++j) {
-        const int ct = ctype ? ctype[j] : CFMM_GE;
-        const double hj = h ? h[j] : 0.0;
-        atb[j] = ct == CFMM_GE && nu[j] <= c[j] * (1.0 + 1e-9);
-        must[j] = ct == CFMM_EQ || (ct == CFMM_GE && !atb[j]);
-        bool touched = false;
-        for (int q = 0; q < K; ++q) touched = touched || D[(size_t)j * K + q] != 0.0;
-        if (must[j] && touched) {
-            for (int q = 0; q < K; ++q) A.push_back(D[(size_t)j * K + q] * nu[j]);
-            rhs.push_back(-(psi[j] + hj) * nu[j]);
-            ++R;
-        }
-    }
-    if (R == 0) th.assign(K, 0.5);
-    else if (K == 1) {
-        double aa = 0.0, ab = 0.0;
-        for (int r = 0; r < R; ++r) { aa += A[r] * A[r]; ab += A[r] * rhs[r]; }
-        th.assign(1, std::min(1.0, std::max(0.0, ab / std::max(aa, 1e-300))));
-    } else box_lsq(A, rhs, R, K, th);
-    double scale = 0.0, res_eq = 0.0, res_ge = 0.0;
-    for (int j = 0; j < n; ++j) {
-        const double hj = h ? h[j] : 0.0;
-        scale += std::fabs(nu[j] * (std::fabs(psi[j]) + std::fabs(hj)));
-        double tot = psi[j] + hj;
-        for (int q = 0; q < K; ++q) tot += D[(size_t)j * K + q] * th[q];
-        if (must[j]) res_eq += std::fabs(nu[j] * tot);
-        if (atb[j]) res_ge += std::max(-(nu[j] * tot), 0.0);
-    }
-    scale = std::max(1.0, scale);
-    return res_eq / scale <= 10.0 * tol && res_ge / scale <= 10.0 * tol;
-}
-
-// constant-sum pools whose price ratio sits on one of their two kinks (problem.py: Problem._kink_candidates)
-void sweep_kink_candidates(const double *nu, const SumCols &sc, double kink_tol, const std::set<std::pair<int, int>> &banned, const std::map<int, SweepTie> &tied,
-                           bool loose, std::map<int, SweepTie> &out)
-{
-    out.clear();
-    for (int64_t i = 0; i < sc.m; ++i) {
-        const double r = std::log(nu[sc.ia[i]]) - std::log(nu[sc.ib[i]]), lg = std::log(sc.fee[i]);
-        const int sgn = r < 0.0 ? 1 : -1;               // a->b kink at r = lg < 0, b->a kink at r = -lg > 0
-        const double dist = std::fabs(r - sgn * lg);
-        const bool near = dist < kink_tol && (dist < 0.5 * std::fabs(lg) || lg == 0.0 || loose);
-        if (near && !tied.count((int)i) && !banned.count({(int)i, sgn})) out[(int)i] = SweepTie{sgn, loose};
-    }
-}
-
-struct SweepPointState {
-    std::map<int, SweepTie> tied;
-    std::set<std::pair<int, int>> banned;
-    std::vector<double> theta;              // of `tied`, in its order, once the fills are recovered
-    int budget = 0, evals = 0, iters = 0, rounds = 0;
-    double kink_tol = 1e-3;
-    bool done = false, fills_ok = false;
-    DevState st = {};
-};
-
+// the slab of a sweep: per point its arguments (UpdArgs), inputs, outputs and device-only state.  The device's copy and its pinned twin
+// share the layout; a round copies arguments + inputs down and the outputs up
 struct SweepLayout {
     int n, B, msum;
     size_t a_stride, o_stride, s_stride;    // doubles per point: inputs | outputs | device-only state
@@ -4455,42 +4263,43 @@ struct SweepLayout {
     DevState *st(char *base, int p) const { return (DevState *)(O(base, p) + 2 * n); }
 };
 
-}  // namespace
-
-struct cfmm_sweep_buffers { char *dev = nullptr, *host = nullptr; size_t cap = 0; double *tr_dev = nullptr; size_t tr_cap = 0; };
-static std::mutex g_sweep_mu;
-static std::map<cfmm_ctx *, cfmm_sweep_buffers> g_sweep;       // (per context, released by cfmm_destroy)
-static void sweep_release(cfmm_ctx *ctx)
-{
-    std::lock_guard<std::mutex> g(g_sweep_mu);
-    auto it = g_sweep.find(ctx);
-    if (it == g_sweep.end()) return;
-    if (it->second.dev) (void)hipFree(it->second.dev);
-    if (it->second.host) (void)hipHostFree(it->second.host);
-    if (it->second.tr_dev) (void)hipFree(it->second.tr_dev);
-    g_sweep.erase(it);
-}
-
-int cfmm_solve_sweep(cfmm_ctx *ctx, int B, const double *c, const double *h, const int32_t *ctype, const double *nu0,
-                     int64_t m_sum, const int32_t *sum_ia, const int32_t *sum_ib, const double *sum_fee, const double *sum_Ra, const double *sum_Rb,
-                     const cfmm_opts *opts_in, double kink_tol, int max_rounds,
-                     double *nu_out, double *psi_out, double *theta_out, int32_t *tsgn_out, double *trades_out, cfmm_stats *out, int32_t *rounds_out)
-{
-    if (!ctx || B < 1 || !c || !nu0 || !nu_out || !psi_out || !out) return ctx ? fail(ctx, CFMM_E_ARG, "solve_sweep: NULL argument or no points") : CFMM_E_ARG;
-    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
-    const int n = ctx->n;
+// one call of cfmm_solve_sweep: what its phases share
+struct SweepRun {
+    cfmm_ctx *ctx;
     cfmm_opts o;
+    EvalArgs ea;
+    int n, B, msum, max_rounds;
+    int64_t pools;
+    SweepLayout L;
+    TradeLayout T;
+    char *host = nullptr, *dev = nullptr;       // the slab's pinned twin and the slab (cfmm_ctx::sweep)
+    sweep::SumCols sc;
+    std::vector<sweep::PointState> ps;
+    std::vector<int> active;                    // the unfinished points of this round, in the order of their arguments
+    std::chrono::steady_clock::time_point t0, t1;
+    float ms = 0.f;
+    SweepRun(cfmm_ctx *c, const cfmm_opts &o_, const EvalArgs &ea_, int B_, const sweep::SumCols &sc_, int max_rounds_)
+        : ctx(c), o(o_), ea(ea_), n(c->n), B(B_), msum((int)sc_.m), max_rounds(max_rounds_ < 1 ? 6 : max_rounds_), pools(cfmm_pool_count(c)),
+          L(c->n, B_, (int)sc_.m), T(trade_layout(*c->pools)), sc(sc_), ps(B_) {}
+};
+
+// the caller's options with their defaults filled in (o, ea), whether this context's network is one the sweep serves, and the points'
+// utilities, start prices and constant-sum columns
+int sweep_check_args(cfmm_ctx *ctx, const cfmm_opts *opts_in, int B, const double *c, const double *h, const int32_t *ctype, const double *nu0,
+                     const sweep::SumCols &sc, const double *theta_out, const int32_t *tsgn_out, cfmm_opts &o, EvalArgs &ea)
+{
+    const int n = ctx->n;
     if (opts_in) o = *opts_in; else cfmm_default_opts(&o);
     if (o.memory == 0) o.memory = n <= 32 ? 8 : 3;
     if (o.memory < 1 || o.memory > MAX_MEMORY || o.max_evals < 1) return fail(ctx, CFMM_E_ARG, "solve_sweep: memory %d, max_evals %d", o.memory, o.max_evals);
     if (o.method == CFMM_METHOD_NEWTON) return fail(ctx, CFMM_E_UNSUPPORTED, "solve_sweep: first-order method only");
-    const EvalArgs ea = make_eval_args(ctx, false, 0x7fffffff, false);
+    ea = make_eval_args(ctx, false, 0x7fffffff, false);
     if (!(ctx->tiny_path && !sharded(ctx) && !ctx->det && extra_launch_pools(ctx) == 0 && ea.ntiles >= 1 && ea.ntiles <= TINY_MAX_TILES && n <= TINY_N))
         return fail(ctx, CFMM_E_UNSUPPORTED, "solve_sweep: serves networks one workgroup evaluates (<= %d tokens, <= %d wave-tiles, no stableswap / generic / K-asset table pools, "
                                              "one GPU, not the reproducible mode); solve the points one at a time or through cfmm_solve_batch", TINY_N, TINY_MAX_TILES);
     if (B > 4096) return fail(ctx, CFMM_E_LIMIT, "solve_sweep: %d points (at most 4096 per call)", B);
-    if (m_sum != ctx->pools->r2[CFMM_POOL_SUM2].b.m) return fail(ctx, CFMM_E_ARG, "solve_sweep: %lld constant-sum pools handed in, %lld uploaded", (long long)m_sum, (long long)ctx->pools->r2[CFMM_POOL_SUM2].b.m);
-    if (m_sum > 0 && (!sum_ia || !sum_ib || !sum_fee || !sum_Ra || !sum_Rb || !theta_out || !tsgn_out)) return fail(ctx, CFMM_E_ARG, "solve_sweep: the constant-sum columns (and theta / tsgn) are needed when such pools exist");
+    if (sc.m != ctx->pools->r2[CFMM_POOL_SUM2].b.m) return fail(ctx, CFMM_E_ARG, "solve_sweep: %lld constant-sum pools handed in, %lld uploaded", (long long)sc.m, (long long)ctx->pools->r2[CFMM_POOL_SUM2].b.m);
+    if (sc.m > 0 && (!sc.ia || !sc.ib || !sc.fee || !sc.Ra || !sc.Rb || !theta_out || !tsgn_out)) return fail(ctx, CFMM_E_ARG, "solve_sweep: the constant-sum columns (and theta / tsgn) are needed when such pools exist");
     for (int p = 0; p < B; ++p) for (int j = 0; j < n; ++j) {
         const double cj = c[(size_t)p * n + j], v = nu0[(size_t)p * n + j];
         if (!(cj >= 0.0) || !std::isfinite(cj)) return fail(ctx, CFMM_E_ARG, "solve_sweep: point %d, c[%d] < 0 or not finite", p, j);
@@ -4502,216 +4311,184 @@ int cfmm_solve_sweep(cfmm_ctx *ctx, int B, const double *c, const double *h, con
         }
     }
     if (h) for (size_t q = 0; q < (size_t)B * n; ++q) if (!std::isfinite(h[q])) return fail(ctx, CFMM_E_ARG, "solve_sweep: point %d, h[%d] is not finite", (int)(q / n), (int)(q % n));
-    for (int64_t i = 0; i < m_sum; ++i) {               // (the host's half of the kink loop indexes prices with these: the columns as uploaded)
-        if (sum_ia[i] < 0 || sum_ia[i] >= n || sum_ib[i] < 0 || sum_ib[i] >= n || sum_ia[i] == sum_ib[i])
-            return fail(ctx, CFMM_E_ARG, "solve_sweep: constant-sum pool %lld: token ids (%d, %d) out of range or equal", (long long)i, sum_ia[i], sum_ib[i]);
-        if (!(sum_fee[i] > 0.0 && sum_fee[i] <= 1.0) || !(sum_Ra[i] > 0.0) || !(sum_Rb[i] > 0.0) || !std::isfinite(sum_Ra[i]) || !std::isfinite(sum_Rb[i]))
-            return fail(ctx, CFMM_E_ARG, "solve_sweep: constant-sum pool %lld: fee %g, reserves (%g, %g)", (long long)i, sum_fee[i], sum_Ra[i], sum_Rb[i]);
+    for (int64_t i = 0; i < sc.m; ++i) {               // (the host's half of the kink loop indexes prices with these: the columns as uploaded)
+        if (sc.ia[i] < 0 || sc.ia[i] >= n || sc.ib[i] < 0 || sc.ib[i] >= n || sc.ia[i] == sc.ib[i])
+            return fail(ctx, CFMM_E_ARG, "solve_sweep: constant-sum pool %lld: token ids (%d, %d) out of range or equal", (long long)i, sc.ia[i], sc.ib[i]);
+        if (!(sc.fee[i] > 0.0 && sc.fee[i] <= 1.0) || !(sc.Ra[i] > 0.0) || !(sc.Rb[i] > 0.0) || !std::isfinite(sc.Ra[i]) || !std::isfinite(sc.Rb[i]))
+            return fail(ctx, CFMM_E_ARG, "solve_sweep: constant-sum pool %lld: fee %g, reserves (%g, %g)", (long long)i, sc.fee[i], sc.Ra[i], sc.Rb[i]);
     }
-    const SumCols sc{m_sum, sum_ia, sum_ib, sum_fee, sum_Ra, sum_Rb};
-    const int msum = (int)m_sum;
-    const SweepLayout L(n, B, msum);
-    // tenders: per point, for every non-empty bucket in the order two-asset kinds 0.., then K = 3..8: delta [k][m] | lambda [k][m]
-    size_t tr_stride = 0;
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) tr_stride += 4 * (size_t)ctx->pools->r2[k].b.m;
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) tr_stride += 2 * (size_t)k * ctx->pools->rn[k].b.m;
-    cfmm_sweep_buffers *sb;
-    {
-        std::lock_guard<std::mutex> g(g_sweep_mu);
-        sb = &g_sweep[ctx];
-    }
-    if (sb->cap < L.total) {
+    return CFMM_OK;
+}
+
+// the context's slab and (with_trades) its tenders, grown to this call's size
+int sweep_reserve(SweepRun &R, bool with_trades)
+{
+    cfmm_ctx *ctx = R.ctx;
+    auto &sb = ctx->sweep;
+    if (sb.cap < R.L.total) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (sb->dev) (void)hipFree(sb->dev);
-        if (sb->host) (void)hipHostFree(sb->host);
-        sb->dev = sb->host = nullptr; sb->cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&sb->dev, L.total + 256));
-        HIP_TRY(ctx, hipHostMalloc((void **)&sb->host, L.total + 256, hipHostMallocDefault));
-        sb->cap = L.total;
+        if (sb.dev) (void)hipFree(sb.dev);
+        if (sb.host) (void)hipHostFree(sb.host);
+        sb.dev = sb.host = nullptr; sb.cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&sb.dev, R.L.total + 256));
+        HIP_TRY(ctx, hipHostMalloc((void **)&sb.host, R.L.total + 256, hipHostMallocDefault));
+        sb.cap = R.L.total;
     }
-    if (trades_out && sb->tr_cap < (size_t)B * tr_stride) {
+    if (with_trades && sb.tr_cap < (size_t)R.B * R.T.stride) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (sb->tr_dev) (void)hipFree(sb->tr_dev);
-        sb->tr_dev = nullptr; sb->tr_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&sb->tr_dev, (size_t)B * tr_stride * sizeof(double) + 256));
-        sb->tr_cap = (size_t)B * tr_stride;
+        if (sb.tr_dev) (void)hipFree(sb.tr_dev);
+        sb.tr_dev = nullptr; sb.tr_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&sb.tr_dev, (size_t)R.B * R.T.stride * sizeof(double) + 256));
+        sb.tr_cap = (size_t)R.B * R.T.stride;
     }
-    char *dev = sb->dev, *host = sb->host;
-    UpdArgs *hu = (UpdArgs *)(host + L.off_u);
-    const double tol = o.tol_gap;
-    const int64_t pools = cfmm_pool_count(ctx);
-    std::vector<SweepPointState> ps(B);
-    // the inputs that do not change from round to round, and the start prices
-    for (int p = 0; p < B; ++p) {
-        double *A = L.A(host, p);
+    R.dev = sb.dev; R.host = sb.host;
+    return CFMM_OK;
+}
+
+// the inputs that do not change from round to round, the start prices, and every point's first budget
+void sweep_stage_inputs(SweepRun &R, const double *c, const double *h, const int32_t *ctype, const double *nu0, double kink_tol)
+{
+    const int n = R.n;
+    for (int p = 0; p < R.B; ++p) {
+        double *A = R.L.A(R.host, p);
         std::memcpy(A, c + (size_t)p * n, n * sizeof(double));
         if (h) std::memcpy(A + n, h + (size_t)p * n, n * sizeof(double)); else std::memset(A + n, 0, n * sizeof(double));
-        int *ct = L.ctype(host, p);
+        int *ct = R.L.ctype(R.host, p);
         for (int j = 0; j < n; ++j) ct[j] = ctype ? ctype[(size_t)p * n + j] : CFMM_GE;
-        std::memcpy(L.O(host, p), nu0 + (size_t)p * n, n * sizeof(double));
-        // legs: short where kinks may have to be found (problem.py: _solve_kinks); a network without constant-sum pools is ONE leg
-        ps[p].budget = msum ? std::min(o.max_evals, pools <= 1000 ? 40 : 100) : o.max_evals;
-        ps[p].kink_tol = kink_tol > 0.0 ? kink_tol : 1e-3;
+        std::memcpy(R.L.O(R.host, p), nu0 + (size_t)p * n, n * sizeof(double));
+        R.ps[p].budget = sweep::first_budget(R.msum, R.pools, R.o.max_evals);
+        R.ps[p].kink_tol = kink_tol > 0.0 ? kink_tol : 1e-3;
     }
-    if (max_rounds < 1) max_rounds = 6;
-    const size_t lds = (size_t)tiny_lds_doubles(n) * sizeof(double);
-    const int threads = 64 * std::min(TINY_THREADS / 64, std::max(1, ea.ntiles));
+}
+
+// point p's pieces of the device's slab, as the kernels' argument record names them
+UpdArgs point_upd_args(const SweepLayout &L, char *dev, int p)
+{
+    const int n = L.n;
+    UpdArgs a = {};
+    a.n = n; a.nslices = 1;
+    double *dA = L.A(dev, p), *dO = L.O(dev, p), *dS = L.S(dev, p);
+    a.acc = nullptr;
+    a.c = dA; a.h = dA + n; a.off = dA + 2 * n; a.glo = dA + 3 * n; a.ghi = dA + 4 * n;
+    a.ctype = L.ctype(dev, p); a.grp = L.grp(dev, p);
+    a.nu_acc = dO; a.psi_acc = dO + n; a.st = L.st(dev, p);
+    a.nu = dS; a.psi_t = dS + n + 2; a.s = dS + 2 * n + 2; a.s_t = dS + 3 * n + 2; a.Gs = dS + 4 * n + 2; a.Gs_t = dS + 5 * n + 2; a.d = dS + 6 * n + 2; a.Ds = dS + 7 * n + 2;
+    a.S = a.Y = a.rho = nullptr;
+    a.ts = nullptr; a.batch = nullptr; a.hstat = nullptr;
+    return a;
+}
+
+// this round's unfinished points: their ties, bounds, tolerance and budget into the pinned slab (sweep_rules.hpp: round_head)
+void sweep_round_prepare(SweepRun &R)
+{
+    const SweepLayout &L = R.L;
+    const int n = R.n;
+    UpdArgs *hu = (UpdArgs *)(R.host + L.off_u);
+    R.active.clear();
+    for (int p = 0; p < R.B; ++p) {
+        sweep::PointState &S = R.ps[p];
+        if (S.done) continue;
+        if (sweep::exhausted(S, R.o.max_evals)) { S.done = true; continue; }
+        double *A = L.A(R.host, p);
+        const sweep::RoundHead hd = sweep::round_head(S, R.sc, n, A, L.ctype(R.host, p), L.flags(R.host, p), L.grp(R.host, p), A + 2 * n, A + 3 * n, A + 4 * n);
+        UpdArgs a = point_upd_args(L, R.dev, p);
+        a.ng = hd.ng; a.M = R.o.memory;
+        a.tol_gap = a.tol_infeas = hd.tol_factor * R.o.tol_gap;
+        a.pg_rule = hd.pg_rule;
+        a.armijo = R.o.armijo; a.max_step = R.o.max_step;
+        a.max_evals = S.budget;
+        a.pool_flags = (hd.tied && R.msum) ? L.flags(R.dev, p) : nullptr;
+        hu[R.active.size()] = a;
+        R.active.push_back(p);
+    }
+}
+
+// one round on the device: inputs down, start + solve of every unfinished point, results up
+int sweep_round_launch(SweepRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    const SweepLayout &L = R.L;
+    const int na = (int)R.active.size();
+    const size_t lds = (size_t)tiny_lds_doubles(R.n) * sizeof(double);
+    const int threads = 64 * std::min(TINY_THREADS / 64, std::max(1, R.ea.ntiles));
+    HIP_TRY(ctx, hipMemcpyAsync(R.dev, R.host, L.off_s, hipMemcpyHostToDevice, ctx->stream));
+    UpdArgs lead = ((const UpdArgs *)(R.host + L.off_u))[0];
+    lead.batch = (const UpdArgs *)(R.dev + L.off_u);
+    hipLaunchKernelGGL(start_kernel<true>, dim3(na), dim3(64), upd_lds_bytes(R.n), ctx->stream, lead, (const double *)nullptr, (double *)nullptr, 0ll, (DevState *)nullptr, 0);
+    hipLaunchKernelGGL(solve_tiny_kernel<true>, dim3(na), dim3(threads), lds, ctx->stream, R.ea, lead, 0);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(R.host + L.off_o, R.dev + L.off_o, (size_t)R.B * L.o_stride * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
-    std::vector<int> active;
-    for (int round = 0; round < 8 * max_rounds; ++round) {
-        active.clear();
-        for (int p = 0; p < B; ++p) {
-            SweepPointState &S = ps[p];
-            if (S.done) continue;
-            if (S.evals >= 4 * o.max_evals) { S.done = true; continue; }
-            // ---- this round's ties, bounds, tolerance and budget of point p (problem.py: _solve_kinks, the head of its loop) ----
-            SweepTies ties; ties.init(n);
-            int *fl = L.flags(host, p);
-            for (int i = 0; i < msum; ++i) fl[i] = 0;
-            for (auto it = S.tied.begin(); it != S.tied.end();) {
-                const int i = it->first;
-                if (ties.tie(sc.ia[i], sc.ib[i], it->second.sgn * std::log(sc.fee[i]))) { fl[i] = 1; ++it; }
-                else { S.banned.insert({i, it->second.sgn}); it = S.tied.erase(it); }
-            }
-            double *A = L.A(host, p);
-            double *off = A + 2 * n, *glo = A + 3 * n, *ghi = A + 4 * n;
-            int *grp = L.grp(host, p);
-            const int *ct = L.ctype(host, p);
-            int ng = n;
-            if (!S.tied.empty()) { ng = ties.groups(grp); for (int j = 0; j < n; ++j) off[j] = ties.off[j]; }
-            else for (int j = 0; j < n; ++j) { grp[j] = j; off[j] = 0.0; }
-            for (int r = 0; r < n; ++r) { glo[r] = -INFINITY; ghi[r] = INFINITY; }
-            double scmax = 0.0;
-            for (int j = 0; j < n; ++j) scmax = std::max(scmax, A[j]);
-            const double smid = scmax > 0.0 ? std::log(scmax) : 0.0;
-            for (int j = 0; j < n; ++j) {                 // (bounds_into_mirror)
-                double l = smid - 100.0, u = smid + 100.0;                // (as bounds_into_mirror: no price runs off to an underflow)
-                if (ct[j] == CFMM_GE) { l = A[j] > 0.0 ? std::log(A[j]) : smid - 100.0; u = INFINITY; }
-                else if (ct[j] == CFMM_FREE) l = u = std::log(A[j]);
-                l -= off[j]; u -= off[j];
-                if (l > glo[grp[j]]) glo[grp[j]] = l;
-                if (u < ghi[grp[j]]) ghi[grp[j]] = u;
-            }
-            UpdArgs a = {};
-            a.n = n; a.ng = ng; a.M = o.memory; a.nslices = 1;
-            double *dA = L.A(dev, p), *dO = L.O(dev, p), *dS = L.S(dev, p);
-            a.acc = nullptr;
-            a.c = dA; a.h = dA + n; a.off = dA + 2 * n; a.glo = dA + 3 * n; a.ghi = dA + 4 * n;
-            a.ctype = L.ctype(dev, p); a.grp = L.grp(dev, p);
-            a.nu_acc = dO; a.psi_acc = dO + n; a.st = L.st(dev, p);
-            a.nu = dS; a.psi_t = dS + n + 2; a.s = dS + 2 * n + 2; a.s_t = dS + 3 * n + 2; a.Gs = dS + 4 * n + 2; a.Gs_t = dS + 5 * n + 2; a.d = dS + 6 * n + 2; a.Ds = dS + 7 * n + 2;
-            a.S = a.Y = a.rho = nullptr;
-            const bool tied = !S.tied.empty();
-            a.tol_gap = a.tol_infeas = tied ? 0.01 * tol : tol;
-            a.pg_rule = tied ? 1 : 0;
-            a.armijo = o.armijo; a.max_step = o.max_step;
-            a.max_evals = S.budget;
-            a.ts = nullptr; a.batch = nullptr; a.hstat = nullptr;
-            a.pool_flags = (tied && msum) ? L.flags(dev, p) : nullptr;
-            hu[active.size()] = a;
-            active.push_back(p);
-        }
-        if (active.empty()) break;
-        const int na = (int)active.size();
-        // ---- one round on the device: inputs down, start + solve of every unfinished point, results up ----
-        HIP_TRY(ctx, hipMemcpyAsync(dev, host, L.off_s, hipMemcpyHostToDevice, ctx->stream));
-        UpdArgs lead = hu[0];
-        lead.batch = (const UpdArgs *)(dev + L.off_u);
-        hipLaunchKernelGGL(start_kernel<true>, dim3(na), dim3(64), upd_lds_bytes(n), ctx->stream, lead, (const double *)nullptr, (double *)nullptr, 0ll, (DevState *)nullptr, 0);
-        hipLaunchKernelGGL(solve_tiny_kernel<true>, dim3(na), dim3(threads), lds, ctx->stream, ea, lead, 0);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(host + L.off_o, dev + L.off_o, (size_t)B * L.o_stride * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        // ---- the host's half of the active-set loop (problem.py: _solve_kinks, the tail of its loop) ----
-        for (int p : active) {
-            SweepPointState &S = ps[p];
-            const DevState st = *L.st(host, p);
-            S.st = st; S.evals += st.evals; S.iters += st.iters; S.rounds += 1;
-            const int status = st.status ? st.status : 3;
-            if (!std::isfinite(st.f)) { S.done = true; S.st.status = CFMM_E_NUMERIC; continue; }
-            const double *nu = L.O(host, p), *psi = nu + n;
-            const double *A = L.A(host, p);
-            if (status == 1) {
-                if (S.tied.empty()) { S.done = true; continue; }
-                const bool ok = sweep_recover_fills(n, nu, psi, A, A + n, L.ctype(host, p), sc, S.tied, tol, S.theta);
-                std::vector<int> bad;
-                { int k = 0; for (auto &kv : S.tied) { if (!(S.theta[k] > 1e-9 && S.theta[k] < 1.0 - 1e-9)) bad.push_back(kv.first); ++k; } }
-                if (ok && bad.empty()) { S.done = true; S.fills_ok = true; continue; }
-                if (!bad.empty()) {                        // fully on / fully off after all: back to bang-bang
-                    int k = 0;
-                    std::map<int, double> th_of;
-                    for (auto &kv : S.tied) th_of[kv.first] = S.theta[k++];
-                    for (int i : bad) {
-                        const SweepTie rec = S.tied[i];
-                        S.tied.erase(i);
-                        S.banned.insert({i, rec.sgn});
-                        // a guessed kink that carries no trade: the optimum sits on the pool's OTHER kink (fee bands narrower than a leg resolves)
-                        if (rec.loose && th_of[i] <= 1e-9 && !S.banned.count({i, -rec.sgn})) S.tied[i] = SweepTie{-rec.sgn, false};
-                    }
-                    S.theta.clear();
-                    continue;
-                }
-            }
-            std::map<int, SweepTie> fresh;
-            sweep_kink_candidates(nu, sc, S.kink_tol, S.banned, S.tied, false, fresh);
-            double wide = S.kink_tol;
-            while (fresh.empty() && status != 1 && wide < 0.05) { wide *= 10.0; sweep_kink_candidates(nu, sc, wide, S.banned, S.tied, true, fresh); }
-            if (!fresh.empty()) {
-                for (auto &kv : fresh) S.tied[kv.first] = kv.second;
-                for (auto it = S.banned.begin(); it != S.banned.end();) { if (fresh.count(it->first)) ++it; else it = S.banned.erase(it); }      // bans expire when the active set changes
-            } else if (status == 3 && S.budget < o.max_evals) S.budget = std::min(o.max_evals, 2 * S.budget);     // no kink in sight: longer legs
-            else if (S.kink_tol < 0.05) S.kink_tol *= 10.0;
-            else S.done = true;
-            S.theta.clear();
-        }
+    return CFMM_OK;
+}
+
+// the host's half of the active-set loop, for every point that ran this round (sweep_rules.hpp: round_tail)
+void sweep_round_decide(SweepRun &R)
+{
+    const SweepLayout &L = R.L;
+    const int n = R.n;
+    for (int p : R.active) {
+        const DevState st = *L.st(R.host, p);
+        const sweep::LegResult leg = {st.status, st.evals, st.iters, st.f, st.primal, st.gap, st.infeas, st.pg};
+        const double *nu = L.O(R.host, p), *A = L.A(R.host, p);
+        sweep::round_tail(R.ps[p], leg, n, nu, nu + n, A, A + n, L.ctype(R.host, p), R.sc, R.o.tol_gap, R.o.max_evals);
     }
-    // ---- the tenders of every point at its accepted prices (the tied pools' come out as zero: the caller scales their full fill by theta) ----
+}
+
+// the tenders of every point at its accepted prices (the tied pools' come out as zero: the caller scales their full fill by theta);
+// closes the device's timing either way
+int sweep_read_tenders(SweepRun &R, double *trades_out)
+{
+    cfmm_ctx *ctx = R.ctx;
+    const SweepLayout &L = R.L;
+    const size_t tr_stride = R.T.stride;
     if (trades_out && tr_stride > 0) {
-        double *td = sb->tr_dev;
-        const double *nu_d = L.O(dev, 0);
+        double *td = ctx->sweep.tr_dev;
+        const double *nu_d = L.O(R.dev, 0);
         const int nus = (int)L.o_stride;
-        const int *fl_d = msum ? L.flags(dev, 0) : nullptr;
+        const int *fl_d = R.msum ? L.flags(R.dev, 0) : nullptr;
         const int fls = (int)(2 * L.a_stride);
-        size_t boff = 0;
         const dim3 blk(256);
         for (int k = 0; k < CFMM_POOL_KINDS2; ++k) {
             Bucket2 b = ctx->pools->r2[k].b;
             if (b.m == 0) continue;
-            const dim3 grid((unsigned)((b.m + 255) / 256), (unsigned)B);
-            double *dd = td + boff, *dl = dd + 2 * b.m;
+            const dim3 grid((unsigned)((b.m + 255) / 256), (unsigned)R.B);
+            double *dd = td + R.T.off2[k], *dl = dd + 2 * b.m;
             with_int<0, 4>(k, [&](auto K) {
                 hipLaunchKernelGGL(trades2_sweep_kernel<K>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride, fl_d, fls);
             });
-            boff += 4 * (size_t)b.m;
         }
         for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) {
             const BucketN &b = ctx->pools->rn[k].b;
             if (b.m == 0) continue;
-            const dim3 grid((unsigned)((b.m + 255) / 256), (unsigned)B);
-            double *dd = td + boff, *dl = dd + (size_t)k * b.m;
+            const dim3 grid((unsigned)((b.m + 255) / 256), (unsigned)R.B);
+            double *dd = td + R.T.offn[k], *dl = dd + (size_t)k * b.m;
             with_int<3, 8>(k, [&](auto K) {
                 hipLaunchKernelGGL(tradesn_sweep_kernel<K>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride);
             });
-            boff += 2 * (size_t)k * b.m;
         }
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
-        { int rc = download_staged(ctx, trades_out, td, (size_t)B * tr_stride * sizeof(double)); if (rc) return rc; }
+        { int rc = download_staged(ctx, trades_out, td, (size_t)R.B * tr_stride * sizeof(double)); if (rc) return rc; }
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     } else {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
-    const auto t1 = std::chrono::steady_clock::now();
-    float ms = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1));
+    R.t1 = std::chrono::steady_clock::now();
+    HIP_TRY(ctx, hipEventElapsedTime(&R.ms, ctx->ev_t0, ctx->ev_t1));
+    return CFMM_OK;
+}
+
+// every point's prices, net trade, fills and statistics to the caller; CFMM_E_NUMERIC if some point's dual value was not finite
+int sweep_report(SweepRun &R, double *nu_out, double *psi_out, double *theta_out, int32_t *tsgn_out, cfmm_stats *out, int32_t *rounds_out)
+{
+    const int n = R.n, msum = R.msum;
     int rc_all = CFMM_OK;
-    for (int p = 0; p < B; ++p) {
-        const SweepPointState &S = ps[p];
-        std::memcpy(nu_out + (size_t)p * n, L.O(host, p), n * sizeof(double));
-        std::memcpy(psi_out + (size_t)p * n, L.O(host, p) + n, n * sizeof(double));
+    for (int p = 0; p < R.B; ++p) {
+        const sweep::PointState &S = R.ps[p];
+        std::memcpy(nu_out + (size_t)p * n, R.L.O(R.host, p), n * sizeof(double));
+        std::memcpy(psi_out + (size_t)p * n, R.L.O(R.host, p) + n, n * sizeof(double));
         for (int i = 0; i < msum; ++i) { theta_out[(size_t)p * msum + i] = std::numeric_limits<double>::quiet_NaN(); tsgn_out[(size_t)p * msum + i] = 0; }
         if (S.fills_ok) { int k = 0; for (auto &kv : S.tied) { theta_out[(size_t)p * msum + kv.first] = S.theta[k++]; tsgn_out[(size_t)p * msum + kv.first] = kv.second.sgn; } }
         cfmm_stats *s = out + p;
@@ -4719,17 +4496,44 @@ int cfmm_solve_sweep(cfmm_ctx *ctx, int B, const double *c, const double *h, con
         s->evals = S.evals; s->iters = S.iters; s->status = S.st.status ? S.st.status : 3;
         s->n_ranks = 1;
         s->dual_value = S.st.f; s->primal_value = S.st.primal; s->gap = S.st.gap; s->infeas = S.st.infeas;
-        s->wall_seconds = std::chrono::duration<double>(t1 - t0).count();          // (of the whole sweep)
-        s->device_seconds = ms * 1e-3;
+        s->wall_seconds = std::chrono::duration<double>(R.t1 - R.t0).count();          // (of the whole sweep)
+        s->device_seconds = R.ms * 1e-3;
         s->pg = S.st.pg;
-        s->pool_subproblems = (int64_t)S.evals * pools;
+        s->pool_subproblems = (int64_t)S.evals * R.pools;
         s->method = CFMM_METHOD_LBFGS;
         if (rounds_out) rounds_out[p] = S.rounds;
-        if (S.st.status == CFMM_E_NUMERIC) rc_all = fail(ctx, CFMM_E_NUMERIC, "solve_sweep: dual value of point %d is not finite", p);
+        if (S.st.status == CFMM_E_NUMERIC) rc_all = fail(R.ctx, CFMM_E_NUMERIC, "solve_sweep: dual value of point %d is not finite", p);
     }
     return rc_all;
 }
 
+}  // namespace
+
+int cfmm_solve_sweep(cfmm_ctx *ctx, int B, const double *c, const double *h, const int32_t *ctype, const double *nu0,
+                     int64_t m_sum, const int32_t *sum_ia, const int32_t *sum_ib, const double *sum_fee, const double *sum_Ra, const double *sum_Rb,
+                     const cfmm_opts *opts_in, double kink_tol, int max_rounds,
+                     double *nu_out, double *psi_out, double *theta_out, int32_t *tsgn_out, double *trades_out, cfmm_stats *out, int32_t *rounds_out)
+{
+    if (!ctx || B < 1 || !c || !nu0 || !nu_out || !psi_out || !out) return ctx ? fail(ctx, CFMM_E_ARG, "solve_sweep: NULL argument or no points") : CFMM_E_ARG;
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
+    const sweep::SumCols sc{m_sum, sum_ia, sum_ib, sum_fee, sum_Ra, sum_Rb};
+    cfmm_opts o; EvalArgs ea;
+    { int rc = sweep_check_args(ctx, opts_in, B, c, h, ctype, nu0, sc, theta_out, tsgn_out, o, ea); if (rc) return rc; }
+    SweepRun R(ctx, o, ea, B, sc, max_rounds);
+    { int rc = sweep_reserve(R, trades_out != nullptr); if (rc) return rc; }
+    sweep_stage_inputs(R, c, h, ctype, nu0, kink_tol);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    R.t0 = std::chrono::steady_clock::now();
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
+    for (int round = 0; round < 8 * R.max_rounds; ++round) {
+        sweep_round_prepare(R);
+        if (R.active.empty()) break;
+        { int rc = sweep_round_launch(R); if (rc) return rc; }
+        sweep_round_decide(R);
+    }
+    { int rc = sweep_read_tenders(R, trades_out); if (rc) return rc; }
+    return sweep_report(R, nu_out, psi_out, theta_out, tsgn_out, out, rounds_out);
+}
 
 int cfmm_get_trades2(cfmm_ctx *ctx, int kind, double *delta, double *lambda)
 {
@@ -4739,8 +4543,7 @@ int cfmm_get_trades2(cfmm_ctx *ctx, int kind, double *delta, double *lambda)
     if (kind == CFMM_POOL_SUM2) b.flags = ctx->flags2;
     if (b.m == 0) return CFMM_OK;
     if (ctx->pt.tr_ovr_valid) {                 // the library's own kink loop left the tenders (solve_tiny_kinks)
-        size_t off = 0;
-        for (int k = 0; k < kind; ++k) off += 4 * (size_t)ctx->pools->r2[k].b.m;
+        const size_t off = trade_layout(*ctx->pools).off2[kind];
         if (delta) std::memcpy(delta, ctx->pt.tr_ovr.data() + off, 2 * (size_t)b.m * sizeof(double));
         if (lambda) std::memcpy(lambda, ctx->pt.tr_ovr.data() + off + 2 * (size_t)b.m, 2 * (size_t)b.m * sizeof(double));
         return CFMM_OK;
@@ -4899,8 +4702,7 @@ int cfmm_apply_trades(cfmm_ctx *ctx, int fee_mode, cfmm_apply_info *info)
     // the kink loop's own tenders (two-asset buckets, partial fills included) travel to the device once; both passes read them there
     const double *ovr = nullptr;
     if (ctx->pt.tr_ovr_valid) {
-        size_t len = 0;
-        for (int k = 0; k < CFMM_POOL_KINDS2; ++k) len += 4 * (size_t)ps.r2[k].b.m;
+        const size_t len = trade_layout(ps).two_asset();
         if (ctx->pt.tr_ovr.size() < len) return fail(ctx, CFMM_E_STATE, "%s: the kink loop's tenders do not match the resident buckets", who);
         if (len > ctx->apply_ovr_cap) {
             if (ctx->apply_ovr) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->apply_ovr); ctx->apply_ovr = nullptr; ctx->apply_ovr_cap = 0; }

@@ -12,10 +12,10 @@
 // The state reaches global memory once, when the solve ends.
 #pragma once
 #include "onewave.hpp"
+#include "tiny_limits.hpp"                 // TINY_N
 
 namespace cfmm {
 
-constexpr int TINY_N = 64;                 // tokens (and price groups): one per lane of wave 0
 constexpr int TINY_THREADS = 512;          // <= 8 waves walk the tiles (256 VGPRs per thread: tile code + update in one kernel)
 constexpr int TINY_MAX_TILES = 64;
 

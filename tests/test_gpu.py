@@ -353,6 +353,50 @@ def test_c_abi_solve_settles_constant_sum_kinks_itself_on_small_networks(seed, u
     p.close(); q.close()
 
 
+def _sweep_record_cases():
+    import json
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if os.path.join(root, "tools") not in sys.path:
+        sys.path.insert(0, os.path.join(root, "tools"))
+    import sweep_records
+    with open(os.path.join(root, "tests", "golden", "sweep_records.json")) as f:
+        want = json.load(f)["cases"]
+    cases = dict(sweep_records.cases())
+    assert set(want) <= set(cases) and "two_asset_50" in want and sum(1 for k in want if k.startswith("tiny")) >= 4
+    return [(name, cases[name], want[name]) for name in sorted(want)]
+
+
+@pytest.mark.parametrize("name,run,want", [pytest.param(*c, id=c[0]) for c in _sweep_record_cases()])
+def test_swept_solve_repeats_the_recorded_rounds(name, run, want):
+    """tools/sweep_records.py: cfmm_solve_sweep straight through the binding on the two-asset sweep at its 50 points, the six random
+    tiny networks of the test above under their dozen utilities, a network without constant-sum pools (one leg per point), and the
+    shipped arbitrage instance through cfmm_solve with the default method (the library's one-point sweep).  The golden file holds what
+    the build BEFORE cfmm_solve_sweep was divided into rules (sweep_rules.hpp) and phases recorded in TEN runs (the first three agreed
+    bit for bit on a case that the later ones moved).  Per point the status, evaluations, iterations, rounds, method and the tied pools'
+    signs are those exactly.  The network without constant-sum pools is left out: its evaluation counts did not repeat on that build.
+    Theta, the dual value and psi: the one-workgroup solve is NOT run-to-run deterministic where several waves add into the LDS tile.
+    Two cases (tiny0_arbitrage, the arbitrage instance) repeated bit for bit in all runs and are held to that.  The others spread by up
+    to 1.1e-13 in psi, 3.6e-14 in the value and 1.3e-15 in theta -- 6.8e-4 in tiny2_liquidate, whose tied pools share tokens so that
+    the fills are not unique -- and each quantity is held to ten times its own case's spread (a quantity that happened to repeat in a
+    case that did not: ten times the case's largest spread).  The file's header and per-case `spread` hold the figures."""
+    import sweep_records
+    got = run()
+    assert len(got) == len(want["points"])
+    val = lambda h: np.array([float.fromhex(x) for x in h])
+    for b, (g, w) in enumerate(zip(got, want["points"])):
+        print(name, b, {k: g[k] for k in sweep_records.INTS}, g["theta"])
+        for k in sweep_records.INTS:
+            assert g[k] == w[k], (name, b, k, g, w)
+        for q in sweep_records.RAW:
+            tol = want["tolerance"][q]
+            if tol == 0.0:
+                assert g["raw"][q] == w["raw"][q], (name, b, q, g, w)
+            else:
+                vg, vw = val(g["raw"][q]), val(w["raw"][q])
+                assert np.array_equal(np.isnan(vg), np.isnan(vw)) and np.nanmax(np.abs(vg - vw), initial=0.0) <= tol, (name, b, q, g, w)
+
+
 def _kink_network(seed):
     """constant-product and constant-sum pools only (what cfmm_solve_batch takes) of the reference's size, three constant-sum pools
     more, as in test_c_abi_solve_settles_constant_sum_kinks_itself_on_small_networks"""

@@ -556,15 +556,19 @@ int main()
 
 def _newton_rules_program(tmp_path, name, body):
     """a stand-alone HOST program over csrc/newton_rules.hpp (nothing of HIP in it): compiled -Wall -Werror, run, its output lines"""
+    return _rules_program(tmp_path, "newton_rules.hpp", "newton", name, body)
+
+
+def _rules_program(tmp_path, header, namespace, name, body, helpers=""):
     import shutil
     import subprocess
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc missing")
     src = tmp_path / f"{name}.cpp"
-    src.write_text('#include "newton_rules.hpp"\n#include <cstdio>\n#include <vector>\nusing namespace newton;\n'
+    src.write_text(f'#include "{header}"\n#include <cstdio>\n#include <vector>\nusing namespace {namespace};\n'
                    'inline void row(const char *k, const double *v, int n) { printf("%s", k); for (int i = 0; i < n; ++i) printf(" %.17g", v[i]); printf("\\n"); }\n'
-                   "int main()\n{\n" + body + "\n    return 0;\n}\n")
+                   + helpers + "int main()\n{\n" + body + "\n    return 0;\n}\n")
     exe = tmp_path / name
     r = subprocess.run([hipcc, "-O1", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "cfmm-routing-code_amd", "csrc"), str(src), "-o", str(exe)],
                        capture_output=True, text=True, timeout=300)
@@ -820,6 +824,344 @@ def test_second_order_token_rules_on_one_token_of_each_kind(tmp_path):
         _same_numbers(got["s2"][i], s2); _same_numbers(got["nu2"][i], nu2); _same_numbers(got["slo2"][i], slo2)
         assert (s2[0] + slo2[0]) == lob[0] and nu2[2] == nu[2] and nu2[4] == nu[4]      # (the bound holds token 0; pinned prices stay)
     assert [float(x) for x in got["collapsed"][0]] == [0.0, 1.0, 0.0]                  # (60 e-foldings under the start; a pinned token does not count)
+
+
+_SWEEP_HELPERS = r'''
+#include <cstdint>
+inline void rowi(const char *k, const int *v, int n) { printf("%s", k); for (int i = 0; i < n; ++i) printf(" %d", v[i]); printf("\n"); }
+// a point's state on one line: done fills_ok status evals iters rounds budget kink_tol | tied: i sgn loose ... | banned: i sgn ... | theta ...
+inline void show(const char *k, const PointState &S)
+{
+    printf("%s %d %d %d %d %d %d %d %.17g |", k, (int)S.done, (int)S.fills_ok, S.st.status, S.evals, S.iters, S.rounds, S.budget, S.kink_tol);
+    for (auto &kv : S.tied) printf(" %d %d %d", kv.first, kv.second.sgn, (int)kv.second.loose);
+    printf(" |");
+    for (auto &b : S.banned) printf(" %d %d", b.first, b.second);
+    printf(" |");
+    for (double t : S.theta) printf(" %.17g", t);
+    printf("\n");
+}
+'''
+
+
+def _sweep_rules_program(tmp_path, name, body):
+    """a stand-alone HOST program over csrc/sweep_rules.hpp (nothing of HIP in it): compiled -Wall -Werror, run, its output lines"""
+    return _rules_program(tmp_path, "sweep_rules.hpp", "sweep", name, body, _SWEEP_HELPERS)
+
+
+def _keyed(lines):
+    out = {}
+    for l in lines:
+        k, _, rest = l.partition(" ")
+        out.setdefault(k, []).append(rest)
+    return out
+
+
+def _cvec(name, v, typ="double"):
+    return "const %s %s[] = {%s};" % (typ, name, ", ".join(repr(float(x)) if typ == "double" else str(int(x)) for x in v))
+
+
+def test_swept_solve_ties_are_the_weighted_union_find_of_the_python_loop(tmp_path):
+    """csrc/sweep_rules.hpp: Ties.  A chain 0-1-2 with offsets d01, d12 gives off[0] - off[2] = d01 + d12; tying 0-2 again with that sum
+    is accepted, with the sum + 1e-6 refused; groups() numbers the groups in the order of their roots.  Then the same list of ties
+    (a refused one among them) through cfmm.problem._Ties: the tie results and group ids equal, the offsets to 1e-15 relative -- both
+    add the same doubles in the same order (find compresses from the top of the path down in both)."""
+    from cfmm.problem import _Ties
+    d01, d12 = 0.25, -0.6
+    pairs = [(3, 1, 0.11), (1, 6, -0.07), (0, 7, 0.3), (7, 3, 0.02), (0, 6, 0.5), (4, 5, -0.2), (5, 4, 0.2), (2, 5, 0.013)]
+    got = _keyed(_sweep_rules_program(tmp_path, "ties", r'''
+    { Ties t; t.init(6);
+      const int a = t.tie(0, 1, %r), b = t.tie(1, 2, %r);
+      t.find(0); t.find(2);
+      const double v[] = {(double)a, (double)b, t.off[0] - t.off[2], (double)t.tie(0, 2, %r + %r), (double)t.tie(0, 2, %r + %r + 1e-6), (double)t.tie(4, 5, 0.1)};
+      row("chain", v, 6);
+      int grp[6]; const int ng = t.groups(grp); rowi("chain_grp", grp, 6); printf("chain_ng %%d\n", ng); }
+    { Ties t; t.init(8);
+      const int a[] = {%s}, b[] = {%s}; const double d[] = {%s};
+      int ok[%d];
+      for (int q = 0; q < %d; ++q) ok[q] = t.tie(a[q], b[q], d[q]);
+      rowi("ok", ok, %d);
+      int grp[8]; const int ng = t.groups(grp); rowi("grp", grp, 8); printf("ng %%d\n", ng); row("off", t.off, 8); }
+    ''' % (d01, d12, d01, d12, d01, d12, ", ".join(str(p[0]) for p in pairs), ", ".join(str(p[1]) for p in pairs),
+           ", ".join(repr(p[2]) for p in pairs), len(pairs), len(pairs), len(pairs))))
+    assert [float(x) for x in got["chain"][0].split()] == [1.0, 1.0, d01 + d12, 1.0, 0.0, 1.0]
+    # roots: tokens 0, 1, 2 hang under 2, token 3 is its own, 4 hangs under 5 -- numbered in the order of the roots 2 < 3 < 5
+    assert got["chain_grp"][0].split() == ["0", "0", "0", "1", "2", "2"] and got["chain_ng"] == ["3"]
+    t = _Ties(8)
+    ok = [int(t.tie(a, b, d)) for a, b, d in pairs]
+    grp, off, ng = t.groups()
+    assert ok == [1, 1, 1, 1, 0, 1, 1, 1]                       # (0-6 is already fixed at 0.3 + 0.02 + 0.11 - 0.07; 5-4 repeats 4-5)
+    assert [int(x) for x in got["ok"][0].split()] == ok
+    assert [int(x) for x in got["grp"][0].split()] == list(grp) and int(got["ng"][0]) == ng == 2
+    _same_numbers(got["off"][0].split(), list(off))
+
+
+def test_swept_solve_box_least_squares_against_the_enumerated_faces(tmp_path):
+    """csrc/sweep_rules.hpp: box_lsq.  K = 2 with A = I: the solution is b clipped to the box, coordinate by coordinate (inside, one
+    coordinate over 1, one under 0 and one over 1).  A coupled 3 x 2 system whose free solution lies outside: the optimum among the nine
+    face assignments {free, 0, 1}^2, enumerated here with NumPy, to 1e-9.  K = 8 with the free solution outside: the clipped free
+    solution (no enumeration beyond 7 unknowns).  Two equal columns: finite values inside [0, 1]."""
+    import itertools
+    rng = np.random.default_rng(5)
+    cases = [("i0", np.eye(2), [0.3, 0.6]), ("i1", np.eye(2), [1.4, 0.5]), ("i2", np.eye(2), [-0.2, 1.7])]
+    A3 = np.array([[1.0, 0.5], [0.2, 1.0], [0.7, -0.3]])
+    cases.append(("c3", A3, A3 @ np.array([1.3, 0.4]) + np.array([0.02, -0.01, 0.03])))
+    A8 = np.eye(8) + 0.25 * (np.abs(np.subtract.outer(np.arange(8), np.arange(8))) == 1)
+    cases.append(("k8", A8, A8 @ np.array([1.5, -0.4, 0.3, 0.6, 0.2, 1.2, 0.5, 0.1]) + 0.01 * rng.standard_normal(8)))
+    cases.append(("rd", np.array([[1.0, 1.0], [2.0, 2.0], [0.5, 0.5]]), [0.6, 1.2, 0.3]))
+    body = ""
+    for nm, A, b in cases:
+        A = np.asarray(A, float)
+        body += ("    { std::vector<double> A = {%s}, b = {%s}, th; box_lsq(A, b, %d, %d, th); row(\"%s\", th.data(), (int)th.size()); }\n"
+                 % (", ".join(repr(float(x)) for x in A.ravel()), ", ".join(repr(float(x)) for x in b), A.shape[0], A.shape[1], nm))
+    got = {k: [float(x) for x in v[0].split()] for k, v in _keyed(_sweep_rules_program(tmp_path, "lsq", body)).items()}
+    for nm, want in (("i0", (0.3, 0.6)), ("i1", (1.0, 0.5)), ("i2", (0.0, 1.0))):
+        assert np.abs(np.array(got[nm]) - want).max() <= 1e-12, (nm, got[nm])       # (the ridge is 1e-14 relative)
+    _, A, b = cases[3]
+    assert not np.all((np.linalg.lstsq(A, b, rcond=None)[0] >= 0) & (np.linalg.lstsq(A, b, rcond=None)[0] <= 1))
+    best = None
+    for faces in itertools.product((None, 0.0, 1.0), repeat=2):
+        th = np.array([0.0 if f is None else f for f in faces])
+        free = [k for k, f in enumerate(faces) if f is None]
+        if free:
+            th[free] = np.linalg.lstsq(A[:, free], b - A @ th, rcond=None)[0]
+            if not np.all((th[free] >= 0) & (th[free] <= 1)):
+                continue
+        r = float(np.sum((A @ th - b) ** 2))
+        if best is None or r < best[0]:
+            best = (r, th)
+    assert np.abs(np.array(got["c3"]) - best[1]).max() <= 1e-9, (got["c3"], best)
+    _, A, b = cases[4]
+    free = np.linalg.solve(A, b)
+    assert free.max() > 1 and free.min() < 0
+    assert np.abs(np.array(got["k8"]) - np.clip(free, 0, 1)).max() <= 1e-9, (got["k8"], free)
+    assert len(got["rd"]) == 2 and all(np.isfinite(v) and 0.0 <= v <= 1.0 for v in got["rd"]), got["rd"]
+
+
+# a 3-token point with ONE constant-sum pool (tokens 0 -> 1, fee g, reserves Ra, Rb) tied on its a->b kink: the full fill tenders
+# Rb / g of token 0 and drains Rb of token 1.  Tokens 0 and 1 are equalities, token 2 a GE token sitting ON its bound nu = c
+_FILL = dict(g=0.997, Ra=7.0, Rb=10.0, nu=[0.997 * 2.0, 2.0, 3.0], c=[0.0, 0.0, 3.0], ctype=[1, 1, 0], surplus=0.7)
+
+
+def _fill_psi(theta):
+    """net trade of the rest of the network that a fill of theta balances exactly on tokens 0 and 1"""
+    f = _FILL
+    return [theta * f["Rb"] / f["g"], -theta * f["Rb"], f["surplus"]]
+
+
+_FILL_DECL = (_cvec("ia", [0], "int32_t") + _cvec("ib", [1], "int32_t") + _cvec("fee", [_FILL["g"]]) + _cvec("Ra", [_FILL["Ra"]]) + _cvec("Rb", [_FILL["Rb"]])
+              + " const SumCols sc{1, ia, ib, fee, Ra, Rb};" + _cvec("nu", _FILL["nu"]) + _cvec("c", _FILL["c"]) + _cvec("h", [0, 0, 0]) + _cvec("ct", _FILL["ctype"], "int32_t"))
+
+
+def test_swept_solve_recovers_the_fill_that_balances_the_tied_pool(tmp_path):
+    """csrc/sweep_rules.hpp: recover_fills on a 3-token point built by hand (above) so that theta = 0.386 balances the two EQ tokens
+    exactly: accepted, theta to 1e-12.  A perturbation of psi orthogonal to the pool's direction (it moves no theta, all of it is
+    residual) of 100 x tol x scale is refused, of 1 x tol x scale accepted (the bar is 10 x tol).  The GE token at its bound carries a
+    positive surplus throughout and does not count; the same surplus on a GE token OFF its bound must balance, and is refused."""
+    f, tol, theta = _FILL, 1e-6, 0.386
+    psi = np.array(_fill_psi(theta))
+    nu = np.array(f["nu"])
+    Acol = np.array([-f["Rb"] / f["g"] * nu[0], f["Rb"] * nu[1]])          # the pool's column on the two tokens that must balance
+    v = np.array([Acol[1], -Acol[0]]); v /= np.abs(v).sum()               # orthogonal to it, |v|_1 = 1
+    scale = max(1.0, float(np.sum(np.abs(nu * np.abs(psi)))))
+    body = "    " + _FILL_DECL + " (void)c;\n    std::map<int, Tie> tied; tied[0] = Tie{1, false}; std::vector<double> th;\n"
+    runs = [("exact", psi, f["c"])]
+    for nm, mult in (("far", 100.0), ("near", 1.0)):
+        p = psi.copy(); p[:2] += mult * tol * scale * v / nu[:2]
+        runs.append((nm, p, f["c"]))
+    runs.append(("offbound", psi, [0.0, 0.0, 1.0]))
+    for nm, p, c in runs:
+        body += ("    { %s %s const int ok = recover_fills(3, nu, psi, c2, h, ct, sc, tied, %r, th); const double o[] = {(double)ok, th[0]}; row(\"%s\", o, 2); }\n"
+                 % (_cvec("psi", p), _cvec("c2", c), tol, nm))
+    got = {k: [float(x) for x in r[0].split()] for k, r in _keyed(_sweep_rules_program(tmp_path, "fills", body)).items()}
+    assert got["exact"][0] == 1.0 and abs(got["exact"][1] - theta) <= 1e-12, got["exact"]
+    assert got["far"][0] == 0.0 and abs(got["far"][1] - theta) <= 1e-9, got["far"]
+    assert got["near"][0] == 1.0, got["near"]
+    assert got["offbound"][0] == 0.0, got["offbound"]
+
+
+def test_swept_solve_finds_the_pools_that_sit_on_a_kink(tmp_path):
+    """csrc/sweep_rules.hpp: kink_candidates, one pool over tokens (0, 1), log-price ratio r, lg = log fee, tolerance 1e-3.
+    r = lg + 0.5e-3: found, sgn +1 (the a->b kink); r = -lg - 0.5e-3: found, sgn -1.  A banned (pool, sgn) and an already tied pool are
+    skipped.  A fee band narrower than twice the distance (|lg| < 2 dist) is ambiguous: found only by a loose search, and marked loose.
+    lg = 0 (no fee: the two kinks coincide): found."""
+    import math
+    lg = math.log(0.99)
+    cases = [("plus", 0.99, lg + 0.5e-3, "", "", 0), ("minus", 0.99, -lg - 0.5e-3, "", "", 0),
+             ("banned", 0.99, lg + 0.5e-3, "banned.insert({0, 1});", "", 0), ("othersign", 0.99, lg + 0.5e-3, "banned.insert({0, -1});", "", 0),
+             ("tied", 0.99, lg + 0.5e-3, "", "tied[0] = Tie{1, false};", 0),
+             ("narrow", math.exp(-0.8e-3), -0.8e-3 + 0.5e-3, "", "", 0), ("narrow_loose", math.exp(-0.8e-3), -0.8e-3 + 0.5e-3, "", "", 1),
+             ("nofee", 1.0, -0.5e-3, "", "", 0), ("far", 0.99, lg + 1.5e-3, "", "", 1)]
+    body = "    const int32_t ia[] = {0}, ib[] = {1}; const double Ra[] = {1.0}, Rb[] = {1.0};\n"
+    for nm, fee, r, ban, tie, loose in cases:
+        body += ("    { const double fee[] = {%r}, nu[] = {std::exp(%r), 1.0}; const SumCols sc{1, ia, ib, fee, Ra, Rb};\n"
+                 "      std::set<std::pair<int, int>> banned; std::map<int, Tie> tied, out; out[5] = Tie{1, true}; %s %s\n"
+                 "      kink_candidates(nu, sc, 1e-3, banned, tied, %d, out);\n"
+                 "      printf(\"%s %%d\", (int)out.size()); for (auto &kv : out) printf(\" %%d %%d %%d\", kv.first, kv.second.sgn, (int)kv.second.loose); printf(\"\\n\"); }\n"
+                 % (fee, r, ban, tie, loose, nm))
+    got = {k: [int(x) for x in v[0].split()] for k, v in _keyed(_sweep_rules_program(tmp_path, "kinks", body)).items()}
+    assert got == {"plus": [1, 0, 1, 0], "minus": [1, 0, -1, 0], "banned": [0], "othersign": [1, 0, 1, 0], "tied": [0], "narrow": [0],
+                   "narrow_loose": [1, 0, 1, 1], "nofee": [1, 0, 1, 0], "far": [0]}, got
+
+
+def test_swept_solve_round_tail_takes_each_branch_of_the_active_set_loop(tmp_path):
+    """csrc/sweep_rules.hpp: round_tail, one case per branch, in the order the loop tries them (the point of the fills test above, and a
+    second pool over tokens (1, 2) with fee 0.99; tolerance 1e-6, max_evals 300; every leg reports 7 evaluations and 5 iterations):
+    a non-finite dual value ends the point with the numeric status; status 1 without ties ends it; status 1 with a fill inside (0, 1) ends
+    it with fills_ok and the fill; a fill at 1 (the balance asks for 1.7) is released and banned, the point goes on; a LOOSE tie with
+    fill 0 is re-tied on the pool's other kink, no longer loose -- unless that sign is banned too; a new candidate joins the ties and
+    clears the bans that do not concern it; status 3 with no candidate within 0.1 doubles a leg budget below max_evals (capped at it);
+    with the budget at max_evals the kink tolerance goes up tenfold; at 0.05 the point is given up."""
+    import math
+    f = _FILL
+    lg0 = math.log(f["g"])
+    far = [1.0, 2.0, 4.0]                                     # log-price ratios -0.69: no kink within the widest search (0.1)
+    on0 = [math.exp(lg0 + 0.5e-3) * 2.0, 2.0, 2.0]            # pool 0 on its a->b kink; pool 1 at ratio 0, 0.01 from either of its kinks
+    decl = ("    " + _cvec("ia", [0, 1], "int32_t") + _cvec("ib", [1, 2], "int32_t") + _cvec("fee", [f["g"], 0.99]) + _cvec("Ra", [f["Ra"], 5.0])
+            + _cvec("Rb", [f["Rb"], 5.0]) + " const SumCols sc{2, ia, ib, fee, Ra, Rb};" + _cvec("c", f["c"]) + _cvec("h", [0, 0, 0]) + _cvec("ct", f["ctype"], "int32_t")
+            + "\n    const double INF = INFINITY; (void)INF;\n")
+    cases = [   # name, leg status, dual value, prices, psi, set-up of the state
+        ("nonfinite", 1, "INF", f["nu"], _fill_psi(0.3), ""),
+        ("plain", 1, "-3.5", f["nu"], _fill_psi(0.3), ""),
+        ("filled", 1, "-3.5", f["nu"], _fill_psi(0.386), "S.tied[0] = Tie{1, false};"),
+        ("full", 1, "-3.5", f["nu"], _fill_psi(1.7), "S.tied[0] = Tie{1, false};"),
+        ("flip", 1, "-3.5", f["nu"], _fill_psi(-0.5), "S.tied[0] = Tie{1, true};"),
+        ("noflip", 1, "-3.5", f["nu"], _fill_psi(-0.5), "S.tied[0] = Tie{1, true}; S.banned.insert({0, -1});"),
+        ("fresh", 3, "-3.5", on0, _fill_psi(0.3), "S.banned.insert({0, -1}); S.banned.insert({1, 1});"),
+        ("longer", 3, "-3.5", far, _fill_psi(0.3), "S.budget = 40;"),
+        ("capped", 0, "-3.5", far, _fill_psi(0.3), "S.budget = 200;"),
+        ("wider", 3, "-3.5", far, _fill_psi(0.3), "S.budget = 300;"),
+        ("wider2", 2, "-3.5", far, _fill_psi(0.3), "S.budget = 40;"),
+        ("giveup", 3, "-3.5", far, _fill_psi(0.3), "S.budget = 300; S.kink_tol = 0.05;"),
+    ]
+    body = decl
+    for nm, status, fval, nu, psi, setup in cases:
+        body += ("    { PointState S; S.budget = 40; S.evals = 10; S.iters = 8; S.rounds = 2; %s\n"
+                 "      %s %s const LegResult leg = {%d, 7, 5, %s, 1.0, 2e-7, 3e-7, 4e-7};\n"
+                 "      round_tail(S, leg, 3, nu, psi, c, h, ct, sc, 1e-6, 300); show(\"%s\", S); }\n" % (setup, _cvec("nu", nu), _cvec("psi", psi), status, fval, nm))
+    got = {}
+    for k, v in _keyed(_sweep_rules_program(tmp_path, "tail", body)).items():
+        head, tied, banned, theta = [p.split() for p in v[0].split("|")]
+        got[k] = dict(done=int(head[0]), fills_ok=int(head[1]), status=int(head[2]), counts=[int(x) for x in head[3:6]], budget=int(head[6]), kink_tol=float(head[7]),
+                      tied=[int(x) for x in tied], banned=[int(x) for x in banned], theta=[float(x) for x in theta])
+    assert len(got) == len(cases)
+    for k, g in got.items():
+        assert g["counts"] == [17, 13, 3], (k, g)              # (the leg's evaluations and iterations are added, the round counted)
+    E_NUMERIC = int(re.search(r"CFMM_E_NUMERIC\s*=\s*(-?\d+)", open(os.path.join(ROOT, "include", "cfmm.h")).read()).group(1))
+
+    def check(k, **want):
+        base = dict(done=0, fills_ok=0, budget=40, kink_tol=1e-3, tied=[], banned=[], theta=[])
+        base.update(want)
+        for key, w in base.items():
+            assert got[k][key] == w, (k, key, got[k], w)
+    check("nonfinite", done=1, status=E_NUMERIC)
+    check("plain", done=1, status=1)
+    check("filled", done=1, fills_ok=1, status=1, tied=[0, 1, 0], theta=got["filled"]["theta"])
+    assert len(got["filled"]["theta"]) == 1 and abs(got["filled"]["theta"][0] - 0.386) <= 1e-12
+    check("full", status=1, banned=[0, 1])
+    check("flip", status=1, tied=[0, -1, 0], banned=[0, 1])
+    check("noflip", status=1, banned=[0, -1, 0, 1])
+    check("fresh", status=3, tied=[0, 1, 0], banned=[0, -1])
+    check("longer", status=3, budget=80)
+    check("capped", status=0, budget=300)
+    check("wider", status=3, budget=300, kink_tol=1e-3 * 10.0)
+    check("wider2", status=2, kink_tol=1e-3 * 10.0)
+    check("giveup", done=1, status=3, budget=300, kink_tol=0.05)
+
+
+def test_swept_solve_round_head_bounds_and_schedule(tmp_path):
+    """csrc/sweep_rules.hpp: round_head, group_bounds, first_budget, exhausted.
+    round_head: two records over the same token pair with different fees contradict -- the first stays tied and flagged, the second is
+    dropped and banned; the tied pair is one group numbered before token 2, token 0 carries the offset log fee; the tolerance factor is
+    0.01 and pg_rule 1; the group's lower bound is the larger of the members' (log c - off), and the slot past ng is unbounded.  An
+    untied point: identity groups, zero offsets, the full tolerance, pg_rule 0.
+    group_bounds, one token each of GE with c > 0, GE with c = 0, EQ, FREE and a CFMM_ULOG entry: [log c, inf), [mid - 100, inf),
+    mid +- 100, log c twice, unbounded -- with mid = log of the largest c over the NON-table tokens.  Two tokens of one group with
+    offsets: the intersection.  A FREE token with c = 0: its index.
+    The schedule: legs of 40 evaluations up to 1000 pools and 100 beyond, never more than max_evals, and one leg of max_evals without
+    constant-sum pools; a point is exhausted at 4 x max_evals."""
+    import math
+    inf = float("inf")
+    ULOG = int(re.search(r"CFMM_ULOG\s*=\s*(-?\d+)", open(os.path.join(ROOT, "include", "cfmm.h")).read()).group(1))
+    f0, f1 = 0.997, 0.99
+    got = _keyed(_sweep_rules_program(tmp_path, "head", r'''
+    { const int32_t ia[] = {0, 0}, ib[] = {1, 1}; const double fee[] = {%r, %r}, Ra[] = {1.0, 1.0}, Rb[] = {1.0, 1.0}; const SumCols sc{2, ia, ib, fee, Ra, Rb};
+      const double c[] = {1.5, 10.0, 2.0}; const int ct[] = {0, 0, 0};
+      int flags[2] = {7, 7}, grp[3]; double off[3], glo[3], ghi[3];
+      PointState S; S.tied[0] = Tie{1, false}; S.tied[1] = Tie{1, false};
+      const RoundHead r = round_head(S, sc, 3, c, ct, flags, grp, off, glo, ghi);
+      show("h1", S); rowi("h1_flags", flags, 2); rowi("h1_grp", grp, 3); row("h1_off", off, 3); row("h1_lo", glo, 3); row("h1_hi", ghi, 3);
+      printf("h1_r %%d %%d %%.17g %%d\n", r.ng, (int)r.tied, r.tol_factor, r.pg_rule);
+      PointState U; int fl2[2] = {7, 7};
+      const RoundHead u = round_head(U, sc, 3, c, ct, fl2, grp, off, glo, ghi);
+      rowi("h2_flags", fl2, 2); rowi("h2_grp", grp, 3); row("h2_off", off, 3); row("h2_lo", glo, 3); row("h2_hi", ghi, 3);
+      printf("h2_r %%d %%d %%.17g %%d\n", u.ng, (int)u.tied, u.tol_factor, u.pg_rule); }
+    { const double c[] = {2.0, 0.0, 5.0, 3.0, 1000.0}; const int ct[] = {CFMM_GE, CFMM_GE, CFMM_EQ, CFMM_FREE, CFMM_ULOG}, grp[] = {0, 1, 2, 3, 4};
+      const double off[5] = {}; double lo[5], hi[5];
+      printf("b1_rc %%d\n", group_bounds(5, c, ct, grp, off, 5, lo, hi)); row("b1_lo", lo, 5); row("b1_hi", hi, 5); }
+    { const double c[] = {2.0, 4.0, 0.0}; const int ct[] = {CFMM_GE, CFMM_EQ, CFMM_FREE}, grp[] = {0, 0, 1};
+      const double off[] = {0.1, -0.2, 0.0}; double lo[2], hi[2];
+      printf("b2_rc %%d\n", group_bounds(2, c, ct, grp, off, 1, lo, hi)); row("b2_lo", lo, 1); row("b2_hi", hi, 1);
+      printf("b3_rc %%d\n", group_bounds(3, c, ct, grp, off, 2, lo, hi)); }
+    printf("budget %%d %%d %%d %%d %%d\n", first_budget(0, 5, 300), first_budget(1, 5, 300), first_budget(3, 1000, 300), first_budget(3, 1001, 300), first_budget(1, 5, 30));
+    { PointState S; S.evals = 1199; const int a = exhausted(S, 300); S.evals = 1200; printf("exhausted %%d %%d\n", a, (int)exhausted(S, 300)); }
+    ''' % (f0, f1)))
+    one = lambda k: got[k][0].split()
+    head, tied, banned, theta = [p.split() for p in got["h1"][0].split("|")]
+    assert tied == ["0", "1", "0"] and banned == ["1", "1"] and theta == []
+    assert one("h1_flags") == ["1", "0"] and one("h1_grp") == ["0", "0", "1"]
+    _same_numbers(one("h1_off"), [math.log(f0), 0.0, 0.0])
+    _same_numbers(one("h1_lo"), [max(math.log(1.5) - math.log(f0), math.log(10.0)), math.log(2.0), -inf])
+    assert [float(x) for x in one("h1_hi")] == [inf, inf, inf]
+    assert [float(x) for x in one("h1_r")] == [2.0, 1.0, 0.01, 1.0]
+    assert one("h2_flags") == ["0", "0"] and one("h2_grp") == ["0", "1", "2"] and [float(x) for x in one("h2_off")] == [0.0, 0.0, 0.0]
+    _same_numbers(one("h2_lo"), [math.log(1.5), math.log(10.0), math.log(2.0)])
+    assert [float(x) for x in one("h2_hi")] == [inf, inf, inf]
+    assert one("h2_r") == ["3", "0", "1", "0"]
+    mid = math.log(5.0)                                       # (the table entry's c = 1000 does not count)
+    assert ULOG >= 3 and one("b1_rc") == ["-1"]
+    _same_numbers(one("b1_lo"), [math.log(2.0), mid - 100.0, mid - 100.0, math.log(3.0), -inf])
+    _same_numbers(one("b1_hi"), [inf, inf, mid + 100.0, math.log(3.0), inf])
+    assert one("b2_rc") == ["-1"]
+    _same_numbers(one("b2_lo"), [max(math.log(2.0) - 0.1, math.log(4.0) - 100.0 + 0.2)])
+    _same_numbers(one("b2_hi"), [math.log(4.0) + 100.0 + 0.2])
+    assert one("b3_rc") == ["2"]
+    assert one("budget") == ["300", "40", "40", "100", "30"] and one("exhausted") == ["0", "1"]
+
+
+def test_swept_solve_folds_the_arbitrage_fill_and_certifies_the_point(tmp_path):
+    """csrc/sweep_rules.hpp: fold_fills and point_certificates on the shipped arbitrage instance, numbers from the 50-digit KKT record of
+    tests/golden: pool 4 (constant-sum, tokens 2 and 3) is partially filled -- theta and the sign read from its y.  psi of the four other
+    pools + the folded fill reproduces the record's psi to 5e-8 (the bound of the GPU test), the pool's tenders its y; value and dual
+    agree with the record's value to 1e-9.  Gap and infeasibility: the record satisfies the KKT system to 1e-49, folding in doubles adds
+    a few ulp of trades of size ~5, so both must come out under 1e-12."""
+    inst, k = I.normalise(I.arbitrage()), golden()["arbitrage"]["kkt"]
+    n, idx, R, fee = inst["n_tokens"], inst["local_indices"][4], inst["reserves"][4], inst["fees"][4]
+    assert inst["kinds"][4] == "sum" and list(k["theta"]) == ["4"]
+    y4 = k["y"][4]
+    sgn = 1 if y4[0] < 0 else -1                              # sgn +1 tenders the pool's first token
+    theta = float(y4[1] / R[1] if sgn > 0 else y4[0] / R[0])
+    assert abs(theta - k["theta"]["4"]) <= 1e-12 and 0.0 < theta < 1.0
+    psi = np.zeros(n)
+    for p in range(4):
+        psi[np.asarray(inst["local_indices"][p])] += np.asarray(k["y"][p])
+    got = _keyed(_sweep_rules_program(tmp_path, "fold", "    " + _cvec("ia", [idx[0], 0], "int32_t") + _cvec("ib", [idx[1], 1], "int32_t") + _cvec("fee", [fee, 0.99])
+                                      + _cvec("Ra", [R[0], 1.0]) + _cvec("Rb", [R[1], 1.0]) + " const SumCols sc{2, ia, ib, fee, Ra, Rb};\n    "
+                                      + _cvec("nu", k["nu"]) + _cvec("c", inst["c"]) + _cvec("h", inst["h"]) + _cvec("ct", inst["ctype"], "int32_t") + r'''
+    double psi[] = {%s}, tr[8] = {9, 9, 9, 9, 9, 9, 9, 9};
+    const double theta[] = {%r, NAN}; const int32_t tsgn[] = {%d, 0};
+    fold_fills(sc, theta, tsgn, psi, tr, tr + 4);
+    row("psi", psi, %d); row("tr", tr, 8);
+    const PointCertificates k = point_certificates(%d, nu, psi, c, h, ct, 50.0);
+    const double v[] = {k.value, k.dual, k.gap, k.infeas}; row("cert", v, 4);''' % (", ".join(repr(float(x)) for x in psi), theta, sgn, n, n)))
+    gpsi = np.array([float(x) for x in got["psi"][0].split()])
+    assert np.abs(gpsi - np.asarray(k["psi"])).max() <= 5e-8
+    tr = [float(x) for x in got["tr"][0].split()]
+    assert tr[1] == tr[3] == tr[5] == tr[7] == 9.0           # (the untied second pool's tenders are left alone)
+    delta, lam = np.array([tr[0], tr[2]]), np.array([tr[4], tr[6]])
+    assert np.abs((lam - delta) - np.asarray(y4)).max() <= 5e-8 and min(delta.min(), lam.min()) >= 0.0 and float(delta @ lam) == 0.0
+    value, dual, gap, infeas = [float(x) for x in got["cert"][0].split()]
+    assert abs(value - k["value"]) <= 1e-9 and abs(dual - k["value"]) <= 1e-9
+    assert 0.0 <= gap <= 1e-12 and 0.0 <= infeas <= 1e-12, (gap, infeas)
 
 
 def test_switch_records_of_a_k_asset_constant_sum_pool_are_rooted_at_the_paying_leg():
