@@ -71,7 +71,7 @@ assert _STATS_STRUCT.size == C.sizeof(Stats)
 
 def build(force=False):
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp", "update.hpp", "apply.hpp", "solve_plan.hpp", "newton_rules.hpp", "sweep_rules.hpp", "tiny_limits.hpp")]
+    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp", "update.hpp", "apply.hpp", "solve_plan.hpp", "newton_rules.hpp", "sweep_rules.hpp", "tiny_limits.hpp", "fixedpoint.hpp")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "cfmm.h"))
     if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _CSRC, "-s"])
@@ -83,7 +83,7 @@ _lib = None
 SYMBOLS = ["cfmm_create", "cfmm_clone", "cfmm_destroy", "cfmm_last_error", "cfmm_backend", "cfmm_default_opts",
            "cfmm_upload_pools2", "cfmm_upload_poolsN", "cfmm_upload_poolsG", "cfmm_update_pools2", "cfmm_update_poolsN", "cfmm_update_poolsG",
            "cfmm_apply_trades", "cfmm_get_reserves2", "cfmm_get_reservesN", "cfmm_get_reservesG", "cfmm_apply_timers", "cfmm_set_pool_flags", "cfmm_set_pool_flagsG", "cfmm_set_utility",
-           "cfmm_set_ties", "cfmm_set_deterministic", "cfmm_debug_eval_limbs", "cfmm_eval_dual", "cfmm_eval_smooth", "cfmm_debug_cholesky", "cfmm_debug_cholesky_apply", "cfmm_time_xcd_handoff", "cfmm_solve", "cfmm_solve_batch", "cfmm_eval_dual_batch", "cfmm_batch_capacity", "cfmm_solve_sweep", "cfmm_get_nu", "cfmm_set_nu", "cfmm_get_psi",
+           "cfmm_set_ties", "cfmm_set_deterministic", "cfmm_debug_eval_limbs", "cfmm_debug_scatter_limbs", "cfmm_eval_dual", "cfmm_eval_smooth", "cfmm_debug_cholesky", "cfmm_debug_cholesky_apply", "cfmm_time_xcd_handoff", "cfmm_solve", "cfmm_solve_batch", "cfmm_eval_dual_batch", "cfmm_batch_capacity", "cfmm_solve_sweep", "cfmm_get_nu", "cfmm_set_nu", "cfmm_get_psi",
            "cfmm_get_solution", "cfmm_get_trades2", "cfmm_get_tradesN", "cfmm_get_tradesG", "cfmm_comm_unique_id", "cfmm_comm_init",
            "cfmm_oneshot_export", "cfmm_oneshot_import", "cfmm_oneshot_attach", "cfmm_oneshot_mailbox", "cfmm_oneshot_enable",
            "cfmm_time_eval_kernel", "cfmm_time_collective", "cfmm_time_newton_kernels", "cfmm_selftest", "cfmm_debug_timers", "cfmm_clock_probe_start", "cfmm_clock_probe_read", "cfmm_clock_probe_stop", "cfmm_clock_probe_chain", "cfmm_pool_count", "cfmm_eval_bytes", "cfmm_stream"]
@@ -122,6 +122,7 @@ def lib():
     L.cfmm_set_ties.argtypes = [vp, C.c_int, ip, dp]
     L.cfmm_set_deterministic.argtypes = [vp, C.c_int]
     L.cfmm_debug_eval_limbs.argtypes = [vp, dp, C.c_double, C.c_double, C.POINTER(C.c_uint64)]
+    L.cfmm_debug_scatter_limbs.argtypes = [vp, C.c_int64, ip, dp, C.c_double, C.c_double, C.POINTER(C.c_uint64)]
     L.cfmm_eval_dual.argtypes = [vp, dp, dp, dp, dp]
     L.cfmm_eval_smooth.argtypes = [vp, dp, C.c_double, dp, dp, dp, dp]
     L.cfmm_debug_cholesky.argtypes = [vp, C.c_int, dp, dp, dp, ip]
@@ -333,6 +334,15 @@ class Context:
         nu = f64(nu)
         limbs = np.zeros((3, self.n), dtype=np.uint64)
         self._chk(self.L.cfmm_debug_eval_limbs(self.h, _d(nu), float(ref_reserve), float(ref_fee), limbs.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return limbs
+
+    def debug_scatter_limbs(self, tok, y, ref_reserve, ref_fee):
+        """raw limbs [3][n] (uint64) after the device's fixed-point split has added y[i] to token tok[i], at the exponent
+        debug_eval_limbs derives from the same (ref_reserve, ref_fee) (test hook)"""
+        tok, y = i32(tok), f64(y)
+        assert tok.shape == y.shape and tok.ndim == 1
+        limbs = np.zeros((3, self.n), dtype=np.uint64)
+        self._chk(self.L.cfmm_debug_scatter_limbs(self.h, len(y), _i(tok), _d(y), float(ref_reserve), float(ref_fee), limbs.ctypes.data_as(C.POINTER(C.c_uint64))))
         return limbs
 
     def eval_dual(self, nu, want_diag=False):

@@ -4850,6 +4850,46 @@ int cfmm_debug_eval_limbs(cfmm_ctx *ctx, const double *nu, double ref_reserve, d
     return CFMM_OK;
 }
 
+// (test hook) the device's fixed-point split alone: Scatter<true>::add(tok[i], y[i]) for i < count on a zeroed [3][n] limb array
+// of its own, with the scale cfmm_debug_eval_limbs derives from the same (ref_reserve, ref_fee)
+int cfmm_debug_scatter_limbs(cfmm_ctx *ctx, int64_t count, const int32_t *tok, const double *y, double ref_reserve, double ref_fee, uint64_t *limbs)
+{
+    if (!ctx || !tok || !y || !limbs || count < 1 || count > (1 << 24)) return ctx ? fail(ctx, CFMM_E_ARG, "debug_scatter_limbs: 1 <= count <= 2^24") : CFMM_E_ARG;
+    if (!(ref_reserve > 0.0) || !(ref_fee > 0.0)) return fail(ctx, CFMM_E_ARG, "debug_scatter_limbs: the reference reserve and fee must be positive");
+    const int n = ctx->n;
+    const double save_r = ctx->det_ref_reserve, save_f = ctx->det_ref_fee;
+    ctx->det_ref_reserve = ref_reserve; ctx->det_ref_fee = ref_fee;
+    double sc, scd;
+    det_scales(ctx, sc, scd);
+    ctx->det_ref_reserve = save_r; ctx->det_ref_fee = save_f;
+    for (int64_t i = 0; i < count; ++i) {
+        if (tok[i] < 0 || tok[i] >= n) return fail(ctx, CFMM_E_ARG, "debug_scatter_limbs: tok[%lld] = %d is not a token", (long long)i, tok[i]);
+        if (!(std::fabs(y[i] * sc) < 0x1p95)) return fail(ctx, CFMM_E_ARG, "debug_scatter_limbs: y[%lld] is outside the split's range", (long long)i);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc = settle(ctx); if (rc) return rc; }
+    const size_t lb = 3 * (size_t)n * sizeof(unsigned long long), yb = (size_t)count * sizeof(double), tb = (size_t)count * sizeof(int32_t);
+    char *buf = nullptr;                                     // limbs | y | tok
+    HIP_TRY(ctx, hipMalloc((void **)&buf, lb + yb + tb));
+    unsigned long long *dL = (unsigned long long *)buf;
+    double *dy = (double *)(buf + lb);
+    int *dt = (int *)(buf + lb + yb);
+    hipError_t e = hipMemsetAsync(dL, 0, lb, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, yb, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dt, tok, tb, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(debug_scatter_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, dL, n, sc, (const int *)dt, (const double *)dy,
+                           (long long)count);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(limbs, dL, lb, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(ctx, CFMM_E_HIP, "debug_scatter_limbs -> %s", hipGetErrorString(e));
+    return CFMM_OK;
+}
+
 static int oneshot_alloc(cfmm_ctx *ctx)
 {
     if (ctx->os_mail) return CFMM_OK;

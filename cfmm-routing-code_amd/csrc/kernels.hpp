@@ -18,6 +18,7 @@
 #include "pool_math.hpp"
 #include "phi2.hpp"
 #include "lbfgs_rules.hpp"
+#include "fixedpoint.hpp"
 
 namespace cfmm {
 
@@ -241,12 +242,14 @@ __device__ __forceinline__ double wave_max(double v) { return wave_allmax(v); }
 // Where a pool's A_i (Lambda_i - Delta_i) lands in the workgroup's LDS tile of psi (arbitrage.py:54).
 //   Scatter<false>: ds_add_f64 -- fast, but fp64 addition is not associative: the sum depends on the order in which lanes,
 //     waves and workgroups arrive, so psi differs in its last bits from run to run (and with it the path of the solve).
-//   Scatter<true> (reproducible mode, cfmm_set_deterministic): every contribution is converted EXACTLY to a 96-bit
-//     fixed-point integer  y * 2^F = a2 2^64 + a1 2^32 + a0  and its three limbs are added to three 64-bit integer
+//   Scatter<true> (reproducible mode, cfmm_set_deterministic): every contribution is floored to a 96-bit fixed-point
+//     integer  floor(y * 2^F) = a2 2^64 + a1 2^32 + a0,  0 <= a0, a1 < 2^32, a2 signed  (fixedpoint.hpp: fixed_split -- exact
+//     for either sign, only the fraction below 2^-F is dropped) and its three limbs are added to three 64-bit integer
 //     accumulators (ds_add_u64; 32 bits of carry head-room each: no carry propagation while adding).  Integer addition is
 //     associative and commutative, so the result is bit-identical whatever the order -- lanes, waves, ticket scheduling,
 //     workgroups, accumulator flushes, pool shards on other GPUs (the limbs are all-reduced as integers) -- and the one
-//     conversion back to fp64 happens in a fixed order (det_fold_kernel).  F is chosen per problem from the largest reserve.
+//     conversion back to fp64 happens in a fixed order (det_fold_kernel).  F is chosen per problem from the largest reserve
+//     and the smallest fee (cfmm_hip.hip: det_scales) so that every |y * 2^F| < 2^84: 10 bits below the split's own range.
 // ------------------------------------------------------------------------------------------
 // element `i` of a column whose base is wave-uniform: byte offset formed in 32 bits (columns stay below 4 GB)
 // NT: non-temporal.  A pool set several times the size of the Infinity Cache (256 MiB) gets nothing out of the cache levels on
@@ -274,14 +277,10 @@ template <> struct Scatter<true> {
     __device__ __forceinline__ void add(int tok, double y) const
     {
         unsigned long long *L = reinterpret_cast<unsigned long long *>(t);
-        const double yf = y * sc;                                  // exact (power of two)
-        const double a2 = floor(yf * 0x1p-64);
-        const double r = fma(-a2, 0x1p64, yf);                     // exact, in [0, 2^64)
-        const double a1 = floor(r * 0x1p-32);
-        const double a0 = floor(fma(-a1, 0x1p32, r));              // in [0, 2^32); the fraction below 2^-F is dropped
-        atomicAdd(&L[tok], (unsigned long long)(unsigned)__double2uint_rz(a0));
-        atomicAdd(&L[n + tok], (unsigned long long)(unsigned)__double2uint_rz(a1));
-        atomicAdd(&L[2 * n + tok], (unsigned long long)(long long)__double2int_rz(a2));
+        const FixedLimbs a = fixed_split(y * sc);                  // y * sc: exact (power of two), |.| < 2^84 (det_scales)
+        atomicAdd(&L[tok], (unsigned long long)a.a0);
+        atomicAdd(&L[n + tok], (unsigned long long)a.a1);
+        atomicAdd(&L[2 * n + tok], (unsigned long long)(long long)a.a2);
     }
 };
 
@@ -1185,11 +1184,9 @@ __global__ void fold_kernel(double *__restrict__ acc, int n, int nslices, int wi
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ double limbs_to_double(unsigned long long l0, unsigned long long l1, unsigned long long l2, double inv_scale)
 {
-    // value = l2 2^64 + l1 2^32 + l0 with every limb a wrapped SIGNED 64-bit sum: exact in 128-bit integer arithmetic
-    const __int128 t = ((__int128)(long long)l2 << 64) + ((__int128)(long long)l1 << 32) + (__int128)(long long)l0;
-    const long long hi = (long long)(t >> 64);
-    const unsigned long long lo = (unsigned long long)t;
-    return ((double)hi * 0x1p64 + (double)lo) * inv_scale;     // two roundings, always the same two
+    // value = l2 2^64 + l1 2^32 + l0, l2 a wrapped SIGNED 64-bit sum, l0 and l1 unsigned: exact in 128-bit integer arithmetic
+    const Fixed128 t = fixed_combine(l0, l1, l2);
+    return ((double)t.hi * 0x1p64 + (double)t.lo) * inv_scale;     // two roundings, always the same two
 }
 __global__ void __launch_bounds__(1024)
 det_fold_kernel(unsigned long long *__restrict__ L, const double *__restrict__ nu, double *__restrict__ out, int n, double inv_scale,
@@ -1214,6 +1211,16 @@ det_fold_kernel(unsigned long long *__restrict__ L, const double *__restrict__ n
         __syncthreads();
     }
     if (threadIdx.x == 0) out[acc_arb(n)] = part[0];
+}
+// (test hook, cfmm_debug_scatter_limbs) Scatter<true>::add itself on caller-supplied contributions, into a zeroed global
+// [3][n] limb array; the host has checked every tok[i] against n
+__global__ void __launch_bounds__(256)
+debug_scatter_kernel(unsigned long long *__restrict__ L, int n, double sc, const int *__restrict__ tok, const double *__restrict__ y, long long count)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const Scatter<true> s{reinterpret_cast<double *>(L), n, sc};
+    s.add(tok[i], y[i]);
 }
 
 // ------------------------------------------------------------------------------------------

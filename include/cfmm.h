@@ -262,18 +262,27 @@ int cfmm_debug_cholesky_apply(cfmm_ctx *ctx, int n, const double *b, double *x);
 
 /* Reproducible mode.  By default psi is scatter-added with fp64 atomics, whose order -- lanes, waves, workgroups -- varies
  * from run to run: psi, and with it the path of a solve, is reproducible to rounding only.  With `on` != 0 every pool's
- * contribution is converted exactly to a 96-bit fixed-point integer and accumulated with integer atomics (associative:
- * any order gives the same bits), all-reduced as integers when pool-sharded, and converted back in a fixed order:
+ * contribution y is floored to the 96-bit fixed-point integer floor(y * 2^F) -- exactly, for tendered (negative) and received
+ * amounts alike; F is chosen from the largest reserve and the smallest fee so that |y * 2^F| < 2^84, and only the fraction
+ * below 2^-F is dropped -- and accumulated with integer atomics (associative: any order gives the same bits),
+ * all-reduced as integers when pool-sharded, and converted back in a fixed order:
  * psi, the iterates and the evaluation count are then BITWISE identical from run to run and for any number of pool
  * shards / GPUs.  Cost, measured (DESIGN.md "Reproducible mode"): the evaluation kernel +20..30 % (three LDS atomics per leg
  * instead of one: 20.1 against 16.6 us at 1e6 mixed pools), the outer iteration +24..30 % (one small extra launch per
  * evaluation).  First-order path and cfmm_eval_dual; needs <= ~2600 tokens; fees >= 1e-3.  Also: CFMM_DETERMINISTIC=1. */
 int cfmm_set_deterministic(cfmm_ctx *ctx, int on);
 /* test hook of the reproducible mode: one dual evaluation returning the RAW integer limbs of psi ([3][n], limb-major, value =
- * (limb2 2^64 + limb1 2^32 + limb0) / 2^F, every limb a wrapped signed 64-bit sum) with the fixed-point exponent F derived from
- * (ref_reserve, ref_fee) instead of this context's own largest reserve / smallest fee -- so that the limbs of the S shards
- * of a network, added as integers on the host, can be compared bit for bit with the unsharded network's. */
+ * (limb2 2^64 + limb1 2^32 + limb0) / 2^F, limb2 a wrapped signed 64-bit sum, limb0 and limb1 sums of values in [0, 2^32)) with
+ * the fixed-point exponent F derived from (ref_reserve, ref_fee) instead of this context's own largest reserve / smallest fee
+ * -- so that the limbs of the S shards of a network, added as integers on the host, can be compared bit for bit with the
+ * unsharded network's. */
 int cfmm_debug_eval_limbs(cfmm_ctx *ctx, const double *nu, double ref_reserve, double ref_fee, uint64_t *limbs);
+/* test hook of the reproducible mode: the device's fixed-point split alone.  Contribution y[i] is added to token tok[i]
+ * (0 <= tok[i] < the context's token count, i < count) exactly as an evaluation adds a pool's, into a zeroed [3][n] limb
+ * array (layout as above) with the exponent F cfmm_debug_eval_limbs derives from the same (ref_reserve, ref_fee); every
+ * |y[i] * 2^F| must be below 2^95.  limbs[.][j] is then the sum over tok[i] == j of the limbs of floor(y[i] * 2^F). */
+int cfmm_debug_scatter_limbs(cfmm_ctx *ctx, int64_t count, const int32_t *tok, const double *y,
+                             double ref_reserve, double ref_fee, uint64_t *limbs /* [3][n] */);
 
 /* prob.solve(): nu0 = start prices.  NULL: continue from cfmm_set_nu / the previous solution -- after a second-order
  * solve that includes (a multiple of) its final barrier weight: the warm start of a parametric sweep (two-asset.py:34-100).

@@ -123,3 +123,42 @@ def table_instance(seed):
     else:
         h = np.exp(rng.normal(0.5, 0.5, n)); h[n - 1] = 0.0; u = dict(type="liquidate", h=h.tolist(), t=n - 1)
     return dict(name=f"tbl{seed}", n_tokens=n, local_indices=L, reserves=R, fees=F, kinds=K, weights=W, params=P, utility=u), with_sum
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the reproducible mode's fixed point (csrc/fixedpoint.hpp): inputs and the exact reference shared by the CPU and the GPU suite
+# ---------------------------------------------------------------------------------------------------------------
+# edge inputs in SCALED units yf = y 2^F (every entry is a double, exactly); the tests take both signs
+FIXED_EDGES = [0.0, 0.3, 1 - 2.0 ** -53, 1.0, 1 + 2.0 ** -52,
+               2.0 ** 10 - 1, 2.0 ** 10, 2.0 ** 11 + 1,
+               2.0 ** 32 - 1, 2.0 ** 32, 2.0 ** 32 + 1,
+               2.0 ** 63, 2.0 ** 64 - 2.0 ** 11, 2.0 ** 64, 2.0 ** 64 + 2.0 ** 12,
+               2.0 ** 84 - 2.0 ** 31]           # the head-room bound of det_scales
+
+
+def fixed_scale_exponent(mr, mf):
+    """F of the fixed point y 2^F as det_scales (csrc/cfmm_hip.hip) derives it from the largest reserve and the smallest fee"""
+    import math
+    return 84 - math.frexp(mr / max(mf, 1e-3))[1]
+
+
+def fixed_random_scaled(count, seed):
+    """`count` values in scaled units: full 53-bit mantissas, exponents uniform over [2^-20, 2^84), random signs"""
+    rng = np.random.default_rng(seed)
+    mant = rng.integers(2 ** 52, 2 ** 53, count).astype(np.float64)          # exact: below 2^53
+    return np.ldexp(mant, rng.integers(-20, 84, count) - 52) * rng.choice([-1.0, 1.0], count)
+
+
+def exact_floor(y, F):
+    """floor(Fraction(y) * 2**F) for an array of doubles as Python integers: y = m 2^e with m a signed 53-bit integer, and
+    m 2^(e + F) floors by a shift (Python's >> rounds towards -inf)"""
+    mant, exp = np.frexp(np.asarray(y, dtype=np.float64))
+    m = np.ldexp(mant, 53).astype(np.int64).tolist()
+    s = (exp.astype(np.int64) - 53 + F).tolist()
+    return [(mi << si) if si >= 0 else (mi >> -si) for mi, si in zip(m, s)]
+
+
+def limbs_as_integers(limbs):
+    """[3][n] uint64 limb sums -> n Python integers l2 2^64 + l1 2^32 + l0: l2 a wrapped signed 64-bit sum, l0 and l1 unsigned"""
+    l = np.asarray(limbs, dtype=np.uint64)
+    return [(int(l[2, j].view(np.int64)) << 64) + (int(l[1, j]) << 32) + int(l[0, j]) for j in range(l.shape[1])]
