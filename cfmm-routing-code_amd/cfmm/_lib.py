@@ -52,6 +52,23 @@ class ApplyInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "_pad"}
 
 
+class AuditTenders(C.Structure):
+    """cfmm_audit_tenders: tenders the caller holds for constant-sum buckets (its own kink loop's fills), replacing the device's"""
+    _fields_ = [("sum2_delta", C.POINTER(C.c_double)), ("sum2_lambda", C.POINTER(C.c_double)),
+                ("sumk_delta", C.POINTER(C.c_double) * (MAX_POOL_SIZE + 1)), ("sumk_lambda", C.POINTER(C.c_double) * (MAX_POOL_SIZE + 1))]
+
+
+class Audit(C.Structure):
+    """cfmm_audit: the report of cfmm_audit_trades (docs/audit.md)"""
+    _fields_ = [("pools", C.c_int64), ("pools_trading", C.c_int64), ("pools_violating", C.c_int64), ("legs_out_of_range", C.c_int64),
+                ("worst_family", C.c_int32), ("worst_kind", C.c_int32), ("worst_k", C.c_int32), ("fixed_exponent", C.c_int32),
+                ("worst_pos", C.c_int64), ("min_slack", C.c_double), ("min_tender", C.c_double), ("min_leg", C.c_double),
+                ("value", C.c_double), ("infeas", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Stats(C.Structure):
     _fields_ = [("evals", C.c_int32), ("iters", C.c_int32), ("status", C.c_int32), ("n_ranks", C.c_int32),
                 ("dual_value", C.c_double), ("primal_value", C.c_double), ("gap", C.c_double),
@@ -71,7 +88,7 @@ assert _STATS_STRUCT.size == C.sizeof(Stats)
 
 def build(force=False):
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp", "update.hpp", "apply.hpp", "solve_plan.hpp", "newton_rules.hpp", "sweep_rules.hpp", "tiny_limits.hpp", "fixedpoint.hpp")]
+    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp", "update.hpp", "apply.hpp", "audit.hpp", "solve_plan.hpp", "newton_rules.hpp", "sweep_rules.hpp", "tiny_limits.hpp", "fixedpoint.hpp")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "cfmm.h"))
     if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _CSRC, "-s"])
@@ -82,7 +99,7 @@ _lib = None
 
 SYMBOLS = ["cfmm_create", "cfmm_clone", "cfmm_destroy", "cfmm_last_error", "cfmm_backend", "cfmm_default_opts",
            "cfmm_upload_pools2", "cfmm_upload_poolsN", "cfmm_upload_poolsG", "cfmm_update_pools2", "cfmm_update_poolsN", "cfmm_update_poolsG",
-           "cfmm_apply_trades", "cfmm_get_reserves2", "cfmm_get_reservesN", "cfmm_get_reservesG", "cfmm_apply_timers", "cfmm_set_pool_flags", "cfmm_set_pool_flagsG", "cfmm_set_utility",
+           "cfmm_apply_trades", "cfmm_get_reserves2", "cfmm_get_reservesN", "cfmm_get_reservesG", "cfmm_apply_timers", "cfmm_audit_trades", "cfmm_debug_audit_launch", "cfmm_set_pool_flags", "cfmm_set_pool_flagsG", "cfmm_set_utility",
            "cfmm_set_ties", "cfmm_set_deterministic", "cfmm_debug_eval_limbs", "cfmm_debug_scatter_limbs", "cfmm_eval_dual", "cfmm_eval_smooth", "cfmm_debug_cholesky", "cfmm_debug_cholesky_apply", "cfmm_time_xcd_handoff", "cfmm_solve", "cfmm_solve_batch", "cfmm_eval_dual_batch", "cfmm_batch_capacity", "cfmm_solve_sweep", "cfmm_get_nu", "cfmm_set_nu", "cfmm_get_psi",
            "cfmm_get_solution", "cfmm_get_trades2", "cfmm_get_tradesN", "cfmm_get_tradesG", "cfmm_comm_unique_id", "cfmm_comm_init",
            "cfmm_oneshot_export", "cfmm_oneshot_import", "cfmm_oneshot_attach", "cfmm_oneshot_mailbox", "cfmm_oneshot_enable",
@@ -116,6 +133,8 @@ def lib():
     L.cfmm_get_reservesN.argtypes = [vp, C.c_int, dp]
     L.cfmm_get_reservesG.argtypes = [vp, C.c_int, C.c_int, dp, dp]
     L.cfmm_apply_timers.argtypes = [vp, C.c_int, dp]
+    L.cfmm_audit_trades.argtypes = [vp, C.POINTER(AuditTenders), C.c_double, C.POINTER(Audit), dp, C.POINTER(C.c_uint64)]
+    L.cfmm_debug_audit_launch.argtypes = [vp, C.c_int, C.c_int, dp]
     L.cfmm_set_pool_flags.argtypes = [vp, C.c_int, ip]
     L.cfmm_set_pool_flagsG.argtypes = [vp, C.c_int, ip]
     L.cfmm_set_utility.argtypes = [vp, dp, dp, ip]
@@ -285,6 +304,45 @@ class Context:
         out = np.zeros(2)
         self._chk(self.L.cfmm_apply_timers(self.h, 1 if on else 0, _d(out)))
         return float(out[0]), float(out[1])
+
+    def audit(self, own=None, tol_pool=0.0, want_limbs=False, check=True):
+        """cfmm_audit_trades: does every pool accept the tenders get_trades* would return now, and what do they add up to exactly
+        (docs/audit.md)?  own: {"sum2" | ("sum", k): (delta, lambda)} tenders the caller holds for constant-sum buckets, replacing the
+        device's; tol_pool <= 0: the library's default.  Returns the report as a dict with "psi" [n] (and "limbs" [3][n] uint64 with
+        want_limbs); check=False: (return code, dict) instead of raising"""
+        rep = Audit()
+        psi = np.zeros(self.n)
+        limbs = np.zeros((3, self.n), dtype=np.uint64) if want_limbs else None
+        ten, keep = None, []
+        _p = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        if own:
+            ten = AuditTenders()
+            for key, (d, l) in own.items():
+                d, l = f64(d), f64(l)
+                keep += [d, l]
+                if key == "sum2":
+                    ten.sum2_delta, ten.sum2_lambda = _p(d), _p(l)
+                elif isinstance(key, tuple) and key[0] == "sum" and 2 <= int(key[1]) <= MAX_POOL_SIZE:
+                    ten.sumk_delta[int(key[1])], ten.sumk_lambda[int(key[1])] = _p(d), _p(l)
+                else:
+                    raise CfmmError(f"audit: own tenders are taken for constant-sum buckets only, not {key!r}")
+        rc = self.L.cfmm_audit_trades(self.h, C.byref(ten) if ten is not None else None, float(tol_pool), C.byref(rep), _d(psi),
+                                      limbs.ctypes.data_as(C.POINTER(C.c_uint64)) if want_limbs else None)
+        out = rep.asdict()
+        out["psi"] = psi
+        if want_limbs:
+            out["limbs"] = limbs
+        if not check:
+            return int(rc), out
+        self._chk(rc)
+        return out
+
+    def debug_audit_launch(self, timed=False, grid=0):
+        """(seconds of the last audit's launches by HIP events, buckets the last audit found stored reordered); switches the events
+        on / off; grid > 0: workgroups per pass from now on (test and measurement hook)"""
+        out = np.zeros(2)
+        self._chk(self.L.cfmm_debug_audit_launch(self.h, 1 if timed else 0, int(grid), _d(out)))
+        return float(out[0]), int(out[1])
 
     def get_reserves2(self, kind, m, with_param=False):
         """resident reserves (Ra, Rb[, param]) of a two-asset bucket of m pools, in upload order"""

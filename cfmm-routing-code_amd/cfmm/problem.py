@@ -257,6 +257,176 @@ def post_trade_reserves(R, delta, lam, fee, fees="pool"):
     return (R + g * delta) - lam
 
 
+# ------------------------------------------------------------------------------- the route audited (docs/audit.md)
+AUDIT_TOL_POOL = 1e-9      # the stopping residual of the K-asset table's stableswap search (csrc/phik.hpp: pool_stable_k), the loosest per-pool solver
+
+
+def audit_buckets(net):
+    """every non-empty bucket of a packed network in the order of the library's bucket records (two-asset kinds, geo-mean sizes 3..8,
+    the table's stableswap then constant-sum sizes): dicts with key (as bucket_trades takes it), family / kind / k (as cfmm_apply_info
+    names them), cls ('log' | 'sum' | 'stable' | 'pow': what the slack is), idx, R [k][m], fee [m], and w [k][m] (cls 'log': the
+    normalised weights), e [m] (cls 'pow': 1 - t) or alpha [m] (cls 'stable')"""
+    out = []
+    cls2 = dict(cp2="log", w2="log", sum2="sum", curve2="stable", pow2="pow")
+    for key, kind in KIND2.items():
+        b = net.get(key)
+        if b is None or not len(b["Ra"]):
+            continue
+        m = len(b["Ra"])
+        rec = dict(key=key, family=0, kind=kind, k=2, cls=cls2[key], idx=np.stack([b["ia"], b["ib"]]).astype(np.int64),
+                   R=np.stack([b["Ra"], b["Rb"]]).astype(np.float64), fee=np.asarray(b["fee"], dtype=np.float64))
+        if key == "cp2":
+            rec["w"] = np.full((2, m), 0.5)
+        elif key == "w2":
+            wa = np.asarray(b["wa"], dtype=np.float64)
+            rec["w"] = np.stack([wa, 1.0 - wa])
+        elif key == "curve2":
+            rec["alpha"] = np.asarray(b["alpha"], dtype=np.float64)
+        elif key == "pow2":
+            rec["e"] = 1.0 - np.asarray(b["t"], dtype=np.float64)
+        out.append(rec)
+    for k in sorted(net.get("gn", {})):
+        b = net["gn"][k]
+        if b["R"].shape[1]:
+            w = np.asarray(b["w"], dtype=np.float64)
+            out.append(dict(key=k, family=1, kind=0, k=k, cls="log", idx=np.asarray(b["idx"], dtype=np.int64), R=np.asarray(b["R"], dtype=np.float64),
+                            fee=np.asarray(b["fee"], dtype=np.float64), w=w / w.sum(axis=0)))
+    for name, kind in sorted(_lib.POOLK.items(), key=lambda kv: kv[1]):
+        for k in range(2, MAX_POOL_SIZE + 1):
+            b = net.get("gk", {}).get((name, k))
+            if b is None or not b["R"].shape[1]:
+                continue
+            rec = dict(key=(name, k), family=2, kind=kind, k=k, cls="stable" if name == "stable" else "sum", idx=np.asarray(b["idx"], dtype=np.int64),
+                       R=np.asarray(b["R"], dtype=np.float64), fee=np.asarray(b["fee"], dtype=np.float64))
+            if name == "stable":
+                rec["alpha"] = np.asarray(b["param"], dtype=np.float64)
+            out.append(rec)
+    return out
+
+
+def audit_exponent(net):
+    """F of the fixed point y 2^F: what the reproducible mode derives from the largest reserve and the smallest fee (csrc/cfmm_hip.hip: det_scales)"""
+    import math
+    mr, mf = 0.0, 1.0
+    for b in audit_buckets(net):
+        mr = max(mr, float(b["R"].max())); mf = min(mf, float(b["fee"].min()))
+    return 84 - math.frexp(max(mr, 1e-300) / max(mf, 1e-3))[1]
+
+
+def _fixed_limbs(y, F):
+    """the three limbs (uint64, uint64, int64 arrays) of floor(y 2^F), exactly, for doubles with |y 2^F| < 2^94: y = m 2^e with m a signed
+    53-bit integer, and m 2^(e + F) is shifted in integer arithmetic (csrc/fixedpoint.hpp: fixed_split gives the same limbs)"""
+    mant, exp = np.frexp(np.asarray(y, dtype=np.float64))
+    m = np.ldexp(mant, 53).astype(np.int64)
+    s = exp.astype(np.int64) - 53 + F
+    M32 = np.int64(0xFFFFFFFF)
+    # s < 0: an arithmetic shift floors (beyond 63 places: 0 or -1)
+    v = m >> np.minimum(np.maximum(-s, 0), 63)
+    neg = (v & M32, (v >> 32) & M32, v >> 63)                          # (the sign fills the top limb)
+    # s >= 0 (<= 41): m = mh 2^32 + ml, shifted by r = s mod 32 in two pieces, then by whole limbs
+    sp = np.maximum(s, 0)
+    r, a = sp & 31, sp >> 5
+    ml, mh = (m & M32).astype(np.uint64), m >> 32
+    t0 = ml << r.astype(np.uint64)
+    l0 = (t0 & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    t1 = (mh << r) + (t0 >> np.uint64(32)).astype(np.int64)
+    l1, l2 = t1 & M32, t1 >> 32
+    pos = (np.where(a == 0, l0, 0), np.where(a == 0, l1, l0), np.where(a == 0, l2, l1 + (l2 << 32)))
+    lo = s < 0
+    return (np.where(lo, neg[0], pos[0]).astype(np.uint64), np.where(lo, neg[1], pos[1]).astype(np.uint64), np.where(lo, neg[2], pos[2]))
+
+
+def audit_trades(net, trades, utility=None, tol_pool=AUDIT_TOL_POOL, exponent=None):
+    """Does every pool accept this route, and what does it add up to?  The NumPy twin of cfmm_audit_trades (include/cfmm.h,
+    docs/audit.md), the host path of pool-sharded problems and the reference of the tests.  trades: {bucket key: (delta, lambda)}, slot-major
+    [k][m] in upload order, as Problem.bucket_trades hands them out.  Per pool, x_j = (R_j + gamma Delta_j) - Lambda_j, each operation
+    rounded on its own; slack: the relative change of the trading function (>= 0: accepted); a pool violates with slack < -tol_pool, a
+    tender negative or not finite, or a leg that does not stay positive (constant sum: x_j < -tol_pool sum R).  psi is summed EXACTLY:
+    every non-zero Lambda_j (+) and Delta_j (-) floored on its own to the 96-bit fixed point floor(y 2^F), as Python integers.
+    exponent: F; None derives it from this network's largest reserve and smallest fee (audit_exponent), which is what the device does
+    for an unsharded context -- the shards of a pool-sharded network pass the exponent of the WHOLE network, so that their integers add.
+    Returns the fields of cfmm_audit plus psi [n], psi_int (n Python integers: psi 2^F before the one rounding), limbs ([3][n] uint64: the
+    layout of cfmm_debug_eval_limbs) and slack ({key: [m]})."""
+    import math
+    n = int(net["n_tokens"])
+    tol = float(tol_pool) if tol_pool is not None and tol_pool > 0 else AUDIT_TOL_POOL
+    F = audit_exponent(net) if exponent is None else int(exponent)
+    L0 = np.zeros(n, dtype=np.uint64); L1 = np.zeros(n, dtype=np.uint64); L2 = np.zeros(n, dtype=np.int64)
+    rep = dict(pools=0, pools_trading=0, pools_violating=0, legs_out_of_range=0, worst_family=-1, worst_kind=-1, worst_k=-1,
+               fixed_exponent=F, worst_pos=-1, min_slack=np.inf, min_tender=np.inf, min_leg=np.inf, value=np.nan, infeas=np.nan)
+    slacks = {}
+    ninf = -np.inf
+    with np.errstate(all="ignore"):
+        for b in audit_buckets(net):
+            D, L = (np.asarray(a, dtype=np.float64) for a in trades[b["key"]])
+            R, g, k = b["R"], b["fee"], b["k"]
+            m = R.shape[1]
+            x = (R + g * D) - L
+            Sx = np.zeros(m); SR = np.zeros(m)
+            for j in range(k):
+                Sx = Sx + x[j]; SR = SR + R[j]
+            if b["cls"] == "log":
+                s = np.zeros(m)
+                for j in range(k):
+                    s = s + b["w"][j] * np.log(x[j] / R[j])
+            elif b["cls"] == "sum":
+                s = (Sx - SR) / SR
+            elif b["cls"] == "stable":
+                Px = np.ones(m); PR = np.ones(m)
+                for j in range(k):
+                    Px = Px * x[j]; PR = PR * R[j]
+                cx, cR = b["alpha"] / Px, b["alpha"] / PR
+                s = ((Sx - cx) - (SR - cR)) / (SR + cR)
+            else:
+                fx = np.zeros(m); fR = np.zeros(m)
+                for j in range(k):
+                    fx = fx + np.power(x[j], b["e"]); fR = fR + np.power(R[j], b["e"])
+                s = (fx - fR) / fR
+            s = np.where(np.isfinite(s), s, ninf) + 0.0
+            tbad = (~(np.isfinite(D) & (D >= 0.0)) | ~(np.isfinite(L) & (L >= 0.0))).any(axis=0)
+            xmin = np.fmin.reduce(x, axis=0)                                   # (NaN legs are told apart below)
+            bad = (s < -tol) | tbad
+            bad |= (xmin < -(tol * SR)) if b["cls"] == "sum" else ~(x > 0.0).all(axis=0)
+            leg = np.where(np.isnan(x).any(axis=0), ninf, xmin / R.max(axis=0))
+            tmin = min(float(np.where(np.isnan(D), ninf, D).min()), float(np.where(np.isnan(L), ninf, L).min()))
+            rep["pools"] += m
+            rep["pools_trading"] += int(((D != 0.0) | (L != 0.0)).any(axis=0).sum())
+            rep["pools_violating"] += int(bad.sum())
+            i = int(np.argmin(s))                                              # (the first of equals: the lowest upload position)
+            if rep["worst_pos"] < 0 or s[i] < rep["min_slack"]:                # (strictly: ties go to the first bucket)
+                rep.update(min_slack=float(s[i]), worst_family=b["family"], worst_kind=b["kind"], worst_k=k, worst_pos=i)
+            rep["min_tender"] = min(rep["min_tender"], tmin)
+            rep["min_leg"] = min(rep["min_leg"], float(leg.min()))
+            slacks[b["key"]] = s
+            for y, sign in ((L, 1.0), (D, -1.0)):
+                sel = y != 0.0
+                yv, tok = sign * y[sel], b["idx"][sel]
+                ok = np.abs(np.ldexp(yv, F)) < 2.0 ** 94                       # (false for values that are not finite)
+                rep["legs_out_of_range"] += int((~ok).sum())
+                a0, a1, a2 = _fixed_limbs(yv[ok], F)
+                np.add.at(L0, tok[ok], a0); np.add.at(L1, tok[ok], a1); np.add.at(L2, tok[ok], a2)
+    limbs = np.stack([L0, L1, L2.view(np.uint64)])
+    psi_int = [(int(L2[j]) << 64) + (int(L1[j]) << 32) + int(L0[j]) for j in range(n)]
+    psi = np.array([math.ldexp(float(v), -F) for v in psi_int], dtype=np.float64).reshape(n)
+    rep.update(psi=psi, psi_int=psi_int, limbs=limbs, slack=slacks)
+    if utility is not None:
+        c, h, ct = utility.c, utility.h, utility.ctype
+        r = psi + h
+        lin = ct <= FREE
+        with np.errstate(all="ignore"):
+            terms = np.where(ct == ULOG, c * np.log(np.where(ct == ULOG, r, 1.0)),
+                             np.where(ct == UQUAD, c * psi - psi * psi / (2.0 * np.where(ct == UQUAD, h, 1.0)), c * psi))
+        value = 0.0
+        for t in terms.tolist():
+            value += t
+        viol = float(np.where(ct == GE, np.maximum(-r, 0.0), np.where(ct == EQ, np.abs(r), 0.0)).max()) if n else 0.0
+        scale = max(float(np.abs(psi).max()) if n else 0.0, float(np.abs(h[lin]).max()) if lin.any() else 0.0)
+        mr = max((float(b["R"].max()) for b in audit_buckets(net)), default=0.0)
+        rep["value"] = value
+        rep["infeas"] = viol / max(scale, 1e-12 * mr, 1e-300)
+    return rep
+
+
 def apply_path(theta, dev_ties, sharded):
     """where Problem.apply_trades forms the new reserves: "device" (cfmm_apply_trades: no host leg) unless fills are held on the
     host (`theta`: the Python kink loop's), price ties / tie flags sit on the device, or the pools are sharded -- then "host\""""
@@ -631,6 +801,7 @@ class Problem:
         self.gap = None; self.infeas = None; self.dual_value = None; self.stats = None
         self._theta = {}
         self._trade_cache = None
+        self.audit_report = None       # the report of the last solve(audit=True)
         self._comm = None              # (n_ranks, rank) once the library's RCCL communicator is up
         self._host = None              # HostComm of a pool-sharded problem (cfmm.distributed.sharded_problem)
         self._dev_utility = None       # the Utility object whose data sits on the device
@@ -1111,11 +1282,64 @@ class Problem:
 
     # -- solve -------------------------------------------------------------------------------
     def solve(self, tol=1e-6, nu0=None, max_evals=2000, memory=0, iters_per_graph=8, kink_tol=1e-3,
-              max_rounds=6, warm_start=False, method="auto"):
+              max_rounds=6, warm_start=False, method="auto", audit=False):
         """`method`: "lbfgs" (first order, on-device), "newton" (barrier-smoothed second order: the remedy for
         stableswap / constant-sum pools at scale; k-asset pools enter it unsmoothed) or "auto" (second order when the
         network holds stableswap pools; otherwise first order, with the host-side active-set loop for constant-sum
-        kinks and the second-order method as its fall-back)."""
+        kinks and the second-order method as its fall-back).
+        `audit`: audit the route the solve ends on (Problem.audit, docs/audit.md) and keep the report as self.audit_report; a status of
+        "optimal" becomes "inaccurate" when a pool refuses its tenders, a contribution falls outside the fixed point, or the audited
+        psi disagrees with the reported one -- or misses the certificates -- beyond the solve's tolerance."""
+        value = self._solve(tol, nu0, max_evals, memory, iters_per_graph, kink_tol, max_rounds, warm_start, method)
+        self.audit_report = None
+        if audit and self.psi is not None and np.all(np.isfinite(self.psi)):
+            rep = self.audit_report = self.audit()
+            tolx = max(self._tol, 1e-12) * (1 + 1e-6) + 1e-15          # (_finish's bar)
+            if self.status == "optimal" and (rep["pools_violating"] > 0 or rep["legs_out_of_range"] > 0
+                                             or not (rep["psi_mismatch"] <= tolx and rep["infeas"] <= tolx and rep["gap"] <= tolx)):
+                self.status = "inaccurate"
+        return value
+
+    def audit(self, tol_pool=AUDIT_TOL_POOL):
+        """Does every pool accept the route this object hands out (deltas / lambdas / bucket_trades), and does it add up?  The report
+        of cfmm_audit_trades (docs/audit.md) as a dict, with psi (summed exactly from the tenders alone), plus
+          psi_mismatch   max |psi_audit - self.psi| / max(|psi_audit|_inf, 1e-12 max reserve)
+          gap            |self.dual_value - value| / max(1, |self.dual_value|): the audited point against the solve's dual value
+        On the device unless the pools are sharded or the tenders were repaired on the host (a worthless component taken out): then
+        the NumPy twin (audit_trades) on the tenders read back.  Fills the Python kink loop holds (constant-sum pools tied on a kink)
+        travel as the caller's own tenders."""
+        ctx = self._ensure_ctx()
+        self._pools_seen()
+        if self.utility is not None:
+            self._send_utility()
+        if self._host is not None or self._comm is not None or (self.stats or {}).get("worthless_tokens"):
+            exponent = None
+            if self._host is not None:                 # the fixed-point exponent of the WHOLE network: the shards' integers then add
+                import math
+                mf = min([1.0] + [float(b["fee"].min()) for b in audit_buckets(self.net)])
+                mf = float(min(self._host.allgather(mf)))
+                exponent = 84 - math.frexp(max(self._max_reserve(), 1e-300) / max(mf, 1e-3))[1]
+            rep = audit_trades(self.net, self._trades(), self.utility, tol_pool, exponent=exponent)
+            rep = {k: v for k, v in rep.items() if k not in ("psi_int", "limbs", "slack")}
+            rep["path"] = "host"
+        else:
+            own = None
+            if self._theta:
+                tr = self._trades()
+                own = {key: tr[key] for key in tr if key == "sum2" or (isinstance(key, tuple) and key[0] == "sum")}
+            rep = ctx.audit(own=own, tol_pool=tol_pool)
+            rep["path"] = "device"
+        psi = rep["psi"]
+        if self.psi is not None:
+            rep["psi_mismatch"] = float(np.abs(psi - self.psi).max()) / max(float(np.abs(psi).max()), 1e-12 * self._max_reserve(), 1e-300)
+        else:
+            rep["psi_mismatch"] = float("nan")
+        dv = getattr(self, "dual_value", None)
+        rep["gap"] = abs(dv - rep["value"]) / max(1.0, abs(dv)) if dv is not None else float("nan")
+        return rep
+
+    def _solve(self, tol=1e-6, nu0=None, max_evals=2000, memory=0, iters_per_graph=8, kink_tol=1e-3,
+               max_rounds=6, warm_start=False, method="auto"):
         if self.utility is None:
             raise ValueError("no utility set")
         ctx = self._ensure_ctx()

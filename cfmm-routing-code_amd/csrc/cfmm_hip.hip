@@ -40,6 +40,7 @@
 #include "phik.hpp"
 #include "update.hpp"
 #include "apply.hpp"
+#include "audit.hpp"
 #include "handoff.hpp"
 #include "solve_plan.hpp"
 #include "newton_rules.hpp"
@@ -202,6 +203,14 @@ struct cfmm_ctx {
     // cfmm_solve_sweep: grow-only slab (device, and its pinned twin) of the points' arguments, inputs, results and state; their tenders
     struct { char *dev = nullptr, *host = nullptr; size_t cap = 0; double *tr_dev = nullptr; size_t tr_cap = 0; } sweep;
     bool apply_timed = false;          // cfmm_apply_timers: HIP events around each pass's launches
+    // cfmm_audit_trades (audit.hpp), made at the first audit: on the device one AuditRec per bucket record | the [3][n] limbs | the
+    // workgroups' partial records; pinned: records | limbs read back.  audit_ovr: grow-only device copy of tenders held on the host
+    char *audit_dev = nullptr, *audit_host = nullptr;
+    double *audit_ovr = nullptr; size_t audit_ovr_cap = 0;
+    bool audit_timed = false;          // cfmm_debug_audit_launch: HIP events around the launches
+    int audit_grid = AU_GRID;          // ... and the workgroups per pass
+    double audit_sec = 0.0;
+    int audit_reordered = 0;           // buckets the last audit found stored reordered (perm non-null)
     double apply_sec[2] = {0.0, 0.0};  // ... of the last apply: the pass that checks, the pass that writes
 
     // tokens / state (device)
@@ -2407,6 +2416,9 @@ int cfmm_destroy(cfmm_ctx *ctx)
     for (int *q : ctx->flagsG) if (q) (void)hipFree(q);
     if (ctx->trade_buf) (void)hipFree(ctx->trade_buf);
     if (ctx->apply_ovr) (void)hipFree(ctx->apply_ovr);
+    if (ctx->audit_dev) (void)hipFree(ctx->audit_dev);
+    if (ctx->audit_host) (void)hipHostFree(ctx->audit_host);
+    if (ctx->audit_ovr) (void)hipFree(ctx->audit_ovr);
     if (ctx->sweep.dev) (void)hipFree(ctx->sweep.dev);
     if (ctx->sweep.host) (void)hipHostFree(ctx->sweep.host);
     if (ctx->sweep.tr_dev) (void)hipFree(ctx->sweep.tr_dev);
@@ -4782,6 +4794,192 @@ int cfmm_apply_timers(cfmm_ctx *ctx, int on, double *out2)
     if (!ctx) return CFMM_E_ARG;
     ctx->apply_timed = on != 0;
     if (out2) { out2[0] = ctx->apply_sec[0]; out2[1] = ctx->apply_sec[1]; }
+    return CFMM_OK;
+}
+
+// ---- the route audited on the device (audit.hpp; docs/audit.md) -----------------------------------------------------------------------
+// One pass over every bucket on this context's stream, as a reader of the store like the read-backs: one record per bucket slot (the
+// slots of the apply records), ONE copy (records | limbs, contiguous) and ONE synchronisation.  Nothing of the context or the store is
+// written: the scratch below is the audit's own.
+namespace {
+struct AuditSpan { size_t recs, limbs, parts, total; };
+AuditSpan audit_span(int n)
+{
+    AuditSpan s;
+    s.recs = 0; s.limbs = APPLY_RECS * sizeof(AuditRec);
+    s.parts = (s.limbs + 3 * (size_t)n * sizeof(unsigned long long) + 255) & ~(size_t)255;
+    s.total = s.parts + (size_t)APPLY_RECS * AU_GRID_MAX * sizeof(AuditRec);
+    return s;
+}
+unsigned audit_grid(const cfmm_ctx *ctx, int64_t m)
+{
+    const int64_t chunks = (m + AU_THREADS - 1) / AU_THREADS;
+    return (unsigned)std::min<int64_t>(chunks, ctx->audit_grid);
+}
+}  // namespace
+
+int cfmm_audit_trades(cfmm_ctx *ctx, const cfmm_audit_tenders *own, double tol_pool, cfmm_audit *out, double *psi, uint64_t *limbs)
+{
+    const char *who = "audit_trades";
+    if (!ctx) return CFMM_E_ARG;
+    if (!out) return fail(ctx, CFMM_E_ARG, "%s: out is NULL", who);
+    std::memset(out, 0, sizeof *out);
+    out->worst_family = out->worst_kind = out->worst_k = -1; out->worst_pos = -1;
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    out->min_slack = out->min_tender = out->min_leg = inf; out->value = out->infeas = nan;
+    if (sharded(ctx)) return fail(ctx, CFMM_E_UNSUPPORTED, "%s: pool-sharded contexts are not served (audit the shards' tenders on the host)", who);
+    const int n = ctx->n;
+    if (n > AU_MAX_TOKENS) return fail(ctx, CFMM_E_LIMIT, "%s: %d tokens exceed the workgroup's tile of 3 n 64-bit limbs (n <= %d)", who, n, AU_MAX_TOKENS);
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
+    PoolStore &ps = entry.ps;
+    if (!ctx->pt.have_nu) return fail(ctx, CFMM_E_STATE, "%s: no prices yet (cfmm_set_nu or a solve first)", who);
+    if (!(tol_pool > 0.0)) tol_pool = 1e-9;
+    const AuditSpan sp = audit_span(n);
+    if (!ctx->audit_dev) {
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->audit_dev, sp.total));
+        hipError_t e = hipHostMalloc((void **)&ctx->audit_host, sp.parts);
+        if (e != hipSuccess) { (void)hipFree(ctx->audit_dev); ctx->audit_dev = nullptr; ctx->audit_host = nullptr; return fail(ctx, CFMM_E_HIP, "%s: pinned records -> %s", who, hipGetErrorString(e)); }
+    }
+    // tenders held on the host travel to the device once: the library's kink loop's (two-asset buckets, as cfmm_get_trades2 returns them),
+    // then the caller's own for the constant-sum buckets it names
+    const TradeLayout tl = trade_layout(ps);
+    const bool kink = ctx->pt.tr_ovr_valid;
+    if (kink && ctx->pt.tr_ovr.size() < tl.two_asset()) return fail(ctx, CFMM_E_STATE, "%s: the kink loop's tenders do not match the resident buckets", who);
+    const int64_t m_sum2 = ps.r2[CFMM_POOL_SUM2].b.m;
+    const bool own2 = own && m_sum2 > 0 && (own->sum2_delta || own->sum2_lambda);
+    if (own2 && !(own->sum2_delta && own->sum2_lambda)) return fail(ctx, CFMM_E_ARG, "%s: own names one array of the constant-sum bucket without the other", who);
+    size_t len = kink ? tl.two_asset() : 0, off_own2 = 0, off_ownk[CFMM_MAX_POOL_SIZE + 1] = {};
+    bool ownk[CFMM_MAX_POOL_SIZE + 1] = {};
+    if (own2) { off_own2 = len; len += 4 * (size_t)m_sum2; }
+    for (int k = 2; own && k <= CFMM_MAX_POOL_SIZE; ++k) {
+        const int64_t m = ps.rg[CFMM_POOLK_SUM][k].b.m;
+        if (m == 0 || !(own->sumk_delta[k] || own->sumk_lambda[k])) continue;
+        if (!(own->sumk_delta[k] && own->sumk_lambda[k])) return fail(ctx, CFMM_E_ARG, "%s: own names one array of the %d-asset constant-sum bucket without the other", who, k);
+        ownk[k] = true; off_ownk[k] = len; len += 2 * (size_t)k * m;
+    }
+    if (len > ctx->audit_ovr_cap) {
+        if (ctx->audit_ovr) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->audit_ovr); ctx->audit_ovr = nullptr; ctx->audit_ovr_cap = 0; }
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->audit_ovr, len * sizeof(double)));
+        ctx->audit_ovr_cap = len;
+    }
+    auto send = [&](size_t off, const double *src, size_t cnt) { return cnt ? hipMemcpyAsync(ctx->audit_ovr + off, src, cnt * sizeof(double), hipMemcpyHostToDevice, ctx->stream) : hipSuccess; };
+    if (kink) HIP_TRY(ctx, send(0, ctx->pt.tr_ovr.data(), tl.two_asset()));
+    if (own2) { HIP_TRY(ctx, send(off_own2, own->sum2_delta, 2 * (size_t)m_sum2)); HIP_TRY(ctx, send(off_own2 + 2 * (size_t)m_sum2, own->sum2_lambda, 2 * (size_t)m_sum2)); }
+    for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k)
+        if (ownk[k]) {
+            const size_t cnt = (size_t)k * ps.rg[CFMM_POOLK_SUM][k].b.m;
+            HIP_TRY(ctx, send(off_ownk[k], own->sumk_delta[k], cnt)); HIP_TRY(ctx, send(off_ownk[k] + cnt, own->sumk_lambda[k], cnt));
+        }
+    // the pass
+    double sc, scd;
+    det_scales(ctx, sc, scd);
+    AuditArgs a;
+    a.n = n; a.sc = sc; a.tol = tol_pool;
+    a.limbs = (unsigned long long *)(ctx->audit_dev + sp.limbs);
+    AuditRec *recs = (AuditRec *)(ctx->audit_dev + sp.recs), *parts = (AuditRec *)(ctx->audit_dev + sp.parts);
+    const size_t lds = 3 * (size_t)n * sizeof(unsigned long long);
+    const double *nu = ctx->nu_acc;
+    const double mu = ctx->pt.mu_last > 0.0 ? ctx->pt.mu_last : 0.0;
+    const double *slo = (mu > 0.0 && ctx->pt.slo_active) ? ctx->sm_slo : nullptr;
+    const dim3 blk(AU_THREADS);
+    const bool timed = ctx->audit_timed;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->audit_dev, 0, sp.parts, ctx->stream));
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
+    auto slot = [&](int q) { a.rec = recs + q; a.part = parts + (size_t)q * AU_GRID_MAX; };
+    ctx->audit_reordered = 0;
+    for (int kind = 0; kind < CFMM_POOL_KINDS2; ++kind) {
+        Bucket2 b = ps.r2[kind].b;
+        if (b.m == 0) continue;
+        if (kind == CFMM_POOL_SUM2) b.flags = ctx->flags2;                  // (as cfmm_get_trades2: flagged pools hand out zeros)
+        const double *ov = (kind == CFMM_POOL_SUM2 && own2) ? ctx->audit_ovr + off_own2 : (kink ? ctx->audit_ovr + tl.off2[kind] : nullptr);
+        slot(apply_rec2(kind));
+        ctx->audit_reordered += b.perm != nullptr;
+        with_int<0, 4>(kind, [&](auto K) { hipLaunchKernelGGL(audit2_kernel<K>, dim3(audit_grid(ctx, b.m)), blk, lds, ctx->stream, b, nu, slo, mu, ov, a); });
+    }
+    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) {
+        const BucketN b = ps.rn[k].b;
+        if (b.m == 0) continue;
+        slot(apply_recN(k));
+        ctx->audit_reordered += b.perm != nullptr;
+        with_int<3, 8>(k, [&](auto K) { hipLaunchKernelGGL(auditN_kernel<K>, dim3(audit_grid(ctx, b.m)), blk, lds, ctx->stream, b, nu, slo, a); });
+    }
+    for (int kind = 0; kind < CFMM_POOLK_KINDS; ++kind)
+        for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) {
+            const BucketG b = ps.rg[kind][k].b;
+            if (b.m == 0) continue;
+            const int *fl = kind == CFMM_POOLK_SUM ? ctx->flagsG[k] : nullptr;          // (as cfmm_get_tradesG)
+            const double *ov = (kind == CFMM_POOLK_SUM && ownk[k]) ? ctx->audit_ovr + off_ownk[k] : nullptr;
+            slot(apply_recG(kind, k));
+            with_int<CFMM_POOLK_STABLE, CFMM_POOLK_SUM>(kind, [&](auto KIND) {
+                with_int<2, 8>(k, [&](auto K) { hipLaunchKernelGGL((auditG_kernel<KIND, K>), dim3(audit_grid(ctx, b.m)), blk, lds, ctx->stream, b, fl, nu, slo, mu, ov, a); });
+            });
+        }
+    HIP_TRY(ctx, hipGetLastError());
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->audit_host, ctx->audit_dev, sp.parts, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (timed) { float ms = 0.f; HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1)); ctx->audit_sec = ms * 1e-3; }
+    // the report
+    const AuditRec *res = (const AuditRec *)(ctx->audit_host + sp.recs);
+    const unsigned long long *hl = (const unsigned long long *)(ctx->audit_host + sp.limbs);
+    int F = 0;
+    (void)std::frexp(sc, &F); F -= 1;                                       // sc = 2^F
+    out->fixed_exponent = F;
+    unsigned long long best = ~0ull;
+    int first = -1;
+    unsigned long long tender = ~0ull, leg = ~0ull;
+    auto take = [&](int64_t m, int q) {
+        if (m == 0) return;
+        out->pools += m; out->pools_trading += (int64_t)res[q].trading; out->pools_violating += (int64_t)res[q].violating; out->legs_out_of_range += (int64_t)res[q].oor;
+        if (first < 0 || res[q].slack < best) { best = res[q].slack; first = q; }       // (ties: the first in bucket order)
+        tender = std::min(tender, res[q].tender); leg = std::min(leg, res[q].leg);
+    };
+    for (int kind = 0; kind < CFMM_POOL_KINDS2; ++kind) take(ps.r2[kind].b.m, apply_rec2(kind));
+    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) take(ps.rn[k].b.m, apply_recN(k));
+    for (int kind = 0; kind < CFMM_POOLK_KINDS; ++kind) for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) take(ps.rg[kind][k].b.m, apply_recG(kind, k));
+    if (first >= 0) {
+        int fam = 0, kind = first, k = 2;
+        if (first >= apply_recG(0, 0)) { fam = 2; kind = (first - apply_recG(0, 0)) / (CFMM_MAX_POOL_SIZE + 1); k = (first - apply_recG(0, 0)) % (CFMM_MAX_POOL_SIZE + 1); }
+        else if (first >= apply_recN(0)) { fam = 1; kind = 0; k = first - apply_recN(0); }
+        out->worst_family = fam; out->worst_kind = kind; out->worst_k = k; out->worst_pos = (int64_t)res[first].pos;
+        out->min_slack = audit_unord(best); out->min_tender = audit_unord(tender); out->min_leg = audit_unord(leg);
+    }
+    if (limbs) std::memcpy(limbs, hl, 3 * (size_t)n * sizeof(uint64_t));
+    std::vector<double> hp((size_t)n);
+    for (int j = 0; j < n; ++j) {
+        const Fixed128 t = fixed_combine(hl[j], hl[n + j], hl[2 * (size_t)n + j]);
+        const __int128 v = (__int128)(((unsigned __int128)(unsigned long long)t.hi << 64) | (unsigned __int128)t.lo);
+        hp[j] = std::ldexp((double)v, -F);                                  // one correctly rounded conversion, one exact scaling
+    }
+    if (psi) std::memcpy(psi, hp.data(), (size_t)n * sizeof(double));
+    if (ctx->have_utility) {
+        // linear-plus-box tokens as sweep::point_certificates (cfmm_stats); the utility table's entries by their own u, outside infeas
+        double value = 0.0, viol = 0.0, scale = 0.0;
+        for (int j = 0; j < n; ++j) {
+            const double c = ctx->hc[j], h = ctx->hh[j], r = hp[j] + h;
+            const int ct = ctx->hctype[j];
+            if (ct == CFMM_ULOG) value += c * std::log(r);
+            else if (ct == CFMM_UQUAD) value += c * hp[j] - hp[j] * hp[j] / (2.0 * h);
+            else {
+                value += c * hp[j];
+                viol = std::max(viol, ct == CFMM_GE ? std::max(-r, 0.0) : (ct == CFMM_EQ ? std::fabs(r) : 0.0));
+                scale = std::max(scale, std::fabs(h));
+            }
+            scale = std::max(scale, std::fabs(hp[j]));
+        }
+        out->value = value;
+        out->infeas = viol / std::max(std::max(scale, 1e-12 * ctx->max_reserve), 1e-300);
+    }
+    return CFMM_OK;
+}
+
+int cfmm_debug_audit_launch(cfmm_ctx *ctx, int timed, int grid, double *out2)
+{
+    if (!ctx) return CFMM_E_ARG;
+    if (grid < 0 || grid > AU_GRID_MAX) return fail(ctx, CFMM_E_ARG, "debug_audit_launch: grid %d is outside 0 (unchanged), 1 .. %d", grid, AU_GRID_MAX);
+    ctx->audit_timed = timed != 0;
+    if (grid > 0) ctx->audit_grid = grid;
+    if (out2) { out2[0] = ctx->audit_sec; out2[1] = (double)ctx->audit_reordered; }
     return CFMM_OK;
 }
 

@@ -227,6 +227,55 @@ int cfmm_get_reservesG(cfmm_ctx *ctx, int kind, int k, double *R /* [k][m] */, d
 /* measurement hook (tools/apply_timing.py): with `on`, every cfmm_apply_trades brackets each pass's launches with HIP events;
  * out2 (or NULL) receives the seconds of the last apply's checking pass and writing pass */
 int cfmm_apply_timers(cfmm_ctx *ctx, int on, double *out2);
+/* The route audited on the device (docs/audit.md): does every pool accept the tenders cfmm_get_trades2 / N / G would return at the moment
+ * of the call -- every bucket, at the context's accepted prices: the exact pool solutions after a first-order solve or cfmm_set_nu, the
+ * gross smoothed tenders after a second-order solve, the tenders with their partial fills after CFMM_METHOD_AUTO's own kink loop -- and
+ * what do they add up to?  The answer is formed from the tenders alone, not from the psi the evaluation kernels summed nor from any
+ * active-set bookkeeping.  Per pool, with x_j = (R_j + gamma Delta_j) - Lambda_j (every operation rounded on its own):
+ *   slack       the relative change of the trading function, >= 0 when the pool accepts the trade:
+ *               CFMM_POOL_CP2 / _W2 / geo-mean N   sum_j w_j log(x_j / R_j)              (w = 1/2, 1/2;  wa, 1 - wa;  the bucket's weights)
+ *               CFMM_POOL_SUM2 / CFMM_POOLK_SUM    (sum x - sum R) / sum R
+ *               CFMM_POOL_CURVE2 / CFMM_POOLK_STABLE   (phi(x) - phi(R)) / (sum R + alpha / prod R),  phi(x) = sum x - alpha / prod x
+ *               CFMM_POOL_POW2                     (phi(x) - phi(R)) / phi(R),  phi(x) = sum x^(1 - t);     not finite: counts as -inf
+ *   a pool VIOLATES if slack < -tol_pool, or a tender is negative or not finite, or a leg does not stay positive: x_j <= 0 -- for the
+ *               constant-sum kinds x_j < -tol_pool sum R: a fully drained leg is feasible there (arbitrage.py:73-74)
+ *   tol_pool <= 0: the default 1e-9, the stopping residual of the table's stableswap search (csrc/phik.hpp: pool_stable_k, ftol), the
+ *               loosest per-pool solver.
+ * psi, exactly: every non-zero Lambda_j adds +Lambda_j to its token and every non-zero Delta_j adds -Delta_j, each floored on its own to
+ * the reproducible mode's 96-bit fixed point floor(y 2^F) (F: the exponent cfmm_set_deterministic would use for this context; the mode
+ * itself is neither needed nor switched) and accumulated with integer atomics; a contribution that is not finite or has |y 2^F| >= 2^94 is
+ * left out and counted.  limbs: the raw sums, laid out as cfmm_debug_eval_limbs'; psi[j]: their value converted once, correctly rounded.
+ * Bitwise the same on every run and for any launch geometry.  value / infeas: from that psi and the utility last set (NaN without one):
+ * c'psi and the violation of psi + h over max(|psi|, |h|, 1e-12 max reserve) as in cfmm_stats; for CFMM_ULOG / CFMM_UQUAD tokens the
+ * entry's u(psi), and only the CFMM_GE / CFMM_EQ tokens enter infeas.
+ *   own         NULL, or tenders the CALLER holds for constant-sum buckets (its own kink loop's fills; both arrays of a bucket or
+ *               neither): they replace the device's tenders for that bucket.  Ignored for an empty bucket.
+ * Violations are a result, not an error: the call returns CFMM_OK.  It changes nothing a later call can see (no pool column, warm start,
+ * generation, price, cached solution or captured launch) and counts as a reader of the pools like cfmm_get_trades*; unlike
+ * cfmm_apply_trades it serves contexts with tie flags or price ties (it audits what the read-backs return: zeros for flagged pools).
+ * Refusals: no prices yet -> CFMM_E_STATE; pool-sharded context -> CFMM_E_UNSUPPORTED; out == NULL -> CFMM_E_ARG; more than 2560 tokens
+ * (the workgroup's tile of 3 n limbs) -> CFMM_E_LIMIT. */
+typedef struct {            /* replacement tenders the CALLER holds (its own kink loop's fills), upload order, or NULL each */
+    const double *sum2_delta, *sum2_lambda;                       /* [2][m] of CFMM_POOL_SUM2                       */
+    const double *sumk_delta[CFMM_MAX_POOL_SIZE + 1],             /* index k: [k][m] of the CFMM_POOLK_SUM bucket    */
+                 *sumk_lambda[CFMM_MAX_POOL_SIZE + 1];            /*          of k assets                            */
+} cfmm_audit_tenders;
+
+typedef struct {
+    int64_t pools, pools_trading, pools_violating, legs_out_of_range;
+    int32_t worst_family, worst_kind, worst_k, fixed_exponent;    /* family / kind / k as in cfmm_apply_info; F of psi */
+    int64_t worst_pos;                                            /* upload order; -1s when no pool is resident        */
+    double  min_slack, min_tender, min_leg;                       /* over every pool (+inf when none is resident); min_leg: x_j / max_j R_j */
+    double  value, infeas;                                        /* from the audited psi and the utility last set     */
+} cfmm_audit;
+
+int cfmm_audit_trades(cfmm_ctx *ctx, const cfmm_audit_tenders *own /* or NULL */, double tol_pool /* <= 0: default */,
+                      cfmm_audit *out, double *psi /* [n] or NULL */, uint64_t *limbs /* [3][n] or NULL */);
+/* test and measurement hook of the audit's launches (tools/audit_timing.py, tests/test_gpu_audit.py), not part of the product's
+ * interface: with `timed`, every cfmm_audit_trades brackets its launches with HIP events; grid > 0: workgroups per pass from then on
+ * (1 .. 2048; 0: leave as it is -- the audited result does not depend on it); out2 (or NULL) receives {seconds of the last audit's
+ * launches, number of buckets the last audit found stored reordered (positions mapped through the upload's permutation)} */
+int cfmm_debug_audit_launch(cfmm_ctx *ctx, int timed, int grid, double *out2);
 /* constant-sum pools sitting on their kink are `tied` (flag 1): they are skipped by the
  * kernels and their fill fraction is assigned by the host's primal recovery */
 int cfmm_set_pool_flags(cfmm_ctx *ctx, int kind, const int32_t *flags /* [m] or NULL */);
