@@ -16,19 +16,12 @@
 #include "kernels.hpp"
 #include "smooth.hpp"
 #include "phik.hpp"
+#include "route_rules.hpp"             // ApplyRec: what a WRITE = false pass leaves per bucket
 
 namespace cfmm {
 
 constexpr int AP_THREADS = 256;
 static_assert(AP_THREADS == GK_THREADS, "the apply passes keep the read-back kernels' thread mapping");
-
-// what a WRITE = false pass leaves per bucket (zeroed, `first` all ones, before the pass)
-struct ApplyRec {
-    unsigned long long moved;         // pools with a non-zero tender
-    unsigned long long refused;       // pools with a leg that would not stay positive and finite
-    unsigned long long first;         // smallest upload-order position among them
-    unsigned long long maxbits;       // bit pattern of the largest new reserve (positive doubles order like their bits)
-};
 
 __device__ __forceinline__ double post_trade_reserve(double R, double g, double D, double L)
 {

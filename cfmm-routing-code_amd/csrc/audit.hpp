@@ -35,27 +35,8 @@ static_assert(AU_THREADS == GK_THREADS, "the audit passes keep the read-back ker
 enum { AU_LOG = 0, AU_SUM = 1, AU_STABLE = 2, AU_POW = 3 };
 constexpr int audit_class2(int kind) { return kind == 2 ? AU_SUM : kind == 3 ? AU_STABLE : kind == 4 ? AU_POW : AU_LOG; }
 
-// doubles as unsigned integers of the same order (NaN counts as -inf: a quantity that cannot be computed is the worst one)
-__host__ __device__ __forceinline__ unsigned long long audit_ord(double x)
-{
-    if (x != x) x = -__builtin_huge_val();
-    unsigned long long b;
-    __builtin_memcpy(&b, &x, sizeof b);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-inline double audit_unord(unsigned long long u)
-{
-    const unsigned long long b = (u >> 63) ? (u & 0x7fffffffffffffffull) : ~u;
-    double x;
-    __builtin_memcpy(&x, &b, sizeof x);
-    return x;
-}
-
-// one per bucket slot (and one partial per workgroup): counts, the smallest slack with the lowest upload position that holds it, the
-// smallest tender and leg ratio (audit_ord images), and the workgroups that have left their partial (zeroed before the pass)
-struct AuditRec {
-    unsigned long long trading, violating, oor, slack, pos, tender, leg, done;
-};
+// AuditRec, one per bucket slot (and one partial per workgroup), and the order-preserving images audit_ord / audit_unord of its
+// minima: route_rules.hpp, where the host folds them
 __host__ __device__ __forceinline__ AuditRec audit_identity() { return AuditRec{0ull, 0ull, 0ull, ~0ull, ~0ull, ~0ull, ~0ull, 0ull}; }
 __host__ __device__ __forceinline__ void audit_merge(AuditRec &a, const AuditRec &b)
 {

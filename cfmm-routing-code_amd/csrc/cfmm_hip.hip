@@ -45,6 +45,7 @@
 #include "solve_plan.hpp"
 #include "newton_rules.hpp"
 #include "sweep_rules.hpp"
+#include "route_rules.hpp"
 
 using namespace cfmm;
 
@@ -149,23 +150,31 @@ struct PoolStore {
     }
 };
 
-// Where the context's prices and solution are, and what the read-backs may return: assigned only by the transitions next to pools_changed
-// the per-point layout of the tenders cfmm_solve_sweep hands out (and Point::tr_ovr keeps): for every bucket in the order two-asset
-// kinds 0.., then K = 3..8: delta [k][m] | lambda [k][m]
-struct TradeLayout {
-    size_t off2[CFMM_POOL_KINDS2], offn[CFMM_MAX_POOL_SIZE + 1], stride;      // a bucket's first double; doubles per point
-    size_t two_asset() const { return offn[3]; }                                // doubles of the two-asset kinds, which come first
-};
-static TradeLayout trade_layout(const PoolStore &ps)
+// The non-empty resident buckets in bucket order (route_rules.hpp: each_slot): f(record, slot, FAMILY, KIND, K), the last three as
+// compile-time constants (family 0: r2[KIND], K = 2; 1: rn[K], KIND = 0; 2: rg[KIND][K]) -- `if constexpr` on the family names a
+// family's kernels for exactly the kinds and sizes its buckets have
+template <class Store, class F> static void each_bucket(Store &ps, F &&f)
 {
-    TradeLayout t = {};
-    size_t off = 0;
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) { t.off2[k] = off; off += 4 * (size_t)ps.r2[k].b.m; }
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) { t.offn[k] = off; off += 2 * (size_t)k * ps.rn[k].b.m; }
-    t.stride = off;
-    return t;
+    using std::integral_constant;
+    route::each_slot([&](int q, int family, int kind, int k) {
+        if (family == 0) {
+            if (ps.r2[kind].b.m) with_int<0, 4>(kind, [&](auto KIND) { f(ps.r2[kind], q, integral_constant<int, 0>{}, KIND, integral_constant<int, 2>{}); });
+        } else if (family == 1) {
+            if (ps.rn[k].b.m) with_int<3, 8>(k, [&](auto K) { f(ps.rn[k], q, integral_constant<int, 1>{}, integral_constant<int, 0>{}, K); });
+        } else if (ps.rg[kind][k].b.m)
+            with_int<CFMM_POOLK_STABLE, CFMM_POOLK_SUM>(kind, [&](auto KIND) { with_int<2, 8>(k, [&](auto K) { f(ps.rg[kind][k], q, integral_constant<int, 2>{}, KIND, K); }); });
+    });
 }
+static route::Counts bucket_counts(const PoolStore &ps)
+{
+    route::Counts c = {};
+    each_bucket(ps, [&](auto &r, int q, auto, auto, auto) { c.m[q] = r.b.m; });
+    return c;
+}
+using route::TradeLayout;
+static TradeLayout trade_layout(const PoolStore &ps) { return route::trade_layout(bucket_counts(ps)); }
 
+// Where the context's prices and solution are, and what the read-backs may return: assigned only by the transitions next to pools_changed
 struct Point {
     bool have_nu = false;              // nu_acc holds prices: the caller's or a solve's
     bool hsol_valid = false;           // hsol holds nu | psi of the last solve
@@ -174,9 +183,6 @@ struct Point {
     std::vector<double> tr_ovr;        // tenders the library's kink loop left (solve_tiny_kinks; cfmm_solve_sweep's `trades` layout):
     bool tr_ovr_valid = false;         // what cfmm_get_trades2 returns while set
 };
-
-// records of cfmm_apply_trades' first pass: one per slot of PoolStore::r2 | rn | rg[0] | rg[1]
-constexpr int APPLY_RECS = CFMM_POOL_KINDS2 + (CFMM_MAX_POOL_SIZE + 1) + CFMM_POOLK_KINDS * (CFMM_MAX_POOL_SIZE + 1);
 
 struct cfmm_ctx {
     int device = 0, n = 0, ng = 0;
@@ -196,17 +202,18 @@ struct cfmm_ctx {
     int *flagsG[CFMM_MAX_POOL_SIZE + 1] = {};      // per-leg tie flags of the table's constant-sum buckets (cfmm_set_pool_flagsG), pool-major
     double *trade_buf = nullptr;       // grow-only scratch for cfmm_get_trades* (delta | lambda)
     size_t trade_cap = 0;
-    // cfmm_apply_trades (apply.hpp): one ApplyRec per bucket record on the device; pinned [2][APPLY_RECS]: their start values | read back
+    // cfmm_apply_trades (apply.hpp): one ApplyRec per bucket slot on the device; pinned [2][route::SLOTS]: their start values | read back
     // (pieces of the two arenas below)
     ApplyRec *apply_dev = nullptr, *apply_host = nullptr;
-    double *apply_ovr = nullptr; size_t apply_ovr_cap = 0;     // grow-only device copy of the kink loop's tenders (Point::tr_ovr)
+    // grow-only device copy of tenders held on the host (Point::tr_ovr, cfmm_audit_tenders): the apply and the audit each upload what
+    // they need in front of their own passes, on this context's stream
+    double *tender_dev = nullptr; size_t tender_cap = 0;
     // cfmm_solve_sweep: grow-only slab (device, and its pinned twin) of the points' arguments, inputs, results and state; their tenders
     struct { char *dev = nullptr, *host = nullptr; size_t cap = 0; double *tr_dev = nullptr; size_t tr_cap = 0; } sweep;
     bool apply_timed = false;          // cfmm_apply_timers: HIP events around each pass's launches
     // cfmm_audit_trades (audit.hpp), made at the first audit: on the device one AuditRec per bucket record | the [3][n] limbs | the
-    // workgroups' partial records; pinned: records | limbs read back.  audit_ovr: grow-only device copy of tenders held on the host
+    // workgroups' partial records; pinned: records | limbs read back
     char *audit_dev = nullptr, *audit_host = nullptr;
-    double *audit_ovr = nullptr; size_t audit_ovr_cap = 0;
     bool audit_timed = false;          // cfmm_debug_audit_launch: HIP events around the launches
     int audit_grid = AU_GRID;          // ... and the workgroups per pass
     double audit_sec = 0.0;
@@ -811,6 +818,14 @@ void point_published(cfmm_ctx *ctx, double mu, bool slo, std::vector<double> *te
 void drop_tenders(cfmm_ctx *ctx) { ctx->pt.tr_ovr_valid = false; }
 // a first-order solve is about to move the point, or the smoothed state of its barrier weight was overwritten (cfmm_time_newton_kernels)
 void drop_barrier(cfmm_ctx *ctx) { ctx->pt.mu_last = 0.0; ctx->pt.slo_active = false; }
+// the point whose tenders the read-backs hand out, the apply moves and the audit checks (route_rules.hpp: point_view): the accepted
+// prices, the last solve's low-order log-prices (NULL: not in use) and its barrier weight (0: the exact pool solutions)
+struct TenderPoint { const double *nu, *slo; double mu; };
+TenderPoint tender_point(const cfmm_ctx *ctx)
+{
+    const route::PointView v = route::point_view(ctx->pt.mu_last, ctx->pt.slo_active);
+    return {ctx->nu_acc, v.use_slo ? ctx->sm_slo : nullptr, v.mu};
+}
 // the reserves moved (a re-upload, or an update through any context of the store): the largest reserve, the captured launches that carry
 // it, the cached solution, the barrier weight and the kink tenders go; prices, utility, ties and tie flags stay (a solve from NULL goes on)
 void reserves_moved(cfmm_ctx *ctx)
@@ -1741,10 +1756,10 @@ int listed_tokens(cfmm_ctx *ctx)
         const unsigned grid = (unsigned)std::min<long long>((count + 255) / 256, 4ll * ctx->cus);
         hipLaunchKernelGGL(mark_tokens_kernel, dim3(grid), dim3(256), 0, ctx->stream, ids, count, mark);
     };
-    const PoolStore &ps = *ctx->pools;
-    for (int k = 0; k < CFMM_POOL_KINDS2; ++k) { pass(ps.r2[k].b.ia, ps.r2[k].b.m); pass(ps.r2[k].b.ib, ps.r2[k].b.m); }
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) pass(ps.rn[k].b.idx, (long long)k * ps.rn[k].b.m);
-    for (auto &row : ps.rg) for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) pass(row[k].b.idx, (long long)k * row[k].b.m);
+    each_bucket(*ctx->pools, [&](auto &r, int, auto FAMILY, auto, auto K) {
+        if constexpr (FAMILY == 0) { pass(r.b.ia, r.b.m); pass(r.b.ib, r.b.m); }
+        else pass(r.b.idx, (long long)K * r.b.m);
+    });
     HIP_TRY(ctx, hipGetLastError());
     if (sharded(ctx)) { int rc = all_reduce(ctx, mark, (size_t)n, NCCL_FLOAT64, NCCL_SUM); if (rc) return rc; }
     std::vector<double> h(n);
@@ -2295,7 +2310,7 @@ int cfmm_create(int device, int n_tokens, cfmm_ctx **out)
         want(&ctx->st3, 3);
         want(&ctx->acc_l, 6 * (size_t)n + 4);
         want(&ctx->ts, 64 + 8 * 4096 + 2048);
-        want(&ctx->apply_dev, APPLY_RECS);
+        want(&ctx->apply_dev, route::SLOTS);
         size_t total = 0;
         for (auto &pc : pieces) total += (pc.bytes + 16 + 255) & ~(size_t)255;
         TRY_C(hipMalloc((void **)&ctx->dev_arena, total));
@@ -2304,7 +2319,7 @@ int cfmm_create(int device, int n_tokens, cfmm_ctx **out)
         for (auto &pc : pieces) { *pc.dst = ctx->dev_arena + off; off += (pc.bytes + 16 + 255) & ~(size_t)255; }
         ctx->util_span = (size_t)((char *)ctx->off - (char *)ctx->c);
         const size_t hb[6] = {2 * sizeof(DevState), 6 * sizeof(DevState), 2 * (size_t)n * sizeof(double), (size_t)n * sizeof(double), ctx->util_span,
-                              2 * APPLY_RECS * sizeof(ApplyRec)};
+                              2 * route::SLOTS * sizeof(ApplyRec)};
         size_t ho[7] = {0, 0, 0, 0, 0, 0, 0};
         for (int q = 0; q < 6; ++q) ho[q + 1] = ho[q] + ((hb[q] + 255) & ~(size_t)255);
         TRY_C(hipHostMalloc((void **)&ctx->host_arena, ho[6], hipHostMallocDefault));      // (pinned, host-cached, and reachable from the device through hipHostGetDevicePointer)
@@ -2318,7 +2333,7 @@ int cfmm_create(int device, int n_tokens, cfmm_ctx **out)
         ctx->util_h = ctx->host_arena + ho[4];
         std::memset(ctx->util_h, 0, ctx->util_span);
         ctx->apply_host = (ApplyRec *)(ctx->host_arena + ho[5]);
-        for (int q = 0; q < APPLY_RECS; ++q) ctx->apply_host[q] = ApplyRec{0ull, 0ull, ~0ull, 0ull};
+        for (int q = 0; q < route::SLOTS; ++q) ctx->apply_host[q] = ApplyRec{0ull, 0ull, ~0ull, 0ull};
     }
     lap("device + pinned arenas");
     TRY_C(hipHostMalloc((void **)&ctx->hstat_h, 64 + ITER_HRING * sizeof(unsigned long long) + 64, hipHostMallocMapped));      // (8 progress words | the per-launch ring | the envelope record)
@@ -2415,10 +2430,9 @@ int cfmm_destroy(cfmm_ctx *ctx)
     if (ctx->flags2) (void)hipFree(ctx->flags2);
     for (int *q : ctx->flagsG) if (q) (void)hipFree(q);
     if (ctx->trade_buf) (void)hipFree(ctx->trade_buf);
-    if (ctx->apply_ovr) (void)hipFree(ctx->apply_ovr);
+    if (ctx->tender_dev) (void)hipFree(ctx->tender_dev);
     if (ctx->audit_dev) (void)hipFree(ctx->audit_dev);
     if (ctx->audit_host) (void)hipHostFree(ctx->audit_host);
-    if (ctx->audit_ovr) (void)hipFree(ctx->audit_ovr);
     if (ctx->sweep.dev) (void)hipFree(ctx->sweep.dev);
     if (ctx->sweep.host) (void)hipHostFree(ctx->sweep.host);
     if (ctx->sweep.tr_dev) (void)hipFree(ctx->sweep.tr_dev);
@@ -3095,13 +3109,11 @@ int cfmm_get_tradesG(cfmm_ctx *ctx, int kind, int k, double *delta, double *lamb
     const BucketG &b = ctx->pools->rg[kind][k].b;
     if (b.m == 0) return CFMM_OK;
     const dim3 grid((unsigned)((b.m + GK_THREADS - 1) / GK_THREADS)), blk(GK_THREADS);
-    const double *nu = ctx->nu_acc;
     const int *fl = kind == CFMM_POOLK_SUM ? ctx->flagsG[k] : nullptr;
-    const double *slo = (ctx->pt.mu_last > 0.0 && ctx->pt.slo_active) ? ctx->sm_slo : nullptr;       // (as cfmm_get_tradesN)
-    const double mu = ctx->pt.mu_last > 0.0 ? ctx->pt.mu_last : 0.0;     // (behind a second-order solve: the constant-sum entry's smoothed tenders)
+    const TenderPoint p = tender_point(ctx);           // (mu > 0: the constant-sum entry's smoothed tenders)
     return read_back(ctx, "get_tradesG", (size_t)k * b.m, delta, lambda, [&](double *dd, double *dl) {
         with_int<CFMM_POOLK_STABLE, CFMM_POOLK_SUM>(kind, [&](auto KIND) {
-            with_int<2, 8>(k, [&](auto K) { hipLaunchKernelGGL((tradesg_kernel<KIND, K>), grid, blk, 0, ctx->stream, b, fl, nu, slo, mu, dd, dl); });
+            with_int<2, 8>(k, [&](auto K) { hipLaunchKernelGGL((tradesg_kernel<KIND, K>), grid, blk, 0, ctx->stream, b, fl, p.nu, p.slo, p.mu, dd, dl); });
         });
     });
 }
@@ -4461,24 +4473,15 @@ int sweep_read_tenders(SweepRun &R, double *trades_out)
         const int *fl_d = R.msum ? L.flags(R.dev, 0) : nullptr;
         const int fls = (int)(2 * L.a_stride);
         const dim3 blk(256);
-        for (int k = 0; k < CFMM_POOL_KINDS2; ++k) {
-            Bucket2 b = ctx->pools->r2[k].b;
-            if (b.m == 0) continue;
-            const dim3 grid((unsigned)((b.m + 255) / 256), (unsigned)R.B);
-            double *dd = td + R.T.off2[k], *dl = dd + 2 * b.m;
-            with_int<0, 4>(k, [&](auto K) {
-                hipLaunchKernelGGL(trades2_sweep_kernel<K>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride, fl_d, fls);
-            });
-        }
-        for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) {
-            const BucketN &b = ctx->pools->rn[k].b;
-            if (b.m == 0) continue;
-            const dim3 grid((unsigned)((b.m + 255) / 256), (unsigned)R.B);
-            double *dd = td + R.T.offn[k], *dl = dd + (size_t)k * b.m;
-            with_int<3, 8>(k, [&](auto K) {
-                hipLaunchKernelGGL(tradesn_sweep_kernel<K>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride);
-            });
-        }
+        each_bucket(*ctx->pools, [&](auto &r, int, auto FAMILY, auto KIND, auto K) {
+            if constexpr (FAMILY < 2) {                 // (the table's buckets are not part of the layout)
+                const auto b = r.b;
+                const dim3 grid((unsigned)((b.m + 255) / 256), (unsigned)R.B);
+                double *dd = td + (FAMILY == 0 ? R.T.off2[KIND] : R.T.offn[K]), *dl = dd + (size_t)K * b.m;
+                if constexpr (FAMILY == 0) hipLaunchKernelGGL(trades2_sweep_kernel<KIND>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride, fl_d, fls);
+                else hipLaunchKernelGGL(tradesn_sweep_kernel<K>, grid, blk, 0, ctx->stream, b, nu_d, nus, dd, dl, (long long)tr_stride);
+            }
+        });
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
         { int rc = download_staged(ctx, trades_out, td, (size_t)R.B * tr_stride * sizeof(double)); if (rc) return rc; }
@@ -4561,13 +4564,11 @@ int cfmm_get_trades2(cfmm_ctx *ctx, int kind, double *delta, double *lambda)
         return CFMM_OK;
     }
     const dim3 grid((unsigned)((b.m + 255) / 256)), blk(256);
-    const double *nu = ctx->nu_acc;
+    const TenderPoint p = tender_point(ctx);
     return read_back(ctx, "get_trades2", 2 * (size_t)b.m, delta, lambda, [&](double *dd, double *dl) {
         with_int<0, 4>(kind, [&](auto K) {
-            if (ctx->pt.mu_last > 0.0) {           // after a second-order solve: the smoothed primal point
-                const double *slo = ctx->pt.slo_active ? ctx->sm_slo : nullptr;
-                hipLaunchKernelGGL(smooth_trades_kernel<K>, grid, blk, 0, ctx->stream, b, nu, slo, ctx->pt.mu_last, dd, dl);
-            } else hipLaunchKernelGGL(trades2_kernel<K>, grid, blk, 0, ctx->stream, b, nu, dd, dl);
+            if (p.mu > 0.0) hipLaunchKernelGGL(smooth_trades_kernel<K>, grid, blk, 0, ctx->stream, b, p.nu, p.slo, p.mu, dd, dl);      // after a second-order solve: the smoothed primal point
+            else hipLaunchKernelGGL(trades2_kernel<K>, grid, blk, 0, ctx->stream, b, p.nu, dd, dl);
         });
     });
 }
@@ -4579,27 +4580,25 @@ int cfmm_get_tradesN(cfmm_ctx *ctx, int k, double *delta, double *lambda)
     const BucketN &b = ctx->pools->rn[k].b;
     if (b.m == 0) return CFMM_OK;
     const dim3 grid((unsigned)((b.m + 255) / 256)), blk(256);
-    const double *nu = ctx->nu_acc;
-    // after a second-order solve that ended with low-order log-prices the k-asset pools were evaluated with them
-    // (gn_newton_kernel): the tenders handed out must be those of the same point, or they would not sum to psi
-    const double *slo = (ctx->pt.mu_last > 0.0 && ctx->pt.slo_active) ? ctx->sm_slo : nullptr;
+    const TenderPoint p = tender_point(ctx);           // (the low-order log-prices gn_newton_kernel evaluated these pools with)
     return read_back(ctx, "get_tradesN", (size_t)k * b.m, delta, lambda, [&](double *dd, double *dl) {
-        with_int<3, 8>(k, [&](auto K) { hipLaunchKernelGGL(tradesn_kernel<K>, grid, blk, 0, ctx->stream, b, nu, slo, dd, dl); });
+        with_int<3, 8>(k, [&](auto K) { hipLaunchKernelGGL(tradesn_kernel<K>, grid, blk, 0, ctx->stream, b, p.nu, p.slo, dd, dl); });
     });
 }
 
 // ---- resident reserves back in upload order (apply.hpp: plain gathers through perm) ---------------------------------------------------
 namespace {
-// `cols` columns of `m` doubles each gathered by launch(scratch) into the read-back scratch, then host[q] <- column q (NULL: skipped)
-extern "C++" template <class Launch> int reserves_back(cfmm_ctx *ctx, const char *who, size_t m, int cols, double *const *host, Launch &&launch)
+// `total` doubles gathered by launch(scratch) into the read-back scratch, then every piece's host <- scratch[off .. off + count) (NULL: skipped)
+struct BackPiece { double *host; size_t off, count; };
+extern "C++" template <class Launch> int reserves_back(cfmm_ctx *ctx, const char *who, size_t total, std::initializer_list<BackPiece> pieces, Launch &&launch)
 {
     double *d0 = nullptr, *d1 = nullptr;
-    { int rc = trade_scratch(ctx, ((size_t)cols * m + 1) / 2, &d0, &d1); if (rc) return rc; }
+    { int rc = trade_scratch(ctx, (total + 1) / 2, &d0, &d1); if (rc) return rc; }
     launch(d0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ctx, CFMM_E_HIP, "%s -> %s", who, hipGetErrorString(e));
-    for (int q = 0; q < cols; ++q)
-        if (host[q]) { int rc = download_staged(ctx, host[q], d0 + (size_t)q * m, m * sizeof(double)); if (rc) return rc; }
+    for (const BackPiece &pc : pieces)
+        if (pc.host) { int rc = download_staged(ctx, pc.host, d0 + pc.off, pc.count * sizeof(double)); if (rc) return rc; }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CFMM_OK;
 }
@@ -4613,9 +4612,8 @@ int cfmm_get_reserves2(cfmm_ctx *ctx, int kind, double *Ra, double *Rb, double *
     const Bucket2 b = ctx->pools->r2[kind].b;
     if (b.m == 0) return CFMM_OK;
     if (!b.param) param = nullptr;
-    double *const host[3] = {Ra, Rb, param};
     const size_t m = (size_t)b.m;
-    return reserves_back(ctx, "get_reserves2", m, 3, host, [&](double *d) {
+    return reserves_back(ctx, "get_reserves2", 3 * m, {{Ra, 0, m}, {Rb, m, m}, {param, 2 * m, m}}, [&](double *d) {
         hipLaunchKernelGGL(reserves2_kernel, dim3(apply_grid(b.m)), dim3(AP_THREADS), 0, ctx->stream, b, d, d + m, param ? d + 2 * m : nullptr);
     });
 }
@@ -4626,8 +4624,8 @@ int cfmm_get_reservesN(cfmm_ctx *ctx, int k, double *R)
     PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
     const BucketN b = ctx->pools->rn[k].b;
     if (b.m == 0) return CFMM_OK;
-    double *const host[1] = {R};
-    return reserves_back(ctx, "get_reservesN", (size_t)k * b.m, 1, host, [&](double *d) {
+    const size_t km = (size_t)k * b.m;
+    return reserves_back(ctx, "get_reservesN", km, {{R, 0, km}}, [&](double *d) {
         hipLaunchKernelGGL(reservesK_kernel, dim3(apply_grid(b.m)), dim3(AP_THREADS), 0, ctx->stream, b.R, b.perm, b.m, k, d, (const double *)nullptr, (double *)nullptr);
     });
 }
@@ -4639,15 +4637,10 @@ int cfmm_get_reservesG(cfmm_ctx *ctx, int kind, int k, double *R, double *param)
     const BucketG b = ctx->pools->rg[kind][k].b;
     if (b.m == 0) return CFMM_OK;
     if (!b.param) param = nullptr;
-    const size_t m = (size_t)b.m;
-    double *d0 = nullptr, *d1 = nullptr;
-    { int rc = trade_scratch(ctx, ((size_t)(k + 1) * m + 1) / 2, &d0, &d1); if (rc) return rc; }
-    hipLaunchKernelGGL(reservesK_kernel, dim3(apply_grid(b.m)), dim3(AP_THREADS), 0, ctx->stream, b.R, (const int *)nullptr, b.m, k, d0, b.param, param ? d0 + (size_t)k * m : nullptr);
-    HIP_TRY(ctx, hipGetLastError());
-    if (R) { int rc = download_staged(ctx, R, d0, (size_t)k * m * sizeof(double)); if (rc) return rc; }
-    if (param) { int rc = download_staged(ctx, param, d0 + (size_t)k * m, m * sizeof(double)); if (rc) return rc; }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CFMM_OK;
+    const size_t m = (size_t)b.m, km = (size_t)k * m;
+    return reserves_back(ctx, "get_reservesG", km + m, {{R, 0, km}, {param, km, m}}, [&](double *d) {
+        hipLaunchKernelGGL(reservesK_kernel, dim3(apply_grid(b.m)), dim3(AP_THREADS), 0, ctx->stream, b.R, (const int *)nullptr, b.m, k, d, b.param, param ? d + km : nullptr);
+    });
 }
 
 // ---- the solve's trades applied to the resident pools (apply.hpp) -----------------------------------------------------------------------
@@ -4656,43 +4649,123 @@ int cfmm_get_reservesG(cfmm_ctx *ctx, int kind, int k, double *R, double *param)
 // there and nothing has changed.  The second writes.  Sharing and ordering are the update's: the store's lock, the wait on every sharer's
 // enqueued work, the refusal while a sharer reads, one bump of the generation.
 namespace {
-inline int apply_rec2(int kind) { return kind; }
-inline int apply_recN(int k) { return CFMM_POOL_KINDS2 + k; }
-inline int apply_recG(int kind, int k) { return CFMM_POOL_KINDS2 + (CFMM_MAX_POOL_SIZE + 1) * (1 + kind) + k; }
-
-extern "C++" template <bool WRITE> int apply_pass(cfmm_ctx *ctx, int aside, const double *ovr)
+// room for `len` doubles in the context's device copy of host-held tenders (grow-only; the stream may still read the one it replaces)
+int tender_room(cfmm_ctx *ctx, size_t len)
 {
-    PoolStore &ps = *ctx->pools;
-    const double *nu = ctx->nu_acc;
-    const double mu = ctx->pt.mu_last > 0.0 ? ctx->pt.mu_last : 0.0;
-    const double *slo = (mu > 0.0 && ctx->pt.slo_active) ? ctx->sm_slo : nullptr;
+    if (len <= ctx->tender_cap) return CFMM_OK;
+    if (ctx->tender_dev) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->tender_dev); ctx->tender_dev = nullptr; ctx->tender_cap = 0; }
+    HIP_TRY(ctx, hipMalloc((void **)&ctx->tender_dev, len * sizeof(double)));
+    ctx->tender_cap = len;
+    return CFMM_OK;
+}
+// a pass's launches between the events ev_t0 and ev_t1 (the measurement hooks' `timed`), then what the call still enqueues behind them;
+// ONE synchronisation, and the launches' seconds
+extern "C++" template <class Pass, class Behind> int timed_pass(cfmm_ctx *ctx, bool timed, double *sec, Pass &&pass, Behind &&behind)
+{
+    float ms = 0.f;
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
+    { int rc = pass(); if (rc) return rc; }
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
+    { int rc = behind(); if (rc) return rc; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (timed) { HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1)); *sec = ms * 1e-3; }
+    return CFMM_OK;
+}
+
+struct ApplyRun {
+    cfmm_ctx *ctx;
+    PoolStore &ps;
+    int aside;
+    route::Counts counts;
+    TradeLayout tl;
+    const double *ovr;                 // the kink loop's tenders on the device (NULL: every pool's own)
+    route::ApplyFold fold;             // the checking pass's records, folded
+};
+
+// what the context must hold: prices, and no ties of the caller's
+int apply_refusals(cfmm_ctx *ctx)
+{
+    if (!ctx->pt.have_nu) return fail(ctx, CFMM_E_STATE, "apply_trades: no prices yet (cfmm_set_nu or a solve first)");
+    bool tied = ctx->flags2 != nullptr || ctx->ng != ctx->n;
+    for (int *q : ctx->flagsG) tied |= q != nullptr;
+    if (tied) return fail(ctx, CFMM_E_UNSUPPORTED, "apply_trades: tie flags or price ties are set by the caller, who then holds the tied pools' fills");
+    return CFMM_OK;
+}
+
+// the kink loop's own tenders (two-asset buckets, partial fills included) travel to the device once, both passes read them there; then
+// the passes are ordered behind the work every sharer of the store has enqueued
+int apply_stage(ApplyRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    if (ctx->pt.tr_ovr_valid) {
+        const size_t len = R.tl.two_asset();
+        if (ctx->pt.tr_ovr.size() < len) return fail(ctx, CFMM_E_STATE, "apply_trades: the kink loop's tenders do not match the resident buckets");
+        { int rc = tender_room(ctx, len); if (rc) return rc; }
+        if (len) HIP_TRY(ctx, hipMemcpyAsync(ctx->tender_dev, ctx->pt.tr_ovr.data(), len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        R.ovr = ctx->tender_dev;
+    }
+    for (cfmm_ctx *s : R.ps.sharers) {
+        if (s == ctx) continue;
+        HIP_TRY(ctx, hipEventRecord(s->ev_pool, s->stream));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s->ev_pool, 0));
+    }
+    return CFMM_OK;
+}
+
+extern "C++" template <bool WRITE> int apply_pass(ApplyRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    const TenderPoint p = tender_point(ctx);
+    const int aside = R.aside;
     const dim3 blk(AP_THREADS);
-    size_t off = 0;
-    for (int kind = 0; kind < CFMM_POOL_KINDS2; ++kind) {
-        const Bucket2 b = ps.r2[kind].b;                // (no tie flags: the call refuses while any are set)
-        if (b.m == 0) continue;
-        const double *ov = ovr ? ovr + off : nullptr;
-        off += 4 * (size_t)b.m;
-        ApplyRec *rec = ctx->apply_dev + apply_rec2(kind);
-        with_int<0, 4>(kind, [&](auto K) { hipLaunchKernelGGL((apply2_kernel<K, WRITE>), dim3(apply_grid(b.m)), blk, 0, ctx->stream, b, nu, slo, mu, aside, ov, rec); });
-    }
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) {
-        const BucketN b = ps.rn[k].b;
-        if (b.m == 0) continue;
-        ApplyRec *rec = ctx->apply_dev + apply_recN(k);
-        with_int<3, 8>(k, [&](auto K) { hipLaunchKernelGGL((applyN_kernel<K, WRITE>), dim3(apply_grid(b.m)), blk, 0, ctx->stream, b, nu, slo, aside, rec); });
-    }
-    for (int kind = 0; kind < CFMM_POOLK_KINDS; ++kind)
-        for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) {
-            const BucketG b = ps.rg[kind][k].b;
-            if (b.m == 0) continue;
-            ApplyRec *rec = ctx->apply_dev + apply_recG(kind, k);
-            with_int<CFMM_POOLK_STABLE, CFMM_POOLK_SUM>(kind, [&](auto KIND) {
-                with_int<2, 8>(k, [&](auto K) { hipLaunchKernelGGL((applyG_kernel<KIND, K, WRITE>), dim3(apply_grid(b.m)), blk, 0, ctx->stream, b, nu, slo, mu, aside, rec); });
-            });
-        }
+    each_bucket(R.ps, [&](auto &r, int q, auto FAMILY, auto KIND, auto K) {
+        const auto b = r.b;                             // (no tie flags: the call refuses while any are set)
+        const dim3 grid(apply_grid(b.m));
+        ApplyRec *rec = ctx->apply_dev + q;
+        if constexpr (FAMILY == 0) {
+            const double *ov = R.ovr ? R.ovr + R.tl.off2[KIND] : nullptr;
+            hipLaunchKernelGGL((apply2_kernel<KIND, WRITE>), grid, blk, 0, ctx->stream, b, p.nu, p.slo, p.mu, aside, ov, rec);
+        } else if constexpr (FAMILY == 1) hipLaunchKernelGGL((applyN_kernel<K, WRITE>), grid, blk, 0, ctx->stream, b, p.nu, p.slo, aside, rec);
+        else hipLaunchKernelGGL((applyG_kernel<KIND, K, WRITE>), grid, blk, 0, ctx->stream, b, p.nu, p.slo, p.mu, aside, rec);
+    });
     HIP_TRY(ctx, hipGetLastError());
     return CFMM_OK;
+}
+
+// pass 1: nothing is written.  ONE copy and ONE synchronisation; the records folded, and the refusal if any pool would not stay sound
+int apply_check_pass(ApplyRun &R, cfmm_apply_info *info)
+{
+    cfmm_ctx *ctx = R.ctx;
+    ApplyRec *res = ctx->apply_host + route::SLOTS;     // (pinned)
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->apply_dev, ctx->apply_host, route::SLOTS * sizeof(ApplyRec), hipMemcpyHostToDevice, ctx->stream));
+    auto back = [&] { HIP_TRY(ctx, hipMemcpyAsync(res, ctx->apply_dev, route::SLOTS * sizeof(ApplyRec), hipMemcpyDeviceToHost, ctx->stream)); return (int)CFMM_OK; };
+    { int rc = timed_pass(ctx, ctx->apply_timed, &ctx->apply_sec[0], [&] { return apply_pass<false>(R); }, back); if (rc) return rc; }
+    if (ctx->apply_timed) ctx->apply_sec[1] = 0.0;
+    const route::ApplyFold &f = R.fold = route::fold_apply(res, R.counts);
+    if (info) { info->pools_moved = f.moved; info->pools_refused = f.refused; }
+    if (!f.refused) return CFMM_OK;
+    const route::SlotName s = route::slot_name(f.first);
+    if (info) { info->first_family = s.family; info->first_kind = s.kind; info->first_k = s.k; info->first_pos = f.first_pos; }
+    return fail(ctx, CFMM_E_UNSUPPORTED, "apply_trades: %lld pools would be left with a reserve that is not positive and finite (first: family %d, kind %d, %d assets, pool %lld); nothing was changed",
+                (long long)f.refused, s.family, s.kind, s.k, (long long)f.first_pos);
+}
+
+// pass 2: the writes; the store's host copy of the constant-sum bucket follows them
+int apply_write_pass(ApplyRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    PoolStore &ps = R.ps;
+    return timed_pass(ctx, ctx->apply_timed, &ctx->apply_sec[1], [&] { return apply_pass<true>(R); }, [&] {
+        const Bucket2 bs = ps.r2[CFMM_POOL_SUM2].b;
+        if (bs.m == 0 || (int64_t)ps.hs_Ra.size() != bs.m) return (int)CFMM_OK;
+        double *d0 = nullptr, *d1 = nullptr;
+        { int rc = trade_scratch(ctx, (size_t)bs.m, &d0, &d1); if (rc) return rc; }
+        hipLaunchKernelGGL(reserves2_kernel, dim3(apply_grid(bs.m)), dim3(AP_THREADS), 0, ctx->stream, bs, d0, d1, (double *)nullptr);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(ps.hs_Ra.data(), d0, (size_t)bs.m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ps.hs_Rb.data(), d1, (size_t)bs.m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        return (int)CFMM_OK;
+    });
 }
 }  // namespace
 
@@ -4705,84 +4778,16 @@ int cfmm_apply_trades(cfmm_ctx *ctx, int fee_mode, cfmm_apply_info *info)
     if (sharded(ctx)) return fail(ctx, CFMM_E_UNSUPPORTED, "%s: pool-sharded contexts are not served", who);
     PoolEntry entry(ctx, false); HIP_TRY(ctx, entry.device);
     PoolStore &ps = entry.ps;
-    if (!ctx->pt.have_nu) return fail(ctx, CFMM_E_STATE, "%s: no prices yet (cfmm_set_nu or a solve first)", who);
-    bool tied = ctx->flags2 != nullptr || ctx->ng != ctx->n;
-    for (int *q : ctx->flagsG) tied |= q != nullptr;
-    if (tied) return fail(ctx, CFMM_E_UNSUPPORTED, "%s: tie flags or price ties are set by the caller, who then holds the tied pools' fills", who);
+    { int rc = apply_refusals(ctx); if (rc) return rc; }
     std::unique_lock<std::mutex> lock(ps.mu);
     if (ps.readers > 0) return fail(ctx, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve, evaluation or read-back", who);
-    // the kink loop's own tenders (two-asset buckets, partial fills included) travel to the device once; both passes read them there
-    const double *ovr = nullptr;
-    if (ctx->pt.tr_ovr_valid) {
-        const size_t len = trade_layout(ps).two_asset();
-        if (ctx->pt.tr_ovr.size() < len) return fail(ctx, CFMM_E_STATE, "%s: the kink loop's tenders do not match the resident buckets", who);
-        if (len > ctx->apply_ovr_cap) {
-            if (ctx->apply_ovr) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->apply_ovr); ctx->apply_ovr = nullptr; ctx->apply_ovr_cap = 0; }
-            HIP_TRY(ctx, hipMalloc((void **)&ctx->apply_ovr, len * sizeof(double)));
-            ctx->apply_ovr_cap = len;
-        }
-        if (len) HIP_TRY(ctx, hipMemcpyAsync(ctx->apply_ovr, ctx->pt.tr_ovr.data(), len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        ovr = ctx->apply_ovr;
-    }
-    for (cfmm_ctx *s : ps.sharers) {
-        if (s == ctx) continue;
-        HIP_TRY(ctx, hipEventRecord(s->ev_pool, s->stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s->ev_pool, 0));
-    }
-    const int aside = fee_mode == CFMM_FEES_ASIDE ? 1 : 0;
-    const bool timed = ctx->apply_timed;
-    float ms = 0.f;
-    ApplyRec *res = ctx->apply_host + APPLY_RECS;
-    // pass 1: nothing is written
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->apply_dev, ctx->apply_host, APPLY_RECS * sizeof(ApplyRec), hipMemcpyHostToDevice, ctx->stream));
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
-    { int rc = apply_pass<false>(ctx, aside, ovr); if (rc) return rc; }
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(res, ctx->apply_dev, APPLY_RECS * sizeof(ApplyRec), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (timed) { HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1)); ctx->apply_sec[0] = ms * 1e-3; ctx->apply_sec[1] = 0.0; }
-    int64_t moved = 0, refused = 0;
-    int first = -1;
-    for (int q = 0; q < APPLY_RECS; ++q) {
-        moved += (int64_t)res[q].moved; refused += (int64_t)res[q].refused;
-        if (first < 0 && res[q].refused) first = q;
-    }
-    if (info) { info->pools_moved = moved; info->pools_refused = refused; }
-    if (refused) {
-        int fam = 0, kind = first, k = 2;
-        if (first >= apply_recG(0, 0)) { fam = 2; kind = (first - apply_recG(0, 0)) / (CFMM_MAX_POOL_SIZE + 1); k = (first - apply_recG(0, 0)) % (CFMM_MAX_POOL_SIZE + 1); }
-        else if (first >= apply_recN(0)) { fam = 1; kind = 0; k = first - apply_recN(0); }
-        if (info) { info->first_family = fam; info->first_kind = kind; info->first_k = k; info->first_pos = (int64_t)res[first].first; }
-        return fail(ctx, CFMM_E_UNSUPPORTED, "%s: %lld pools would be left with a reserve that is not positive and finite (first: family %d, kind %d, %d assets, pool %lld); nothing was changed",
-                    who, (long long)refused, fam, kind, k, (long long)res[first].first);
-    }
-    // pass 2: the writes
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
-    { int rc = apply_pass<true>(ctx, aside, ovr); if (rc) return rc; }
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
-    const Bucket2 bs = ps.r2[CFMM_POOL_SUM2].b;
-    const bool host_sum = bs.m > 0 && (int64_t)ps.hs_Ra.size() == bs.m;           // the store's host copy of the constant-sum bucket follows
-    if (host_sum) {
-        double *d0 = nullptr, *d1 = nullptr;
-        { int rc = trade_scratch(ctx, (size_t)bs.m, &d0, &d1); if (rc) return rc; }
-        hipLaunchKernelGGL(reserves2_kernel, dim3(apply_grid(bs.m)), dim3(AP_THREADS), 0, ctx->stream, bs, d0, d1, (double *)nullptr);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(ps.hs_Ra.data(), d0, (size_t)bs.m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ps.hs_Rb.data(), d1, (size_t)bs.m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (timed) { HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1)); ctx->apply_sec[1] = ms * 1e-3; }
-    // every bucket's largest reserve, exact (pass 1 visited every pool), as a fresh upload would record it
-    double mx_all = 0.0;
-    auto record = [&](auto &r, int q) {
-        if (r.b.m == 0) return;
-        double d; std::memcpy(&d, &res[q].maxbits, sizeof d);
-        r.mxr = d; mx_all = std::max(mx_all, d);
-    };
-    for (int kind = 0; kind < CFMM_POOL_KINDS2; ++kind) record(ps.r2[kind], apply_rec2(kind));
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) record(ps.rn[k], apply_recN(k));
-    for (int kind = 0; kind < CFMM_POOLK_KINDS; ++kind) for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) record(ps.rg[kind][k], apply_recG(kind, k));
-    if (info) info->max_reserve = mx_all;
+    const route::Counts counts = bucket_counts(ps);
+    ApplyRun R{ctx, ps, fee_mode == CFMM_FEES_ASIDE ? 1 : 0, counts, route::trade_layout(counts), nullptr, {}};
+    { int rc = apply_stage(R); if (rc) return rc; }
+    { int rc = apply_check_pass(R, info); if (rc) return rc; }
+    { int rc = apply_write_pass(R); if (rc) return rc; }
+    each_bucket(ps, [&](auto &r, int q, auto, auto, auto) { r.mxr = R.fold.mx[q]; });      // every bucket's largest reserve, exact (pass 1 visited every pool), as a fresh upload would record it
+    if (info) info->max_reserve = R.fold.mx_all;
     ps.gen.fetch_add(1, std::memory_order_acq_rel);
     lock.unlock();
     pools_seen(ctx);           // this context too drops what it derived from the old reserves (solution, kink tenders, barrier warm start, captured launches); prices, utility and ties stay
@@ -4802,19 +4807,133 @@ int cfmm_apply_timers(cfmm_ctx *ctx, int on, double *out2)
 // slots of the apply records), ONE copy (records | limbs, contiguous) and ONE synchronisation.  Nothing of the context or the store is
 // written: the scratch below is the audit's own.
 namespace {
-struct AuditSpan { size_t recs, limbs, parts, total; };
-AuditSpan audit_span(int n)
-{
-    AuditSpan s;
-    s.recs = 0; s.limbs = APPLY_RECS * sizeof(AuditRec);
-    s.parts = (s.limbs + 3 * (size_t)n * sizeof(unsigned long long) + 255) & ~(size_t)255;
-    s.total = s.parts + (size_t)APPLY_RECS * AU_GRID_MAX * sizeof(AuditRec);
-    return s;
-}
 unsigned audit_grid(const cfmm_ctx *ctx, int64_t m)
 {
     const int64_t chunks = (m + AU_THREADS - 1) / AU_THREADS;
     return (unsigned)std::min<int64_t>(chunks, ctx->audit_grid);
+}
+
+struct AuditRun {
+    cfmm_ctx *ctx;
+    PoolStore &ps;
+    double tol;
+    route::Counts counts;
+    TradeLayout tl;
+    route::AuditSpan sp;
+    bool kink;                         // the library's kink loop left the two-asset tenders on the host (as cfmm_get_trades2 returns them)
+    route::AuditStage st;
+    double sc;                         // 2^F (det_scales)
+};
+
+// a report no audit has filled in: no worst pool, minima over nothing, no value
+void audit_blank(cfmm_audit *out)
+{
+    std::memset(out, 0, sizeof *out);
+    out->worst_family = out->worst_kind = out->worst_k = -1; out->worst_pos = -1;
+    out->min_slack = out->min_tender = out->min_leg = std::numeric_limits<double>::infinity();
+    out->value = out->infeas = std::numeric_limits<double>::quiet_NaN();
+}
+
+// the audit's own scratch, made at the first audit
+int audit_reserve(AuditRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    if (ctx->audit_dev) return CFMM_OK;
+    HIP_TRY(ctx, hipMalloc((void **)&ctx->audit_dev, R.sp.total));
+    hipError_t e = hipHostMalloc((void **)&ctx->audit_host, R.sp.parts);
+    if (e != hipSuccess) { (void)hipFree(ctx->audit_dev); ctx->audit_dev = nullptr; ctx->audit_host = nullptr; return fail(ctx, CFMM_E_HIP, "audit_trades: pinned records -> %s", hipGetErrorString(e)); }
+    return CFMM_OK;
+}
+
+// tenders held on the host travel to the device once (route_rules.hpp: audit_stage): the library's kink loop's, then the caller's own
+// for the constant-sum buckets it names
+int audit_stage_tenders(AuditRun &R, const cfmm_audit_tenders *own)
+{
+    cfmm_ctx *ctx = R.ctx;
+    if (R.kink && ctx->pt.tr_ovr.size() < R.tl.two_asset()) return fail(ctx, CFMM_E_STATE, "audit_trades: the kink loop's tenders do not match the resident buckets");
+    const route::AuditStage &st = R.st = route::audit_stage(R.counts, R.kink, own);
+    if (st.half == route::slot2(CFMM_POOL_SUM2)) return fail(ctx, CFMM_E_ARG, "audit_trades: own names one array of the constant-sum bucket without the other");
+    if (st.half >= 0) return fail(ctx, CFMM_E_ARG, "audit_trades: own names one array of the %d-asset constant-sum bucket without the other", route::slot_name(st.half).k);
+    { int rc = tender_room(ctx, st.len); if (rc) return rc; }
+    auto send = [&](size_t off, const double *src, size_t cnt) { return cnt ? hipMemcpyAsync(ctx->tender_dev + off, src, cnt * sizeof(double), hipMemcpyHostToDevice, ctx->stream) : hipSuccess; };
+    if (R.kink) HIP_TRY(ctx, send(0, ctx->pt.tr_ovr.data(), R.tl.two_asset()));
+    const size_t m2 = (size_t)R.counts.m[route::slot2(CFMM_POOL_SUM2)];
+    if (st.own2) { HIP_TRY(ctx, send(st.off_own2, own->sum2_delta, 2 * m2)); HIP_TRY(ctx, send(st.off_own2 + 2 * m2, own->sum2_lambda, 2 * m2)); }
+    for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k)
+        if (st.ownk[k]) {
+            const size_t cnt = (size_t)k * R.counts.m[route::slotG(CFMM_POOLK_SUM, k)];
+            HIP_TRY(ctx, send(st.off_ownk[k], own->sumk_delta[k], cnt)); HIP_TRY(ctx, send(st.off_ownk[k] + cnt, own->sumk_lambda[k], cnt));
+        }
+    return CFMM_OK;
+}
+
+// the pass: every bucket's launch, ONE copy (records | limbs, contiguous) and ONE synchronisation
+int audit_launches(AuditRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    const route::AuditStage &st = R.st;
+    AuditArgs a;
+    a.n = ctx->n; a.sc = R.sc; a.tol = R.tol;
+    a.limbs = (unsigned long long *)(ctx->audit_dev + R.sp.limbs);
+    AuditRec *recs = (AuditRec *)(ctx->audit_dev + R.sp.recs), *parts = (AuditRec *)(ctx->audit_dev + R.sp.parts);
+    const size_t lds = 3 * (size_t)ctx->n * sizeof(unsigned long long);
+    const TenderPoint p = tender_point(ctx);
+    const double *dev = ctx->tender_dev;
+    const dim3 blk(AU_THREADS);
+    ctx->audit_reordered = 0;
+    each_bucket(R.ps, [&](auto &r, int q, auto FAMILY, auto KIND, auto K) {
+        auto b = r.b;
+        const dim3 grid(audit_grid(ctx, b.m));
+        a.rec = recs + q; a.part = parts + (size_t)q * AU_GRID_MAX;
+        if constexpr (FAMILY == 0) {
+            if (KIND == CFMM_POOL_SUM2) b.flags = ctx->flags2;                  // (flagged pools hand out zeros, as the read-back's do)
+            const double *ov = (KIND == CFMM_POOL_SUM2 && st.own2) ? dev + st.off_own2 : (R.kink ? dev + R.tl.off2[KIND] : nullptr);
+            ctx->audit_reordered += b.perm != nullptr;
+            hipLaunchKernelGGL(audit2_kernel<KIND>, grid, blk, lds, ctx->stream, b, p.nu, p.slo, p.mu, ov, a);
+        } else if constexpr (FAMILY == 1) {
+            ctx->audit_reordered += b.perm != nullptr;
+            hipLaunchKernelGGL(auditN_kernel<K>, grid, blk, lds, ctx->stream, b, p.nu, p.slo, a);
+        } else {
+            const int *fl = KIND == CFMM_POOLK_SUM ? ctx->flagsG[K] : nullptr;      // (the read-back's per-leg tie flags)
+            const double *ov = (KIND == CFMM_POOLK_SUM && st.ownk[K]) ? dev + st.off_ownk[K] : nullptr;
+            hipLaunchKernelGGL((auditG_kernel<KIND, K>), grid, blk, lds, ctx->stream, b, fl, p.nu, p.slo, p.mu, ov, a);
+        }
+    });
+    HIP_TRY(ctx, hipGetLastError());
+    return CFMM_OK;
+}
+int audit_pass(AuditRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    double scd;
+    det_scales(ctx, R.sc, scd);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->audit_dev, 0, R.sp.parts, ctx->stream));
+    return timed_pass(ctx, ctx->audit_timed, &ctx->audit_sec, [&] { return audit_launches(R); }, [&] {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->audit_host, ctx->audit_dev, R.sp.parts, hipMemcpyDeviceToHost, ctx->stream));
+        return (int)CFMM_OK;
+    });
+}
+
+// the report: the records folded, the limbs and their psi, its value and infeasibility under the utility last set
+void audit_report(AuditRun &R, cfmm_audit *out, double *psi, uint64_t *limbs)
+{
+    cfmm_ctx *ctx = R.ctx;
+    const int n = ctx->n;
+    const AuditRec *res = (const AuditRec *)(ctx->audit_host + R.sp.recs);
+    const unsigned long long *hl = (const unsigned long long *)(ctx->audit_host + R.sp.limbs);
+    const route::AuditFold f = route::fold_audit(res, R.counts);
+    const route::SlotName worst = route::slot_name(f.worst);
+    out->fixed_exponent = route::fixed_exponent(R.sc);
+    out->pools = f.pools; out->pools_trading = f.trading; out->pools_violating = f.violating; out->legs_out_of_range = f.oor;
+    out->worst_family = worst.family; out->worst_kind = worst.kind; out->worst_k = worst.k; out->worst_pos = f.worst_pos;
+    out->min_slack = f.min_slack; out->min_tender = f.min_tender; out->min_leg = f.min_leg;
+    if (limbs) std::memcpy(limbs, hl, 3 * (size_t)n * sizeof(uint64_t));
+    std::vector<double> hp((size_t)n);
+    route::psi_from_limbs(hl, n, out->fixed_exponent, hp.data());
+    if (psi) std::memcpy(psi, hp.data(), (size_t)n * sizeof(double));
+    if (!ctx->have_utility) return;
+    const route::PsiWorth w = route::psi_worth(hp.data(), n, ctx->hc.data(), ctx->hh.data(), ctx->hctype.data(), ctx->max_reserve);
+    out->value = w.value; out->infeas = w.infeas;
 }
 }  // namespace
 
@@ -4823,153 +4942,17 @@ int cfmm_audit_trades(cfmm_ctx *ctx, const cfmm_audit_tenders *own, double tol_p
     const char *who = "audit_trades";
     if (!ctx) return CFMM_E_ARG;
     if (!out) return fail(ctx, CFMM_E_ARG, "%s: out is NULL", who);
-    std::memset(out, 0, sizeof *out);
-    out->worst_family = out->worst_kind = out->worst_k = -1; out->worst_pos = -1;
-    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
-    out->min_slack = out->min_tender = out->min_leg = inf; out->value = out->infeas = nan;
+    audit_blank(out);
     if (sharded(ctx)) return fail(ctx, CFMM_E_UNSUPPORTED, "%s: pool-sharded contexts are not served (audit the shards' tenders on the host)", who);
-    const int n = ctx->n;
-    if (n > AU_MAX_TOKENS) return fail(ctx, CFMM_E_LIMIT, "%s: %d tokens exceed the workgroup's tile of 3 n 64-bit limbs (n <= %d)", who, n, AU_MAX_TOKENS);
+    if (ctx->n > AU_MAX_TOKENS) return fail(ctx, CFMM_E_LIMIT, "%s: %d tokens exceed the workgroup's tile of 3 n 64-bit limbs (n <= %d)", who, ctx->n, AU_MAX_TOKENS);
     PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
-    PoolStore &ps = entry.ps;
     if (!ctx->pt.have_nu) return fail(ctx, CFMM_E_STATE, "%s: no prices yet (cfmm_set_nu or a solve first)", who);
-    if (!(tol_pool > 0.0)) tol_pool = 1e-9;
-    const AuditSpan sp = audit_span(n);
-    if (!ctx->audit_dev) {
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->audit_dev, sp.total));
-        hipError_t e = hipHostMalloc((void **)&ctx->audit_host, sp.parts);
-        if (e != hipSuccess) { (void)hipFree(ctx->audit_dev); ctx->audit_dev = nullptr; ctx->audit_host = nullptr; return fail(ctx, CFMM_E_HIP, "%s: pinned records -> %s", who, hipGetErrorString(e)); }
-    }
-    // tenders held on the host travel to the device once: the library's kink loop's (two-asset buckets, as cfmm_get_trades2 returns them),
-    // then the caller's own for the constant-sum buckets it names
-    const TradeLayout tl = trade_layout(ps);
-    const bool kink = ctx->pt.tr_ovr_valid;
-    if (kink && ctx->pt.tr_ovr.size() < tl.two_asset()) return fail(ctx, CFMM_E_STATE, "%s: the kink loop's tenders do not match the resident buckets", who);
-    const int64_t m_sum2 = ps.r2[CFMM_POOL_SUM2].b.m;
-    const bool own2 = own && m_sum2 > 0 && (own->sum2_delta || own->sum2_lambda);
-    if (own2 && !(own->sum2_delta && own->sum2_lambda)) return fail(ctx, CFMM_E_ARG, "%s: own names one array of the constant-sum bucket without the other", who);
-    size_t len = kink ? tl.two_asset() : 0, off_own2 = 0, off_ownk[CFMM_MAX_POOL_SIZE + 1] = {};
-    bool ownk[CFMM_MAX_POOL_SIZE + 1] = {};
-    if (own2) { off_own2 = len; len += 4 * (size_t)m_sum2; }
-    for (int k = 2; own && k <= CFMM_MAX_POOL_SIZE; ++k) {
-        const int64_t m = ps.rg[CFMM_POOLK_SUM][k].b.m;
-        if (m == 0 || !(own->sumk_delta[k] || own->sumk_lambda[k])) continue;
-        if (!(own->sumk_delta[k] && own->sumk_lambda[k])) return fail(ctx, CFMM_E_ARG, "%s: own names one array of the %d-asset constant-sum bucket without the other", who, k);
-        ownk[k] = true; off_ownk[k] = len; len += 2 * (size_t)k * m;
-    }
-    if (len > ctx->audit_ovr_cap) {
-        if (ctx->audit_ovr) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->audit_ovr); ctx->audit_ovr = nullptr; ctx->audit_ovr_cap = 0; }
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->audit_ovr, len * sizeof(double)));
-        ctx->audit_ovr_cap = len;
-    }
-    auto send = [&](size_t off, const double *src, size_t cnt) { return cnt ? hipMemcpyAsync(ctx->audit_ovr + off, src, cnt * sizeof(double), hipMemcpyHostToDevice, ctx->stream) : hipSuccess; };
-    if (kink) HIP_TRY(ctx, send(0, ctx->pt.tr_ovr.data(), tl.two_asset()));
-    if (own2) { HIP_TRY(ctx, send(off_own2, own->sum2_delta, 2 * (size_t)m_sum2)); HIP_TRY(ctx, send(off_own2 + 2 * (size_t)m_sum2, own->sum2_lambda, 2 * (size_t)m_sum2)); }
-    for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k)
-        if (ownk[k]) {
-            const size_t cnt = (size_t)k * ps.rg[CFMM_POOLK_SUM][k].b.m;
-            HIP_TRY(ctx, send(off_ownk[k], own->sumk_delta[k], cnt)); HIP_TRY(ctx, send(off_ownk[k] + cnt, own->sumk_lambda[k], cnt));
-        }
-    // the pass
-    double sc, scd;
-    det_scales(ctx, sc, scd);
-    AuditArgs a;
-    a.n = n; a.sc = sc; a.tol = tol_pool;
-    a.limbs = (unsigned long long *)(ctx->audit_dev + sp.limbs);
-    AuditRec *recs = (AuditRec *)(ctx->audit_dev + sp.recs), *parts = (AuditRec *)(ctx->audit_dev + sp.parts);
-    const size_t lds = 3 * (size_t)n * sizeof(unsigned long long);
-    const double *nu = ctx->nu_acc;
-    const double mu = ctx->pt.mu_last > 0.0 ? ctx->pt.mu_last : 0.0;
-    const double *slo = (mu > 0.0 && ctx->pt.slo_active) ? ctx->sm_slo : nullptr;
-    const dim3 blk(AU_THREADS);
-    const bool timed = ctx->audit_timed;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->audit_dev, 0, sp.parts, ctx->stream));
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
-    auto slot = [&](int q) { a.rec = recs + q; a.part = parts + (size_t)q * AU_GRID_MAX; };
-    ctx->audit_reordered = 0;
-    for (int kind = 0; kind < CFMM_POOL_KINDS2; ++kind) {
-        Bucket2 b = ps.r2[kind].b;
-        if (b.m == 0) continue;
-        if (kind == CFMM_POOL_SUM2) b.flags = ctx->flags2;                  // (as cfmm_get_trades2: flagged pools hand out zeros)
-        const double *ov = (kind == CFMM_POOL_SUM2 && own2) ? ctx->audit_ovr + off_own2 : (kink ? ctx->audit_ovr + tl.off2[kind] : nullptr);
-        slot(apply_rec2(kind));
-        ctx->audit_reordered += b.perm != nullptr;
-        with_int<0, 4>(kind, [&](auto K) { hipLaunchKernelGGL(audit2_kernel<K>, dim3(audit_grid(ctx, b.m)), blk, lds, ctx->stream, b, nu, slo, mu, ov, a); });
-    }
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) {
-        const BucketN b = ps.rn[k].b;
-        if (b.m == 0) continue;
-        slot(apply_recN(k));
-        ctx->audit_reordered += b.perm != nullptr;
-        with_int<3, 8>(k, [&](auto K) { hipLaunchKernelGGL(auditN_kernel<K>, dim3(audit_grid(ctx, b.m)), blk, lds, ctx->stream, b, nu, slo, a); });
-    }
-    for (int kind = 0; kind < CFMM_POOLK_KINDS; ++kind)
-        for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) {
-            const BucketG b = ps.rg[kind][k].b;
-            if (b.m == 0) continue;
-            const int *fl = kind == CFMM_POOLK_SUM ? ctx->flagsG[k] : nullptr;          // (as cfmm_get_tradesG)
-            const double *ov = (kind == CFMM_POOLK_SUM && ownk[k]) ? ctx->audit_ovr + off_ownk[k] : nullptr;
-            slot(apply_recG(kind, k));
-            with_int<CFMM_POOLK_STABLE, CFMM_POOLK_SUM>(kind, [&](auto KIND) {
-                with_int<2, 8>(k, [&](auto K) { hipLaunchKernelGGL((auditG_kernel<KIND, K>), dim3(audit_grid(ctx, b.m)), blk, lds, ctx->stream, b, fl, nu, slo, mu, ov, a); });
-            });
-        }
-    HIP_TRY(ctx, hipGetLastError());
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->audit_host, ctx->audit_dev, sp.parts, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (timed) { float ms = 0.f; HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1)); ctx->audit_sec = ms * 1e-3; }
-    // the report
-    const AuditRec *res = (const AuditRec *)(ctx->audit_host + sp.recs);
-    const unsigned long long *hl = (const unsigned long long *)(ctx->audit_host + sp.limbs);
-    int F = 0;
-    (void)std::frexp(sc, &F); F -= 1;                                       // sc = 2^F
-    out->fixed_exponent = F;
-    unsigned long long best = ~0ull;
-    int first = -1;
-    unsigned long long tender = ~0ull, leg = ~0ull;
-    auto take = [&](int64_t m, int q) {
-        if (m == 0) return;
-        out->pools += m; out->pools_trading += (int64_t)res[q].trading; out->pools_violating += (int64_t)res[q].violating; out->legs_out_of_range += (int64_t)res[q].oor;
-        if (first < 0 || res[q].slack < best) { best = res[q].slack; first = q; }       // (ties: the first in bucket order)
-        tender = std::min(tender, res[q].tender); leg = std::min(leg, res[q].leg);
-    };
-    for (int kind = 0; kind < CFMM_POOL_KINDS2; ++kind) take(ps.r2[kind].b.m, apply_rec2(kind));
-    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) take(ps.rn[k].b.m, apply_recN(k));
-    for (int kind = 0; kind < CFMM_POOLK_KINDS; ++kind) for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) take(ps.rg[kind][k].b.m, apply_recG(kind, k));
-    if (first >= 0) {
-        int fam = 0, kind = first, k = 2;
-        if (first >= apply_recG(0, 0)) { fam = 2; kind = (first - apply_recG(0, 0)) / (CFMM_MAX_POOL_SIZE + 1); k = (first - apply_recG(0, 0)) % (CFMM_MAX_POOL_SIZE + 1); }
-        else if (first >= apply_recN(0)) { fam = 1; kind = 0; k = first - apply_recN(0); }
-        out->worst_family = fam; out->worst_kind = kind; out->worst_k = k; out->worst_pos = (int64_t)res[first].pos;
-        out->min_slack = audit_unord(best); out->min_tender = audit_unord(tender); out->min_leg = audit_unord(leg);
-    }
-    if (limbs) std::memcpy(limbs, hl, 3 * (size_t)n * sizeof(uint64_t));
-    std::vector<double> hp((size_t)n);
-    for (int j = 0; j < n; ++j) {
-        const Fixed128 t = fixed_combine(hl[j], hl[n + j], hl[2 * (size_t)n + j]);
-        const __int128 v = (__int128)(((unsigned __int128)(unsigned long long)t.hi << 64) | (unsigned __int128)t.lo);
-        hp[j] = std::ldexp((double)v, -F);                                  // one correctly rounded conversion, one exact scaling
-    }
-    if (psi) std::memcpy(psi, hp.data(), (size_t)n * sizeof(double));
-    if (ctx->have_utility) {
-        // linear-plus-box tokens as sweep::point_certificates (cfmm_stats); the utility table's entries by their own u, outside infeas
-        double value = 0.0, viol = 0.0, scale = 0.0;
-        for (int j = 0; j < n; ++j) {
-            const double c = ctx->hc[j], h = ctx->hh[j], r = hp[j] + h;
-            const int ct = ctx->hctype[j];
-            if (ct == CFMM_ULOG) value += c * std::log(r);
-            else if (ct == CFMM_UQUAD) value += c * hp[j] - hp[j] * hp[j] / (2.0 * h);
-            else {
-                value += c * hp[j];
-                viol = std::max(viol, ct == CFMM_GE ? std::max(-r, 0.0) : (ct == CFMM_EQ ? std::fabs(r) : 0.0));
-                scale = std::max(scale, std::fabs(h));
-            }
-            scale = std::max(scale, std::fabs(hp[j]));
-        }
-        out->value = value;
-        out->infeas = viol / std::max(std::max(scale, 1e-12 * ctx->max_reserve), 1e-300);
-    }
+    const route::Counts counts = bucket_counts(entry.ps);
+    AuditRun R{ctx, entry.ps, tol_pool > 0.0 ? tol_pool : 1e-9, counts, route::trade_layout(counts), route::audit_span(ctx->n, AU_GRID_MAX), ctx->pt.tr_ovr_valid, {}, 0.0};
+    { int rc = audit_reserve(R); if (rc) return rc; }
+    { int rc = audit_stage_tenders(R, own); if (rc) return rc; }
+    { int rc = audit_pass(R); if (rc) return rc; }
+    audit_report(R, out, psi, limbs);
     return CFMM_OK;
 }
 

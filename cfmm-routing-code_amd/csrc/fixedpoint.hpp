@@ -5,7 +5,7 @@
 #include <cmath>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
-#define CFMM_FX_HD __host__ __device__ __forceinline__
+#define CFMM_FX_HD __host__ __device__ inline __attribute__((always_inline))     // (__forceinline__ spelt out: a host program that hipcc builds need not include the HIP runtime's header)
 #else
 #define CFMM_FX_HD inline
 #endif

@@ -376,6 +376,36 @@ def test_a_drained_pool_refuses_the_whole_call_and_nothing_changes():
     pc.close(); p.close()
 
 
+def test_a_drained_table_pool_is_named_by_family_kind_size_and_position():
+    """the refusal names a bucket beyond the two-asset family: 40 constant-product pools over 16 tokens and 20 three-asset constant-sum
+    pools of the K-asset table, those over tokens 0 .. 7 inside their fee band, the one at upload position 7 alone over tokens
+    (8, 9, 10) with gamma nu_9 > nu_8 -- its leg in token 9 is paid out whole"""
+    n, rng = 16, np.random.default_rng(41)
+    net = synthetic.make_network(n, m_cp2=40, seed=12)
+    ms, k = 20, 3
+    idx = np.stack([rng.choice(8, k, replace=False) for _ in range(ms)]).T.astype(np.int32)
+    idx[:, 7] = (8, 9, 10)
+    net["gk"] = {("sum", k): dict(idx=np.ascontiguousarray(idx), R=np.exp(rng.normal(3.0, 1.0, (k, ms))), fee=np.full(ms, 0.997), param=np.zeros(ms))}
+    nu = net["c"] * np.exp(rng.normal(0.0, 0.05, n))
+    nu[:8] = np.exp(rng.uniform(-1e-4, 1e-4, 8))
+    nu[9] = 1.2 * nu[8]; nu[10] = 1.0001 * nu[8]
+    p = cfmm.Problem.from_network(copy_net(net), utility=cfmm.Arbitrage(net["c"]))
+    ctx = p._ensure_ctx()
+    ctx.set_nu(nu)
+    lam = trades_of(ctx, net)[("sum", k)][1]
+    assert lam[1, 7] == net["gk"][("sum", k)]["R"][1, 7], (lam[:, 7], net["gk"][("sum", k)]["R"][:, 7])      # Lambda = R_out
+    before = reserves_of(ctx, net)
+    for mode in MODES:
+        rc, info = ctx.apply_trades(mode, check=False)
+        assert rc == _lib.E_UNSUPPORTED, (rc, info)
+        assert info["pools_refused"] == 1
+        assert (info["first_family"], info["first_kind"], info["first_k"], info["first_pos"]) == (2, _lib.POOLK["sum"], k, 7), info
+    after = reserves_of(ctx, net)
+    for key in before:
+        assert np.array_equal(after[key], before[key]), key
+    p.close()
+
+
 # ------------------------------------------------------------------------------------------- 6: state refusals
 def test_state_refusals_leave_the_pools_untouched():
     net, _ = drained_network()

@@ -1164,6 +1164,269 @@ def test_swept_solve_folds_the_arbitrage_fill_and_certifies_the_point(tmp_path):
     assert 0.0 <= gap <= 1e-12 and 0.0 <= infeas <= 1e-12, (gap, infeas)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# csrc/route_rules.hpp: the bucket order and its slots, the layouts of host-held tenders, the folds of the apply's and the audit's
+# records, the audited psi from its limbs and its worth under a utility
+# ---------------------------------------------------------------------------------------------------------------
+_ROUTE_HELPERS = r'''
+#include <cstdint>
+#include <cstring>
+inline void rowi(const char *k, const long long *v, int n) { printf("%s", k); for (int i = 0; i < n; ++i) printf(" %lld", v[i]); printf("\n"); }
+inline unsigned long long bits(double x) { unsigned long long b; std::memcpy(&b, &x, sizeof b); return b; }
+// pools per slot of the tests' store: two-asset kinds 3 0 5 0 2, geo-mean sizes 3: 4, 5: 1, the table's stableswap 3: 7, constant sum 3: 6, 5: 2
+inline Counts some_counts()
+{
+    Counts c = {};
+    c.m[slot2(0)] = 3; c.m[slot2(2)] = 5; c.m[slot2(4)] = 2; c.m[slotN(3)] = 4; c.m[slotN(5)] = 1;
+    c.m[slotG(CFMM_POOLK_STABLE, 3)] = 7; c.m[slotG(CFMM_POOLK_SUM, 3)] = 6; c.m[slotG(CFMM_POOLK_SUM, 5)] = 2;
+    return c;
+}
+'''
+_KINDS2, _KS, _POOLK = _lib.POOL_POW2 + 1, _lib.MAX_POOL_SIZE + 1, dict(stable=0, sum=1)
+_slot2 = lambda kind: kind
+_slotN = lambda k: _KINDS2 + k
+_slotG = lambda kind, k: _KINDS2 + _KS * (1 + kind) + k
+
+
+def _route_rules_program(tmp_path, name, body):
+    """a stand-alone HOST program over csrc/route_rules.hpp (nothing of HIP in it): compiled -Wall -Werror, run, its output lines"""
+    return _rules_program(tmp_path, "route_rules.hpp", "route", name, body, _ROUTE_HELPERS)
+
+
+def _ints(line):
+    return [int(x) for x in line.split()]
+
+
+def test_route_slots_round_trip_and_ascend_in_the_documented_bucket_order(tmp_path):
+    """csrc/route_rules.hpp: slot2 / slotN / slotG, slot_name, each_slot.  The documented bucket order (include/cfmm.h: cfmm_apply_info) --
+    two-asset kinds 0.., geo-mean sizes 3..8, the table's kinds each by size 2..8 -- written out here: slot_name inverts the slot of every
+    bucket with the family / kind / k the header documents, no slot is hit twice, the slots ascend along that order and stay below SLOTS,
+    and each_slot enumerates exactly that order.  No slot: -1 each."""
+    assert (_KINDS2, _KS, _lib.POOLK) == (5, 9, _POOLK)
+    order = [(0, kind, 2) for kind in range(_KINDS2)] + [(1, 0, k) for k in range(3, _KS)] + [(2, kind, k) for kind in range(2) for k in range(2, _KS)]
+    got = _keyed(_route_rules_program(tmp_path, "slots", r'''
+    for (int kind = 0; kind < CFMM_POOL_KINDS2; ++kind) { const SlotName s = slot_name(slot2(kind)); printf("slot %d %d %d %d\n", slot2(kind), s.family, s.kind, s.k); }
+    for (int k = 3; k <= CFMM_MAX_POOL_SIZE; ++k) { const SlotName s = slot_name(slotN(k)); printf("slot %d %d %d %d\n", slotN(k), s.family, s.kind, s.k); }
+    for (int kind = 0; kind < CFMM_POOLK_KINDS; ++kind) for (int k = 2; k <= CFMM_MAX_POOL_SIZE; ++k) { const SlotName s = slot_name(slotG(kind, k)); printf("slot %d %d %d %d\n", slotG(kind, k), s.family, s.kind, s.k); }
+    each_slot([](int q, int family, int kind, int k) { printf("each %d %d %d %d\n", q, family, kind, k); });
+    const SlotName none = slot_name(-1);
+    printf("none %d %d %d\nslots %d\n", none.family, none.kind, none.k, SLOTS);'''))
+    rows = [_ints(l) for l in got["slot"]]
+    assert [tuple(r[1:]) for r in rows] == order                         # the round trip, in the order written out above
+    slots = [r[0] for r in rows]
+    assert slots == sorted(set(slots)) and 0 <= slots[0] and slots[-1] < int(got["slots"][0])      # distinct, ascending, in range
+    assert slots == [_slot2(k) for k in range(_KINDS2)] + [_slotN(k) for k in range(3, _KS)] + [_slotG(kind, k) for kind in range(2) for k in range(2, _KS)]
+    assert [_ints(l) for l in got["each"]] == rows
+    assert _ints(got["none"][0]) == [-1, -1, -1]
+
+
+def test_route_layouts_of_swept_tenders_and_of_the_audits_staged_tenders(tmp_path):
+    """csrc/route_rules.hpp: trade_layout, audit_stage, audit_span, fixed_exponent, point_view on hand-set counts with empty buckets in the middle
+    (_ROUTE_HELPERS: some_counts).  The sums are written out here.  The staging layout: without and with the kink loop's block, the caller's
+    two-asset block, two k-asset blocks, all three; each way of naming one array of a bucket without the other gives that bucket's slot
+    (the first in the order two-asset, then k ascending); arrays named for an empty bucket are ignored."""
+    got = _keyed(_route_rules_program(tmp_path, "layouts", r'''
+    const Counts c = some_counts();
+    const TradeLayout t = trade_layout(c);
+    { long long v[CFMM_POOL_KINDS2]; for (int k = 0; k < CFMM_POOL_KINDS2; ++k) v[k] = (long long)t.off2[k]; rowi("off2", v, CFMM_POOL_KINDS2); }
+    { long long v[KS] = {}; for (int k = 3; k < KS; ++k) v[k] = (long long)t.offn[k]; rowi("offn", v, KS); }
+    printf("stride %zu %zu\n", t.stride, t.two_asset());
+    const double x = 0.0, *p = &x;
+    auto show = [&](const char *key, const Counts &cc, bool kink, const cfmm_audit_tenders *own) {
+        const AuditStage s = audit_stage(cc, kink, own);
+        printf("%s %zu %d %d %zu |", key, s.len, s.half, (int)s.own2, s.off_own2);
+        for (int k = 2; k < KS; ++k) printf(" %d:%zu", (int)s.ownk[k], s.off_ownk[k]);
+        printf("\n");
+    };
+    cfmm_audit_tenders own = {};
+    show("none", c, false, nullptr); show("kink", c, true, nullptr); show("blank", c, true, &own);
+    own.sum2_delta = own.sum2_lambda = p;                               show("own2", c, true, &own);
+    own.sumk_delta[3] = own.sumk_lambda[3] = p;                         show("all", c, true, &own);
+    own.sumk_delta[4] = p;                                              show("empty4", c, true, &own);      // (no 4-asset bucket: ignored)
+    own.sum2_delta = own.sum2_lambda = nullptr; own.sumk_delta[5] = own.sumk_lambda[5] = p; show("ownk", c, false, &own);
+    own.sumk_lambda[5] = nullptr;                                       show("half5d", c, false, &own);
+    own.sumk_lambda[5] = p; own.sumk_delta[3] = nullptr;                show("half3l", c, false, &own);
+    own.sum2_delta = p;                                                 show("half2d", c, true, &own);      // (the two-asset bucket is met first)
+    own.sum2_delta = nullptr; own.sum2_lambda = p;                      show("half2l", c, true, &own);
+    Counts e = c; e.m[slot2(CFMM_POOL_SUM2)] = 0;                       show("empty2", e, false, &own);      // (no constant-sum pairs: ignored, bucket 3 is half)
+    const AuditSpan sp = audit_span(10, 2048);
+    printf("span %zu %zu %zu %zu %zu\n", sp.recs, sp.limbs, sp.parts, sp.total, sizeof(cfmm::AuditRec));
+    printf("exp %d %d %d\n", fixed_exponent(0x1p71), fixed_exponent(0x1p-3), fixed_exponent(1.0));
+    for (double mu : {0.0, 1e-6, -1.0}) for (int slo = 0; slo < 2; ++slo) { const PointView v = point_view(mu, slo != 0); printf("view %.17g %d\n", v.mu, (int)v.use_slo); }'''))
+    # which point the tenders are of: the barrier weight only while positive, the low-order log-prices only with it
+    assert [(float(l.split()[0]), int(l.split()[1])) for l in got["view"]] == [(0.0, 0), (0.0, 0), (1e-6, 0), (1e-6, 1), (0.0, 0), (0.0, 0)]
+    # two-asset kinds 3 0 5 0 2 pools of 4 doubles; geo-mean 3: 4 pools of 6, 5: 1 pool of 10
+    assert _ints(got["off2"][0]) == [0, 12, 12, 32, 32]
+    assert _ints(got["offn"][0])[3:] == [40, 64, 64, 74, 74, 74]
+    assert got["stride"] == ["74 40"]
+    two, s2, s3, s5 = 40, 4 * 5, 2 * 3 * 6, 2 * 5 * 2
+    no = " ".join(["0:0"] * 7)
+    ks = lambda d: " ".join("1:%d" % d[k] if k in d else "0:0" for k in range(2, _KS))
+    assert got["none"] == ["0 -1 0 0 | " + no] and got["kink"] == ["%d -1 0 0 | %s" % (two, no)] and got["blank"] == got["kink"]
+    assert got["own2"] == ["%d -1 1 %d | %s" % (two + s2, two, no)]
+    assert got["all"] == ["%d -1 1 %d | %s" % (two + s2 + s3, two, ks({3: two + s2}))] and got["empty4"] == got["all"]
+    assert got["ownk"] == ["%d -1 0 0 | %s" % (s3 + s5, ks({3: 0, 5: s3}))]
+    assert _ints(got["half5d"][0].split("|")[0])[1] == _slotG(_POOLK["sum"], 5)
+    assert _ints(got["half3l"][0].split("|")[0])[1] == _slotG(_POOLK["sum"], 3)
+    assert _ints(got["half2d"][0].split("|")[0])[1] == _slot2(_lib.POOL_SUM2) and _ints(got["half2l"][0].split("|")[0])[1] == _slot2(_lib.POOL_SUM2)
+    assert _ints(got["empty2"][0].split("|")[0])[1] == _slotG(_POOLK["sum"], 3)
+    # one 64-byte record per slot | 3 n limbs, rounded up to 256 bytes | 2048 partial records per slot
+    slots = _KINDS2 + 3 * _KS
+    parts = -(-(slots * 64 + 3 * 10 * 8) // 256) * 256
+    assert got["span"] == ["0 %d %d %d 64" % (slots * 64, parts, parts + slots * 2048 * 64)]
+    assert got["exp"] == ["71 -3 0"]
+
+
+def test_route_fold_of_the_apply_records(tmp_path):
+    """csrc/route_rules.hpp: fold_apply.  Refusals in a later slot (the table's 3-asset constant-sum bucket) and an earlier one (the
+    3-asset geo-mean bucket): the earlier one is named, with ITS position; the totals add over the resident buckets; each largest reserve
+    is the double whose bit pattern the record holds (one ulp under 2048 survives); empty slots holding stale records -- a refusal in
+    front of every other, a larger maximum -- are ignored.  Without a refusal: -1 / -1."""
+    got = _keyed(_route_rules_program(tmp_path, "fold_apply", r'''
+    const Counts c = some_counts();
+    cfmm::ApplyRec r[SLOTS];
+    for (auto &q : r) q = cfmm::ApplyRec{0ull, 0ull, ~0ull, 0ull};
+    r[slot2(0)] = {3, 0, ~0ull, bits(2.0)};
+    r[slot2(1)] = {100, 5, 0, bits(1e308)};                                 // (stale: no pool of kind 1)
+    r[slot2(2)] = {4, 0, ~0ull, bits(0x1.fffffffffffffp+10)};
+    r[slotN(3)] = {4, 2, 11, bits(1e300)};
+    r[slotN(4)] = {9, 9, 1, bits(1e301)};                                   // (stale)
+    r[slotG(CFMM_POOLK_SUM, 3)] = {1, 1, 7, bits(3.0)};
+    auto show = [&](const char *key) {
+        const ApplyFold f = fold_apply(r, c);
+        printf("%s %lld %lld %d %lld\n", key, (long long)f.moved, (long long)f.refused, f.first, (long long)f.first_pos);
+        const double v[] = {f.mx[slot2(0)], f.mx[slot2(1)], f.mx[slot2(2)], f.mx[slotN(3)], f.mx[slotN(4)], f.mx[slotG(CFMM_POOLK_SUM, 3)], f.mx_all};
+        row(key, v, 7);
+    };
+    show("two");
+    r[slotN(3)].refused = 0; r[slotN(3)].first = ~0ull; show("later");
+    r[slotG(CFMM_POOLK_SUM, 3)].refused = 0; show("clean");'''))
+    top = float.fromhex("0x1.fffffffffffffp+10")
+    assert got["two"][0] == "12 3 %d 11" % _slotN(3) and [float(x) for x in got["two"][1].split()] == [2.0, 0.0, top, 1e300, 0.0, 3.0, 1e300]
+    assert got["later"][0] == "12 1 %d 7" % _slotG(_POOLK["sum"], 3)
+    assert got["clean"][0] == "12 0 -1 -1"
+
+
+def test_route_fold_of_the_audit_records_and_the_order_preserving_images(tmp_path):
+    """csrc/route_rules.hpp: fold_audit, audit_ord / audit_unord.  The same smallest slack in two buckets names the first in bucket
+    order; a strictly smaller one in a later bucket wins; a stale record in an empty slot does not count; the counts add and the
+    minima come back as doubles.  An empty network: -1 / -1 / -1 / -1 and +inf three times.  audit_unord(audit_ord(x)) is x bit for bit
+    for +-0, denormals, +-inf and ordinary values, NaN counts as -inf, and the images ascend with the doubles."""
+    import struct
+    xs = [float("-inf"), -2.25, -5e-324, -0.0, 0.0, 5e-324, 2.2250738585072014e-308 / 4, 1.5, float("inf")]
+    got = _keyed(_route_rules_program(tmp_path, "fold_audit", r'''
+    using cfmm::audit_ord; using cfmm::audit_unord;
+    const Counts c = some_counts();
+    cfmm::AuditRec r[SLOTS];
+    for (auto &q : r) q = cfmm::AuditRec{0ull, 0ull, 0ull, ~0ull, ~0ull, ~0ull, ~0ull, 0ull};
+    r[slot2(0)] = {2, 1, 0, audit_ord(-0.5), 3, audit_ord(0.0), audit_ord(0.25), 1};
+    r[slot2(1)] = {50, 50, 50, audit_ord(-100.0), 0, audit_ord(-7.0), audit_ord(-7.0), 1};      // (stale: no pool of kind 1)
+    r[slot2(2)] = {5, 0, 1, audit_ord(0.0), 0, audit_ord(1.0), audit_ord(0.0), 1};
+    r[slot2(4)] = {0, 0, 0, audit_ord(1e-3), 1, audit_ord(2.0), audit_ord(0.5), 1};
+    r[slotN(3)] = {4, 1, 0, audit_ord(-0.5), 1, audit_ord(-1e-9), audit_ord(0.5), 1};
+    r[slotN(5)] = {1, 0, 0, audit_ord(0.125), 0, audit_ord(0.0), audit_ord(0.75), 1};
+    r[slotG(CFMM_POOLK_STABLE, 3)] = {7, 0, 2, audit_ord(1e-12), 6, audit_ord(0.0), audit_ord(0.9), 1};
+    r[slotG(CFMM_POOLK_SUM, 3)] = {3, 0, 0, audit_ord(-0.25), 5, audit_ord(0.0), audit_ord(0.125), 1};
+    r[slotG(CFMM_POOLK_SUM, 5)] = {2, 0, 0, audit_ord(0.0), 0, audit_ord(0.0), audit_ord(1.0), 1};
+    auto show = [&](const char *key, const Counts &cc) {
+        const AuditFold f = fold_audit(r, cc);
+        const SlotName s = slot_name(f.worst);
+        printf("%s %lld %lld %lld %lld %d %d %d %d %lld\n", key, (long long)f.pools, (long long)f.trading, (long long)f.violating, (long long)f.oor, f.worst, s.family, s.kind, s.k, (long long)f.worst_pos);
+        const double v[] = {f.min_slack, f.min_tender, f.min_leg}; row(key, v, 3);
+    };
+    show("tie", c);
+    r[slotG(CFMM_POOLK_SUM, 3)].slack = audit_ord(-0.75); show("later", c);
+    r[slotG(CFMM_POOLK_SUM, 3)].slack = audit_ord(NAN); show("nan", c);
+    const Counts none = {}; show("empty", none);
+    const double xs[] = {@XS@, NAN};
+    for (double x : xs) printf("ord %llu %llu %llu\n", bits(x), audit_ord(x), bits(audit_unord(audit_ord(x))));'''.replace("@XS@", ", ".join(
+        "-INFINITY" if x == float("-inf") else "INFINITY" if x == float("inf") else x.hex() for x in xs))))
+    head = "30 24 2 3"                                                  # pools 3 + 5 + 2 + 4 + 1 + 7 + 6 + 2; trading, violating, out of range added up
+    assert got["tie"][0] == "%s %d 0 0 2 3" % (head, _slot2(0)) and [float(x) for x in got["tie"][1].split()] == [-0.5, -1e-9, 0.0]
+    assert got["later"][0] == "%s %d 2 %d 3 5" % (head, _slotG(_POOLK["sum"], 3), _POOLK["sum"]) and float(got["later"][1].split()[0]) == -0.75
+    assert got["nan"][0] == got["later"][0] and float(got["nan"][1].split()[0]) == float("-inf")      # (what cannot be computed is the worst)
+    assert got["empty"][0] == "0 0 0 0 -1 -1 -1 -1 -1" and [float(x) for x in got["empty"][1].split()] == [float("inf")] * 3
+    rows = [_ints(l) for l in got["ord"]]
+    as_bits = lambda x: struct.unpack("<Q", struct.pack("<d", x))[0]
+    assert [r[0] for r in rows[:-1]] == [as_bits(x) for x in xs]
+    assert all(r[2] == r[0] for r in rows[:-1])                          # the round trip, bit for bit (-0 stays -0)
+    assert rows[-1][2] == as_bits(float("-inf")) and rows[-1][1] == rows[0][1]
+    assert [r[1] for r in rows[:-1]] == sorted(set(r[1] for r in rows[:-1]))      # strictly ascending with the doubles
+
+
+def _limb_sums(contribs):
+    """[3][n] uint64 limb sums of per-token lists of integers, each split as fixed_split does (a0, a1 in [0, 2^32), a2 = v >> 64 signed),
+    the sums wrapped to 64 bits"""
+    M32, M64 = (1 << 32) - 1, (1 << 64) - 1
+    out = np.zeros((3, len(contribs)), dtype=np.uint64)
+    for j, vs in enumerate(contribs):
+        out[0, j] = sum(v & M32 for v in vs) & M64
+        out[1, j] = sum((v >> 32) & M32 for v in vs) & M64
+        out[2, j] = sum(v >> 64 for v in vs) & M64
+    return out
+
+
+def test_route_psi_from_limbs_against_python_integers(tmp_path):
+    """csrc/route_rules.hpp: psi_from_limbs = fixed_combine, ONE correctly rounded conversion, one exact scaling.  Limb sums of exact
+    floors (helpers.exact_floor) for a negative sum, a sum whose low limbs carry (5000 contributions with full low limbs: l0, l1 beyond
+    2^32), sums beyond 2^64 in magnitude of both signs, more than 53 significant bits (the conversion must round, once), zero: the
+    result equals math.ldexp(float(v), -F) exactly, v the Python integer the limbs stand for (helpers.limbs_as_integers)."""
+    import math
+    from helpers import exact_floor, limbs_as_integers
+    F = 40
+    ys = [[-3.75, 1.5, -2.0 ** -45],                                     # negative, with a fraction that floors away
+          [(2.0 ** 32 - 1) * 2.0 ** -F] * 5000 + [(2.0 ** 32 - 1) * 2.0 ** (32 - F)] * 5000,       # a0 = 2^32 - 1, then a1 = 2^32 - 1, 5000 times each: both low sums carry
+          [2.0 ** 30, 2.0 ** 41 + 1.0, 3.0 * 2.0 ** 40],                 # 2^F y beyond 2^64
+          [-2.0 ** 41 - 2.0 ** -11, -7.0 * 2.0 ** 39, -2.0 ** -45],      # ... and negative
+          [2.0 ** 30 + 2.0 ** -22, 2.0 ** -40, 2.0 ** -40, 1.0 + 2.0 ** -39],      # 71 significant bits: rounded once
+          [0.0]]
+    ints = [exact_floor(np.array(y), F) for y in ys]
+    limbs = _limb_sums(ints)
+    want = [sum(v) for v in ints]
+    assert limbs_as_integers(limbs) == want
+    assert want[0] < 0 and int(limbs[0, 1]) >= 2 ** 32 and int(limbs[1, 1]) >= 2 ** 32 and want[2] > 2 ** 64 and want[3] < -2 ** 64 and want[4].bit_length() > 53
+    n = len(ys)
+    got = _route_rules_program(tmp_path, "psi", "    const unsigned long long hl[] = {%s};\n    double psi[%d];\n    psi_from_limbs(hl, %d, %d, psi);\n    row(\"psi\", psi, %d);"
+                               % (", ".join("%dull" % int(x) for x in limbs.reshape(-1)), n, n, F, n))
+    assert [float(x) for x in got[0].split()[1:]] == [math.ldexp(float(v), -F) for v in want]
+
+
+def test_route_value_and_infeasibility_of_the_audited_psi_against_the_numpy_twin(tmp_path):
+    """csrc/route_rules.hpp: psi_worth against cfmm.problem.audit_trades on the SAME psi (the twin's own): the shipped arbitrage instance
+    at the fixture's KKT point with its utility, and hand-made tenders on a random six-token network under a hand-made utility with one
+    token of every kind (GE, EQ, FREE, ULOG, UQUAD, and a second GE with h < 0 that is violated).  Both add the tokens' terms in token
+    order in doubles and take the same maxima: infeas must be EQUAL, value within one ulp of the twin's (both cases gave equal bits; the
+    ulp is for the ULOG term, which goes through the C library's log here and NumPy's there)."""
+    import math
+    from cfmm.problem import Utility, audit_trades, audit_buckets
+    from test_audit_host import kkt_route
+    cases = []
+    p, _, tr = kkt_route("arbitrage", dict(shipped_cases())["arbitrage"])
+    cases.append(("shipped", p.net, tr, p.utility))
+    q = problem_of(random_instance(5, n_tokens=6, n_pools=10))
+    tr = {}
+    for b in audit_buckets(q.net):
+        d, l = np.zeros_like(b["R"]), np.zeros_like(b["R"])
+        d[0] = 0.0625 * b["R"][0]; l[1] = 0.03125 * b["R"][1]
+        tr[b["key"]] = (d, l)
+    ct = np.array([_lib.GE, _lib.EQ, _lib.FREE, _lib.ULOG, _lib.UQUAD, _lib.GE], dtype=np.int32)
+    cases.append(("hand", q.net, tr, Utility(np.array([1.0, 0.9, 1.1, 2.5, 1.2, 0.8]), np.array([0.5, 0.25, 3.0, 1e3, 40.0, -1e3]), ct)))
+    body, want = "", {}
+    for name, net, tr, util in cases:
+        rep = audit_trades(net, tr, util)
+        mr = max(float(b["R"].max()) for b in audit_buckets(net))
+        want[name] = (rep, util)
+        body += ("    { " + _cvec("psi", rep["psi"]) + _cvec("c", util.c) + _cvec("h", util.h) + _cvec("ct", util.ctype, "int")
+                 + " const PsiWorth w = psi_worth(psi, %d, c, h, ct, %r); const double v[] = {w.value, w.infeas}; row(\"%s\", v, 2); }\n" % (len(rep["psi"]), mr, name))
+    got = _keyed(_route_rules_program(tmp_path, "worth", body))
+    for name, (rep, util) in want.items():
+        value, infeas = [float(x) for x in got[name][0].split()]
+        print(name, "value", value, rep["value"], "infeas", infeas, rep["infeas"])
+        assert infeas == rep["infeas"], (name, infeas, rep["infeas"])
+        assert abs(value - rep["value"]) <= math.ulp(rep["value"]), (name, value, rep["value"])
+    assert want["hand"][0]["infeas"] > 0.0 and np.isfinite(want["hand"][0]["value"]) and want["shipped"][0]["infeas"] <= 1e-12
+
+
 def test_switch_records_of_a_k_asset_constant_sum_pool_are_rooted_at_the_paying_leg():
     """cfmm/problem.py: _canonical_switches, _split_payers (round 6, pure functions of the records: every rank of a pool-sharded solve
     computes the same).  Three tokens tied for cheapest, found pair by pair in rounds whose cheapest token differed -- records (0, 3) and
