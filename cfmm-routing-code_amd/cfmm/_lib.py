@@ -88,7 +88,7 @@ assert _STATS_STRUCT.size == C.sizeof(Stats)
 
 def build(force=False):
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp", "update.hpp", "apply.hpp", "audit.hpp", "solve_plan.hpp", "newton_rules.hpp", "sweep_rules.hpp", "tiny_limits.hpp", "fixedpoint.hpp")]
+    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp", "update.hpp", "apply.hpp", "audit.hpp", "solve_plan.hpp", "newton_rules.hpp", "sweep_rules.hpp", "route_rules.hpp", "update_rules.hpp", "tiny_limits.hpp", "fixedpoint.hpp")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "cfmm.h"))
     if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _CSRC, "-s"])
@@ -99,6 +99,7 @@ _lib = None
 
 SYMBOLS = ["cfmm_create", "cfmm_clone", "cfmm_destroy", "cfmm_last_error", "cfmm_backend", "cfmm_default_opts",
            "cfmm_upload_pools2", "cfmm_upload_poolsN", "cfmm_upload_poolsG", "cfmm_update_pools2", "cfmm_update_poolsN", "cfmm_update_poolsG",
+           "cfmm_update_terms2", "cfmm_update_termsN", "cfmm_update_termsG",
            "cfmm_apply_trades", "cfmm_get_reserves2", "cfmm_get_reservesN", "cfmm_get_reservesG", "cfmm_apply_timers", "cfmm_audit_trades", "cfmm_debug_audit_launch", "cfmm_set_pool_flags", "cfmm_set_pool_flagsG", "cfmm_set_utility",
            "cfmm_set_ties", "cfmm_set_deterministic", "cfmm_debug_eval_limbs", "cfmm_debug_scatter_limbs", "cfmm_eval_dual", "cfmm_eval_smooth", "cfmm_debug_cholesky", "cfmm_debug_cholesky_apply", "cfmm_time_xcd_handoff", "cfmm_solve", "cfmm_solve_batch", "cfmm_eval_dual_batch", "cfmm_batch_capacity", "cfmm_solve_sweep", "cfmm_get_nu", "cfmm_set_nu", "cfmm_get_psi",
            "cfmm_get_solution", "cfmm_get_trades2", "cfmm_get_tradesN", "cfmm_get_tradesG", "cfmm_comm_unique_id", "cfmm_comm_init",
@@ -128,6 +129,9 @@ def lib():
     L.cfmm_update_pools2.argtypes = [vp, C.c_int, C.c_int64, ip, dp, dp, dp]
     L.cfmm_update_poolsN.argtypes = [vp, C.c_int, C.c_int64, ip, dp]
     L.cfmm_update_poolsG.argtypes = [vp, C.c_int, C.c_int, C.c_int64, ip, dp, dp]
+    L.cfmm_update_terms2.argtypes = [vp, C.c_int, C.c_int64, ip, dp, dp]
+    L.cfmm_update_termsN.argtypes = [vp, C.c_int, C.c_int64, ip, dp, dp]
+    L.cfmm_update_termsG.argtypes = [vp, C.c_int, C.c_int, C.c_int64, ip, dp]
     L.cfmm_apply_trades.argtypes = [vp, C.c_int, C.POINTER(ApplyInfo)]
     L.cfmm_get_reserves2.argtypes = [vp, C.c_int, dp, dp, dp]
     L.cfmm_get_reservesN.argtypes = [vp, C.c_int, dp]
@@ -288,6 +292,28 @@ class Context:
         if cnt != len(pos) or (param is not None and len(param) != cnt):
             raise CfmmError(f"update_poolsG: {len(pos)} positions but {cnt} reserve columns" + ("" if param is None else f", {len(param)} parameters"))
         self._chk(self.L.cfmm_update_poolsG(self.h, kind, k, cnt, _i(pos), _d(R), _d(param)))
+
+    def update_terms2(self, kind, pos, fee=None, wa=None):
+        """new fees and / or (POOL_W2) weights wa of the pools `pos` (upload order) of a two-asset bucket, in place; None = unchanged"""
+        pos, fee, wa = i32(pos), f64(fee), f64(wa)
+        if any(c is not None and len(c) != len(pos) for c in (fee, wa)):
+            raise CfmmError(f"update_terms2: {len(pos)} positions but columns of " + ", ".join(str(len(c)) for c in (fee, wa) if c is not None) + " entries")
+        self._chk(self.L.cfmm_update_terms2(self.h, kind, len(pos), _i(pos), _d(fee), _d(wa)))
+
+    def update_termsN(self, k, pos, fee=None, w=None):
+        """new fees [count] and / or weights w [k][count] of the pools `pos` of the geo-mean bucket of k assets, in place; None = unchanged"""
+        pos, fee, w = i32(pos), f64(fee), f64(w)
+        if (fee is not None and len(fee) != len(pos)) or (w is not None and w.shape != (k, len(pos))):
+            raise CfmmError(f"update_termsN: {len(pos)} positions of {k}-asset pools but" + ("" if fee is None else f" {len(fee)} fees")
+                            + ("" if w is None else f" weights of shape {w.shape}"))
+        self._chk(self.L.cfmm_update_termsN(self.h, int(k), len(pos), _i(pos), _d(fee), _d(w)))
+
+    def update_termsG(self, kind, k, pos, fee):
+        """new fees of the pools `pos` of the K-asset table's bucket (kind, k), in place"""
+        pos, fee = i32(pos), f64(fee)
+        if fee is not None and len(fee) != len(pos):
+            raise CfmmError(f"update_termsG: {len(pos)} positions but {len(fee)} fees")
+        self._chk(self.L.cfmm_update_termsG(self.h, kind, int(k), len(pos), _i(pos), _d(fee)))
 
     def apply_trades(self, fee_mode=0, check=True):
         """commit the tenders cfmm_get_trades* would return now to the resident pools (cfmm_apply_trades); fee_mode: FEE_MODES or its

@@ -244,6 +244,59 @@ def route_updates(net, where, pools, reserves, params=None):
     return out
 
 
+def route_terms(net, where, pools, fees=None, weights=None):
+    """New fees and / or weights of some pools of a packed network, routed to their buckets, beside route_updates: `pools` are indices
+    into the reference's pool list, fees[i] the new fee of pools[i], weights[i] its new geo-mean exponents (either list may be None, or
+    hold None for "unchanged").  Weights are normalised as pack() does (w / w.sum()).  Checks lengths, the fee in (0, 1], weights positive
+    (with pack's messages), range and duplicates; a two-asset pool that pack() put into 'cp2' takes no weights (unequal ones would move it
+    to another bucket: a re-upload), a 'w2' pool may take equal ones and stays where it is; raises ValueError.  Returns {bucket key: (positions
+    int32[count], fee [count] or None, w or None)}, positions ascending; w is slot-major [k][count] for a geo-mean bucket and the first
+    token's weight wa [count] for 'w2'.  An entry without a new fee (weights) in a bucket where another entry has one keeps its current."""
+    pools = [int(i) for i in pools]
+    for what, col in (("fees", fees), ("weight vectors", weights)):
+        if col is not None and len(col) != len(pools):
+            raise ValueError(f"{len(pools)} pools but {len(col)} {what}")
+    if len(set(pools)) != len(pools):
+        raise ValueError("a pool is named twice")
+    rows = {}
+    for e, i in enumerate(pools):
+        if not 0 <= i < len(where):
+            raise ValueError(f"pool {i}: outside [0, {len(where)})")
+        key, pos = where[i]
+        f = None if fees is None or fees[e] is None else float(fees[e])
+        if f is not None and not (0 < f <= 1):
+            raise ValueError(f"pool {i}: the fee must be in (0, 1], got {f!r}")
+        w = None if weights is None or weights[e] is None else np.asarray(weights[e], dtype=np.float64).ravel()
+        if w is not None:
+            if key == "cp2":
+                raise ValueError(f"pool {i}: a constant-product pool (bucket 'cp2': equal weights) holds no weight column; giving it unequal weights is a re-upload")
+            if key != "w2" and not isinstance(key, int):
+                raise ValueError(f"pool {i}: this kind of pool has no weights to update")
+            k = 2 if key == "w2" else key
+            if len(w) != k or not np.all(w > 0) or not np.all(np.isfinite(w)):
+                raise ValueError(f"pool {i}: bad weights")
+            w = w / w.sum()
+            if not np.all((w > 0) & (w < 1)):
+                raise ValueError(f"pool {i}: bad weights")
+        if f is not None or w is not None:
+            rows.setdefault(key, []).append((pos, f, w))
+    out = {}
+    for key, rr in rows.items():
+        rr.sort(key=lambda r: r[0])
+        b, fam = _bucket_of(net, key)
+        pos = np.array([r[0] for r in rr], dtype=np.int32)
+        fee = w = None
+        if any(r[1] is not None for r in rr):
+            fee = np.array([b["fee"][r[0]] if r[1] is None else r[1] for r in rr], dtype=np.float64)
+        if any(r[2] is not None for r in rr):
+            if key == "w2":
+                w = np.array([b["wa"][r[0]] if r[2] is None else r[2][0] for r in rr], dtype=np.float64)
+            else:
+                w = np.array([b["w"][:, r[0]] if r[2] is None else r[2] for r in rr], dtype=np.float64).T.copy()
+        out[key] = (pos, fee, w)
+    return out
+
+
 def post_trade_reserves(R, delta, lam, fee, fees="pool"):
     """Reserves of pools after their tenders are executed: R' = (R + g delta) - lam, every operation individually rounded -- the
     expression cfmm_apply_trades evaluates on the device (docs/apply_trades.md).  g = 1 with fees="pool" (the fee stays in the
@@ -476,6 +529,17 @@ def shard_updates(m, rank, world, positions, R, param=None):
     sel = (pos >= lo) & (pos < hi)
     R = np.asarray(R, dtype=np.float64)
     return pos[sel] - lo, R[:, sel], (None if param is None else np.asarray(param, dtype=np.float64)[sel])
+
+
+def shard_terms(m, rank, world, positions, fee=None, w=None):
+    """shard_updates for the per-pool columns of a terms update (Problem.update_bucket_terms): the entries given in GLOBAL positions
+    that fall in this rank's slice of a bucket of m pools, with positions local to it.  Every rank calls update_bucket_terms with its
+    part, an empty one included.  Returns (positions, fee [count] or None, w or None); w is [k][count] or, for 'w2', [count]."""
+    lo, hi = shard_range(m, rank, world)
+    pos = np.asarray(positions, dtype=np.int64).ravel()
+    sel = (pos >= lo) & (pos < hi)
+    return (pos[sel] - lo, None if fee is None else np.asarray(fee, dtype=np.float64)[sel],
+            None if w is None else np.asarray(w, dtype=np.float64)[..., sel])
 
 
 def shard_network(net, rank, world):
@@ -1115,8 +1179,8 @@ class Problem:
     def update_reserves(self, pools, reserves, params=None):
         """New reserves of some pools, written into the resident columns in place (nothing else is uploaded again): `pools` index the
         pool list the Problem was built from, reserves[i] is the new reserve vector of pools[i], params[i] the new alpha / t of a
-        curve / power-sum pool (None: unchanged).  Fees, weights and token ids stay (changing them is a new Problem).  The per-block loop
-        of a router:
+        curve / power-sum pool (None: unchanged).  Fees and weights have their own calls (update_fees, update_weights); token ids
+        stay (changing them, or adding / removing pools, is a new Problem).  The per-block loop of a router:
 
             p.solve()
             for block in blocks:
@@ -1176,6 +1240,74 @@ class Problem:
         if param is not None:
             cur[pos] = param
         self._reserves_changed()
+
+    # -- in-place updates of fees and weights (include/cfmm.h: cfmm_update_terms*) --------------
+    def update_fees(self, pools, fees):
+        """New fees of some pools (dynamic-fee pools), in place: `pools` index the pool list the Problem was built from."""
+        if self.where is None:
+            raise CfmmError("update_fees needs a Problem built from pool lists; use update_bucket_terms()")
+        for key, (pos, fee, w) in route_terms(self.net, self.where, pools, fees=fees).items():
+            self.update_bucket_terms(key, pos, fee, w)
+
+    def update_weights(self, pools, weights):
+        """New geo-mean exponents of some pools (liquidity-bootstrapping pools), in place; normalised as pack() does.  A two-asset pool
+        with equal weights lives in the constant-product bucket and has no weight column: giving it unequal weights is a new Problem."""
+        if self.where is None:
+            raise CfmmError("update_weights needs a Problem built from pool lists; use update_bucket_terms()")
+        for key, (pos, fee, w) in route_terms(self.net, self.where, pools, weights=weights).items():
+            self.update_bucket_terms(key, pos, fee, w)
+
+    def update_bucket_terms(self, key, positions, fee=None, w=None):
+        """New fees ([count], each in (0, 1]; None: unchanged) and / or weights (None: unchanged; [k][count] slot-major for a geo-mean
+        bucket, the first token's weight wa [count] for 'w2', each in (0, 1) and NOT normalised here: update_weights does that) of the
+        pools `positions` of one bucket, in place on the device and in self.net -- update_bucket's keys, sharing and pool-sharded rule
+        (local positions, every rank calls; shard_terms picks a rank's part)."""
+        b, fam = _bucket_of(self.net, key)
+        pos = np.ascontiguousarray(positions, dtype=np.int64).ravel()
+        m = len(b["Ra"]) if fam == "two" else b["R"].shape[1]
+        if len(pos) and (pos.min() < 0 or pos.max() >= m):
+            raise ValueError(f"bucket {key!r}: a position outside [0, {m})")
+        if len(np.unique(pos)) != len(pos):
+            raise ValueError(f"bucket {key!r}: a position is named twice")
+        if fee is None and w is None and len(pos):
+            raise ValueError(f"bucket {key!r}: neither fees nor weights given")
+        if fee is not None:
+            fee = np.ascontiguousarray(fee, dtype=np.float64).ravel()
+            if len(fee) != len(pos):
+                raise ValueError(f"bucket {key!r}: {len(pos)} positions but {len(fee)} fees")
+            if not np.all((fee > 0) & (fee <= 1)):
+                raise ValueError(f"bucket {key!r}: the fee must be in (0, 1]")
+        if w is not None:
+            if key != "w2" and fam != "gn":
+                raise ValueError(f"bucket {key!r}: no weights to update" + (" (unequal weights for a constant-product pool are a re-upload)" if key == "cp2" else ""))
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            shape = (len(pos),) if key == "w2" else (b["R"].shape[0], len(pos))
+            if w.size == 0 and len(pos) == 0:
+                w = w.reshape(shape)
+            if w.shape != shape:
+                raise ValueError(f"bucket {key!r}: weights of shape {w.shape}, expected {shape}")
+            if not np.all((w > 0) & (w < 1)):
+                raise ValueError(f"bucket {key!r}: weights must be in (0, 1)")
+        if self.ctx is not None and self._uploaded:
+            call = getattr(self.ctx, {"two": "update_terms2", "gn": "update_termsN", "gk": "update_termsG"}[fam], None)
+            if call is None:
+                raise CfmmError(f"this context ({getattr(self.ctx, 'backend', type(self.ctx).__name__)}) has no in-place update of fees and weights "
+                                "(cfmm_update_terms*): build a new Problem")
+            p32 = pos.astype(np.int32)
+            if fam == "two":
+                call(KIND2[key], p32, fee, w)
+            elif fam == "gn":
+                call(int(key), p32, fee, w)
+            else:
+                call(_lib.POOLK[key[0]], key[1], p32, fee)
+        if fee is not None:
+            b["fee"][pos] = fee
+        if w is not None:
+            if key == "w2":
+                b["wa"][pos] = w
+            else:
+                b["w"][:, pos] = w
+        self._reserves_changed()         # (the start-price relations, the kink fills and the trade cache depend on fees and weights too)
 
     def _reserves_changed(self):
         """what was derived from the old reserves goes: start-price relations (and the start prices memoised on them), the largest

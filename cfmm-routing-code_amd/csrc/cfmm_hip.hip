@@ -46,6 +46,7 @@
 #include "newton_rules.hpp"
 #include "sweep_rules.hpp"
 #include "route_rules.hpp"
+#include "update_rules.hpp"
 
 using namespace cfmm;
 
@@ -2654,7 +2655,7 @@ struct PoolEntry {
 struct Kind2Info { const char *name; bool needs_param; bool (*param_ok)(double); const char *param_rule; };
 static const Kind2Info kKind2[CFMM_POOL_KINDS2] = {
     {"constant product", false, nullptr, ""},
-    {"weighted geometric mean", true, [](double x) { return x > 0.0 && x < 1.0; }, "a weight in (0, 1)"},
+    {"weighted geometric mean", true, [](double x) { return terms::weight_ok(x); }, "a weight in (0, 1)"},
     {"constant sum", false, nullptr, ""},
     {"stableswap", true, [](double x) { return x > 0.0 && x <= std::numeric_limits<double>::max(); }, "alpha > 0"},
     {"power sum", true, [](double x) { return x >= 1e-3 && x <= 0.999; }, "an exponent t in [0.001, 0.999]"},
@@ -2705,7 +2706,7 @@ int cfmm_upload_pools2(cfmm_ctx *ctx, int kind, int64_t m, const double *Ra, con
         auto reserve_ok = [](double x) { return x > 0.0 && x <= std::numeric_limits<double>::max(); };
         cols.push_back(checked_col<double>(Ra, m, (void **)&b.Ra, &scan, 0, reserve_ok));
         cols.push_back(checked_col<double>(Rb, m, (void **)&b.Rb, &scan, 0, reserve_ok));
-        cols.push_back(checked_col<double>(fee, m, (void **)&b.fee, &scan, 1, [](double x) { return x > 0.0 && x <= 1.0; }));
+        cols.push_back(checked_col<double>(fee, m, (void **)&b.fee, &scan, 1, terms::fee_ok));
         if (param) {
             if (kKind2[kind].param_ok) cols.push_back(checked_col<double>(param, m, (void **)&b.param, &scan, 2, kKind2[kind].param_ok));
             else cols.push_back(plain_col(param, m * sizeof(double), (void **)&b.param));
@@ -2777,8 +2778,8 @@ int cfmm_upload_poolsN(cfmm_ctx *ctx, int k, int64_t m, const int32_t *idx, cons
         std::vector<Col> cols;
         cols.push_back(transposed_col<int32_t>(idx, k, m, (void **)&b.idx, &scan, false, [ntok](int32_t v) { return (uint32_t)v < (uint32_t)ntok; }));
         cols.push_back(transposed_col<double>(R, k, m, (void **)&b.R, &scan, true, [](double x) { return x > 0.0 && x <= std::numeric_limits<double>::max(); }));
-        cols.push_back(transposed_col<double>(w, k, m, (void **)&b.w, &scan, false, [](double x) { return x > 0.0 && x < 1.0; }));
-        cols.push_back(checked_col<double>(fee, m, (void **)&b.fee, &scan, 1, [](double x) { return x > 0.0 && x <= 1.0; }));
+        cols.push_back(transposed_col<double>(w, k, m, (void **)&b.w, &scan, false, terms::weight_ok));
+        cols.push_back(checked_col<double>(fee, m, (void **)&b.fee, &scan, 1, terms::fee_ok));
         {
             Col c; c.bytes = m * sizeof(double); c.dst = (void **)&b.lfee;
             c.fill = [fee](char *out, size_t off, size_t len) {
@@ -2838,7 +2839,7 @@ int cfmm_upload_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t m, const int32_t 
         std::vector<Col> cols;
         cols.push_back(transposed_col<int32_t>(idx, k, m, (void **)&b.idx, &scan, false, [ntok](int32_t v) { return (uint32_t)v < (uint32_t)ntok; }));
         cols.push_back(transposed_col<double>(R, k, m, (void **)&b.R, &scan, true, [](double x) { return x > 0.0 && x <= std::numeric_limits<double>::max(); }));
-        cols.push_back(checked_col<double>(fee, m, (void **)&b.fee, &scan, 1, [](double x) { return x > 0.0 && x <= 1.0; }));
+        cols.push_back(checked_col<double>(fee, m, (void **)&b.fee, &scan, 1, terms::fee_ok));
         if (param) cols.push_back(checked_col<double>(param, m, (void **)&b.param, &scan, 2, [](double x) { return x > 0.0 && x <= std::numeric_limits<double>::max(); }));
         // derived columns, reserved here and filled on the device behind the copies (phik.hpp: gk_derive_kernel): 1 / fee, the coupling
         // at the pool's own reserves, the evaluation tiles' warm start
@@ -2965,16 +2966,18 @@ extern "C++" template <class R> struct UpdateFrame {
         return update_check_positions(ctx, who, r.b.m, count, pos);
     }
 
+    // behind the work every sharer has enqueued: the scatter of the staged parts, complete on return.  `flag`: the scatter raised its
+    // flag (the recorded extremum was overwritten towards the inside), and then `word` is what reduce() left of the bucket
     template <class Launch, class Reduce>
-    int run(const std::vector<UpdPart> &parts, const int *perm, double mx_new, int64_t count, Launch &&launch, Reduce &&reduce)
+    int scatter(const std::vector<UpdPart> &parts, const int *perm, int64_t count, Launch &&launch, Reduce &&reduce, bool &flag, unsigned long long &word)
     {
         const int64_t m = r.b.m;
+        flag = false; word = 0ull;
         for (cfmm_ctx *s : entry.ps.sharers) {
             if (s == ctx) continue;
             HIP_TRY(ctx, hipEventRecord(s->ev_pool, s->stream));
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s->ev_pool, 0));
         }
-        double mx = std::max(r.mxr, mx_new);
         if (count > 0) {
             if (perm && !r.inv) {
                 HIP_TRY(ctx, hipMalloc((void **)&r.inv, (size_t)m * sizeof(int) + 16));
@@ -2983,24 +2986,49 @@ extern "C++" template <class R> struct UpdateFrame {
             }
             std::vector<size_t> offs;
             { int rc = update_stage(ctx, parts, offs); if (rc) return rc; }
-            int *lowered = (int *)ctx->upd_dev;
-            launch(ctx->upd_dev, offs, perm ? r.inv : nullptr, lowered);
+            int *raised = (int *)ctx->upd_dev;
+            launch(ctx->upd_dev, offs, perm ? r.inv : nullptr, raised);
             HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->upd_host, lowered, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->upd_host, raised, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (*(const int *)ctx->upd_host) {                 // a reserve equal to the bucket's maximum went down: reduce the bucket again
+            if (*(const int *)ctx->upd_host) {                 // the value that held the bucket's extremum moved inwards: reduce the bucket again
                 unsigned long long *out = (unsigned long long *)(ctx->upd_dev + 64);
                 reduce(out);
                 HIP_TRY(ctx, hipGetLastError());
                 HIP_TRY(ctx, hipMemcpyAsync(ctx->upd_host, out, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
                 HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                double d; std::memcpy(&d, ctx->upd_host, sizeof d);
-                mx = std::max(d, mx_new);
+                flag = true; word = *ctx->upd_host;
             }
         } else {
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         }
+        return CFMM_OK;
+    }
+
+    // reserves: reduce(out) leaves the bit pattern of the bucket's largest reserve
+    template <class Launch, class Reduce>
+    int run(const std::vector<UpdPart> &parts, const int *perm, double mx_new, int64_t count, Launch &&launch, Reduce &&reduce)
+    {
+        bool lowered; unsigned long long word;
+        { int rc = scatter(parts, perm, count, launch, reduce, lowered, word); if (rc) return rc; }
+        double mx = std::max(r.mxr, mx_new);
+        if (lowered) {                                         // a reserve equal to the bucket's maximum went down
+            double d; std::memcpy(&d, &word, sizeof d);
+            mx = std::max(d, mx_new);
+        }
         r.mxr = mx;
+        entry.ps.gen.fetch_add(1, std::memory_order_acq_rel);
+        return CFMM_OK;
+    }
+
+    // fees and weights: mn_new the smallest new fee (1 without fees); reduce(out) leaves the fee column's smallest entry as
+    // update_rules.hpp: fee_from_reduced reads it
+    template <class Launch, class Reduce>
+    int run_terms(const std::vector<UpdPart> &parts, const int *perm, double mn_new, int64_t count, Launch &&launch, Reduce &&reduce)
+    {
+        bool raised; unsigned long long word;
+        { int rc = scatter(parts, perm, count, launch, reduce, raised, word); if (rc) return rc; }
+        r.mnf = terms::min_fee_after(r.mnf, raised, mn_new, raised ? terms::fee_from_reduced(word) : 1.0);
         entry.ps.gen.fetch_add(1, std::memory_order_acq_rel);
         return CFMM_OK;
     }
@@ -3099,6 +3127,129 @@ int cfmm_update_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t count, const int3
         },
         [&](unsigned long long *out) {
             hipLaunchKernelGGL(upd_max_kernel, dim3(max_grid((int64_t)k * m)), dim3(UP_THREADS), 0, ctx->stream, b.R, (long long)k * m, (const double *)nullptr, 0ll, out);
+        });
+}
+
+// ---- in-place updates of resident pools' trading terms: fees and weights (update.hpp; the host decisions: update_rules.hpp) ----------
+// The frame of the reserve updates.  What an upload derives from a fee or a weight is made the way the upload makes it: log fee of the
+// geo-mean pools on the HOST while staging (the upload's column is std::log's), log(R / w) and 1 / fee on the device, the host copy of
+// the constant-sum bucket's fees, the bucket's smallest fee (update_rules.hpp: min_fee_after); a two-asset bucket's compact mirror is
+// dropped and built again by the next call that reads the pools (update_rules.hpp: mirror_reset).
+namespace {
+// fee[count] (or NULL): every entry a fee an upload takes; the smallest through mn
+int update_check_fees(cfmm_ctx *ctx, const char *who, const double *fee, int64_t count, double &mn)
+{
+    if (!fee) return CFMM_OK;
+    const int64_t bad = terms::first_bad(fee, count, terms::fee_ok, &mn);
+    return bad < 0 ? CFMM_OK : fail(ctx, CFMM_E_ARG, "%s: entry %lld has fee %g outside (0, 1]", who, (long long)bad, fee[bad]);
+}
+int update_check_weights(cfmm_ctx *ctx, const char *who, const double *w, int64_t cnt)
+{
+    if (!w) return CFMM_OK;
+    const int64_t bad = terms::first_bad(w, cnt, terms::weight_ok);
+    return bad < 0 ? CFMM_OK : fail(ctx, CFMM_E_ARG, "%s: weight %lld is %g, outside (0, 1)", who, (long long)bad, w[bad]);
+}
+}  // namespace
+
+int cfmm_update_terms2(cfmm_ctx *ctx, int kind, int64_t count, const int32_t *pos, const double *fee, const double *wa)
+{
+    const char *who = "update_terms2";
+    if (!ctx) return CFMM_E_ARG;
+    if (kind < 0 || kind >= CFMM_POOL_KINDS2 || count < 0) return fail(ctx, CFMM_E_ARG, "%s: kind %d, count %lld", who, kind, (long long)count);
+    if (wa && kind != CFMM_POOL_W2) return fail(ctx, CFMM_E_ARG, "%s: kind %d (%s) has no weight", who, kind, kKind2[kind].name);
+    if (count > 0 && !pos) return fail(ctx, CFMM_E_ARG, "%s: NULL positions", who);
+    if (count > 0 && !fee && !wa) return fail(ctx, CFMM_E_ARG, "%s: neither fees nor weights given", who);
+    UpdateFrame f(ctx, who, ctx->pools->r2[kind]);
+    { int rc = f.open(count, pos, [&] { return fail(ctx, CFMM_E_STATE, "%s: no %s pools uploaded", who, kKind2[kind].name); }); if (rc) return rc; }
+    double mn_new = 1.0;
+    { int rc = update_check_fees(ctx, who, fee, count, mn_new); if (rc) return rc; }
+    { int rc = update_check_weights(ctx, who, wa, count); if (rc) return rc; }
+    const Bucket2 b = f.r.b;
+    const int64_t m = b.m;
+    const double mn_old = f.r.mnf;
+    std::vector<UpdPart> parts = {{pos, (size_t)count * 4}};
+    if (fee) parts.push_back({fee, (size_t)count * 8});
+    if (wa) parts.push_back({wa, (size_t)count * 8});
+    const int cnt = (int)count;
+    int rc = f.run_terms(parts, b.perm, mn_new, count,
+        [&](const char *d, const std::vector<size_t> &o, const int *inv, int *raised) {
+            hipLaunchKernelGGL(upd_terms2_kernel, dim3(upd_grid(count)), dim3(UP_THREADS), 0, ctx->stream, b, cnt, (const int *)(d + o[0]),
+                               fee ? (const double *)(d + o[1]) : nullptr, wa ? (const double *)(d + o[fee ? 2 : 1]) : nullptr, inv, mn_old, raised);
+        },
+        [&](unsigned long long *out) {
+            hipLaunchKernelGGL(upd_min_kernel, dim3(max_grid(m)), dim3(UP_THREADS), 0, ctx->stream, b.fee, (long long)m, out);
+        });
+    if (rc) return rc;
+    Resident2 &r = f.r;
+    if (terms::mirror_reset(r.ctried, fee != nullptr, count)) {
+        // (the stream is drained behind the waits on every sharer's work, no context reads the store, and every context rebuilds its
+        //  launch arguments from the record behind the generation bump: nothing holds the mirror's addresses any more)
+        if (r.cmem) (void)hipFree(r.cmem);
+        r.cmem = nullptr; r.ctried = false;
+        r.b.cid = nullptr; r.b.cfee = nullptr; r.b.ctab = nullptr;
+    }
+    PoolStore &ps = *ctx->pools;
+    if (fee && kind == CFMM_POOL_SUM2 && (int64_t)ps.hs_fee.size() == m)
+        for (int64_t i = 0; i < count; ++i) ps.hs_fee[pos[i]] = fee[i];
+    return CFMM_OK;
+}
+
+int cfmm_update_termsN(cfmm_ctx *ctx, int k, int64_t count, const int32_t *pos, const double *fee, const double *w)
+{
+    const char *who = "update_termsN";
+    if (!ctx) return CFMM_E_ARG;
+    if (k < 3 || k > CFMM_MAX_POOL_SIZE || count < 0) return fail(ctx, CFMM_E_ARG, "%s: pool size %d outside 3..%d, or count %lld", who, k, CFMM_MAX_POOL_SIZE, (long long)count);
+    if (count > 0 && !pos) return fail(ctx, CFMM_E_ARG, "%s: NULL positions", who);
+    if (count > 0 && !fee && !w) return fail(ctx, CFMM_E_ARG, "%s: neither fees nor weights given", who);
+    UpdateFrame f(ctx, who, ctx->pools->rn[k]);
+    { int rc = f.open(count, pos, [&] { return fail(ctx, CFMM_E_STATE, "%s: no geo-mean pools of %d assets uploaded", who, k); }); if (rc) return rc; }
+    double mn_new = 1.0;
+    { int rc = update_check_fees(ctx, who, fee, count, mn_new); if (rc) return rc; }
+    { int rc = update_check_weights(ctx, who, w, (int64_t)k * count); if (rc) return rc; }
+    std::vector<double> lfee;                              // log fee, by the host's std::log as the upload's staging forms it
+    if (fee) { lfee.resize((size_t)count); for (int64_t i = 0; i < count; ++i) lfee[(size_t)i] = std::log(fee[i]); }
+    const BucketN b = f.r.b;
+    const int64_t m = b.m;
+    const double mn_old = f.r.mnf;
+    std::vector<UpdPart> parts = {{pos, (size_t)count * 4}};
+    if (fee) { parts.push_back({fee, (size_t)count * 8}); parts.push_back({lfee.data(), (size_t)count * 8}); }
+    if (w) parts.push_back({w, (size_t)count * k * 8});
+    const int cnt = (int)count;
+    return f.run_terms(parts, b.perm, mn_new, count,
+        [&](const char *d, const std::vector<size_t> &o, const int *inv, int *raised) {
+            hipLaunchKernelGGL(upd_termsN_kernel, dim3(upd_grid(count)), dim3(UP_THREADS), 0, ctx->stream, b, k, cnt, (const int *)(d + o[0]),
+                               fee ? (const double *)(d + o[1]) : nullptr, fee ? (const double *)(d + o[2]) : nullptr,
+                               w ? (const double *)(d + o[fee ? 3 : 1]) : nullptr, inv, mn_old, raised);
+        },
+        [&](unsigned long long *out) {
+            hipLaunchKernelGGL(upd_min_kernel, dim3(max_grid(m)), dim3(UP_THREADS), 0, ctx->stream, b.fee, (long long)m, out);
+        });
+}
+
+int cfmm_update_termsG(cfmm_ctx *ctx, int kind, int k, int64_t count, const int32_t *pos, const double *fee)
+{
+    const char *who = "update_termsG";
+    if (!ctx) return CFMM_E_ARG;
+    if (kind < 0 || kind >= CFMM_POOLK_KINDS || k < 2 || k > CFMM_MAX_POOL_SIZE || count < 0)
+        return fail(ctx, CFMM_E_ARG, "%s: kind %d, %d assets, count %lld", who, kind, k, (long long)count);
+    if (count > 0 && !pos) return fail(ctx, CFMM_E_ARG, "%s: NULL positions", who);
+    if (count > 0 && !fee) return fail(ctx, CFMM_E_ARG, "%s: no fees given", who);
+    UpdateFrame f(ctx, who, ctx->pools->rg[kind][k]);
+    { int rc = f.open(count, pos, [&] { return fail(ctx, CFMM_E_STATE, "%s: no pools of kind %d with %d assets uploaded", who, kind, k); }); if (rc) return rc; }
+    double mn_new = 1.0;
+    { int rc = update_check_fees(ctx, who, fee, count, mn_new); if (rc) return rc; }
+    const BucketG b = f.r.b;
+    const int64_t m = b.m;
+    const double mn_old = f.r.mnf;
+    const std::vector<UpdPart> parts = {{pos, (size_t)count * 4}, {fee, (size_t)count * 8}};
+    const int cnt = (int)count;
+    return f.run_terms(parts, nullptr, mn_new, count,
+        [&](const char *d, const std::vector<size_t> &o, const int *, int *raised) {
+            hipLaunchKernelGGL(upd_termsG_kernel, dim3(upd_grid(count)), dim3(UP_THREADS), 0, ctx->stream, b, cnt, (const int *)(d + o[0]),
+                               (const double *)(d + o[1]), mn_old, raised);
+        },
+        [&](unsigned long long *out) {
+            hipLaunchKernelGGL(upd_min_kernel, dim3(max_grid(m)), dim3(UP_THREADS), 0, ctx->stream, b.fee, (long long)m, out);
         });
 }
 

@@ -112,4 +112,95 @@ upd_max_kernel(const double *__restrict__ a, long long na, const double *__restr
     }
 }
 
+// ---- the trading TERMS of resident pools: the fee, and the weights where the family has them (cfmm_update_terms2 / N / G) ----------
+// The same frame: one launch per call scatters the staged records and rewrites what the upload derives from a fee or a weight.  The
+// bucket's SMALLEST fee fixes the reproducible mode's exponent like the largest reserve does: every scatter reads the fee it
+// overwrites and sets `raised` when a fee equal to the recorded minimum `mn` goes up -- only then is the fee column reduced again
+// (upd_min_kernel; update_rules.hpp: min_fee_after).
+
+// two-asset bucket: pos[count], fee[count] or null, wa[count] or null (CFMM_POOL_W2's param column)
+__global__ void __launch_bounds__(UP_THREADS)
+upd_terms2_kernel(Bucket2 b, int count, const int *__restrict__ pos, const double *__restrict__ fee, const double *__restrict__ wa,
+                  const int *__restrict__ inv, double mn, int *__restrict__ raised)
+{
+    const int i = blockIdx.x * UP_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const int q = pos[i];
+    const long long p = inv ? inv[q] : q;
+    if (fee) {
+        double *f = const_cast<double *>(b.fee);
+        const double o = f[p], v = fee[i];
+        if (o == mn && v > o) *raised = 1;
+        f[p] = v;
+    }
+    if (wa) const_cast<double *>(b.param)[p] = wa[i];
+}
+
+// geo-mean bucket of K assets: fee[count] and lfee[count] = log fee as the HOST forms it (the upload's column is the host's std::log),
+// or null; w slot-major [K][count] or null -> pool-major legs, + lrw = log(R / w) per leg from the resident reserve
+__global__ void __launch_bounds__(UP_THREADS)
+upd_termsN_kernel(BucketN b, int K, int count, const int *__restrict__ pos, const double *__restrict__ fee, const double *__restrict__ lfee,
+                  const double *__restrict__ w, const int *__restrict__ inv, double mn, int *__restrict__ raised)
+{
+    const int i = blockIdx.x * UP_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const int q = pos[i];
+    const long long p = inv ? inv[q] : q;
+    if (fee) {
+        double *f = const_cast<double *>(b.fee);
+        const double o = f[p], v = fee[i];
+        if (o == mn && v > o) *raised = 1;
+        f[p] = v;
+        const_cast<double *>(b.lfee)[p] = lfee[i];
+    }
+    if (w) {
+        double *bw = const_cast<double *>(b.w), *lrw = const_cast<double *>(b.lrw);
+        for (int j = 0; j < K; ++j) {
+            const long long leg = p * K + j;
+            const double v = w[(long long)j * count + i];
+            bw[leg] = v;
+            lrw[leg] = lrw_leg(b.R[leg], v);
+        }
+    }
+}
+
+// K-asset table bucket (never permuted): fee[count]; + 1 / fee (phik.hpp: gk_derive_kernel's expression), and the evaluation tiles'
+// warm start of the updated pool dropped (NaN, as at upload and as the reserve update does)
+__global__ void __launch_bounds__(UP_THREADS)
+upd_termsG_kernel(BucketG b, int count, const int *__restrict__ pos, const double *__restrict__ fee, double mn, int *__restrict__ raised)
+{
+    const int i = blockIdx.x * UP_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const long long p = pos[i];
+    double *f = const_cast<double *>(b.fee);
+    const double o = f[p], v = fee[i];
+    if (o == mn && v > o) *raised = 1;
+    f[p] = v;
+    const_cast<double *>(b.ifee)[p] = 1.0 / v;
+    b.ws[p] = __builtin_nan("");
+}
+
+// smallest value of a[0 .. n) (positive doubles) into *out as the COMPLEMENT of its bit pattern: *out is zeroed first, and the largest
+// complement is the smallest value (update_rules.hpp: fee_from_reduced)
+__global__ void __launch_bounds__(UP_THREADS) upd_min_kernel(const double *__restrict__ a, long long n, unsigned long long *__restrict__ out)
+{
+    __shared__ unsigned long long part[UP_THREADS / 64];
+    const long long stride = (long long)gridDim.x * UP_THREADS;
+    unsigned long long mx = 0ull;
+    for (long long i = (long long)blockIdx.x * UP_THREADS + threadIdx.x; i < n; i += stride) {
+        const unsigned long long v = ~(unsigned long long)__double_as_longlong(a[i]);
+        mx = v > mx ? v : mx;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long v = __shfl_xor(mx, o, 64);
+        mx = v > mx ? v : mx;
+    }
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < UP_THREADS / 64; ++w) mx = part[w] > mx ? part[w] : mx;
+        atomicMax(out, mx);
+    }
+}
+
 }  // namespace cfmm

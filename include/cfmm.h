@@ -138,7 +138,8 @@ int cfmm_destroy(cfmm_ctx *ctx);
  * no copy) but has its own stream, utility, prices and solver state: several solves over one pool set --
  * the parameter sweep of two-asset.py:34-100, or independent utilities -- can then be in flight at once
  * (one per host thread), one solve's single-workgroup nu update overlapping another's evaluation kernels.
- * Pools cannot be re-uploaded while clones exist; their reserves can be updated in place through any of them (cfmm_update_pools*). */
+ * Pools cannot be re-uploaded while clones exist; their reserves, fees and weights can be updated in place through any of them
+ * (cfmm_update_pools*, cfmm_update_terms*). */
 int cfmm_clone(cfmm_ctx *src, cfmm_ctx **out);
 const char *cfmm_last_error(cfmm_ctx *ctx);       /* ctx may be NULL: last error of cfmm_create */
 const char *cfmm_backend(cfmm_ctx *ctx);          /* "hip:gfx950"                               */
@@ -168,8 +169,8 @@ int cfmm_upload_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t m, const int32_t 
  *   pos[count]    the pools, by their index in the order the bucket was uploaded (the index cfmm_get_trades* reports in), not by the
  *                 position the library stores them at (large buckets are reordered on the device: the update maps through the inverse)
  *   Ra, Rb        [count];  R: slot-major [k][count], like the uploads
- * Fees, weights (of the two-asset weighted pools too) and token ids can NOT be updated (the ids decide the reordering, the fees the compact
- * mirror, log fee, 1 / fee and the smallest fee, the weights log(R / w)): changing one of them, or adding / removing pools, is a re-upload.
+ * Fees and weights are updated by cfmm_update_terms2 / N / G below (cfmm_update_pools2 keeps refusing a CFMM_POOL_W2 parameter).  Token
+ * ids can NOT be updated (they decide the reordering): changing them, or adding / removing pools, is a re-upload.
  * Rules:
  *   - everything is checked before anything is written: a position outside [0, m) or named twice, a reserve that is not positive and
  *     finite, a parameter the bucket's upload refuses (the same rule) -> CFMM_E_ARG and the pools are left bit for bit as they were;
@@ -189,6 +190,35 @@ int cfmm_update_pools2(cfmm_ctx *ctx, int kind, int64_t count, const int32_t *po
 int cfmm_update_poolsN(cfmm_ctx *ctx, int k, int64_t count, const int32_t *pos, const double *R /* [k][count] */);
 int cfmm_update_poolsG(cfmm_ctx *ctx, int kind, int k, int64_t count, const int32_t *pos,
                        const double *R /* [k][count] */, const double *param /* NULL = unchanged */);
+/* The trading TERMS of resident pools, in place: the fee, and the weights where the family has them (dynamic-fee pools; liquidity-
+ * bootstrapping pools, whose weights move every block).  Writes the new fee / weights of `count` pools of ONE bucket into the columns in
+ * HBM and remakes what the upload derives from them, the way the upload makes it: log fee of the geo-mean pools (on the host, as the
+ * upload does), log(R / w) of every leg of a pool whose weights are given, 1 / fee of the table's pools (their root-search warm start is
+ * dropped), the host copy of the constant-sum bucket's fees that CFMM_METHOD_AUTO's kink loop reads, and the bucket's smallest fee
+ * (exact, what a fresh upload would record: the reproducible mode's fixed-point exponent, cfmm_audit's fixed_exponent).  An updated pool
+ * is bitwise the pool a fresh upload would have made.  The compact mirror of a large two-asset bucket indexes a table of the bucket's
+ * distinct fees: a fee update drops it and the next call that reads the pools builds it again from the new column, so that it is
+ * present exactly when a fresh upload would have it (at most 256 distinct fees).
+ *   pos[count]    as for cfmm_update_pools*: upload order, mapped through the inverse of the reordering
+ *   fee           [count], each in (0, 1], or NULL = unchanged (cfmm_update_termsG has nothing else to take: NULL with count > 0 is refused)
+ *   wa            [count], each in (0, 1), CFMM_POOL_W2 only (any other kind: CFMM_E_ARG), or NULL = unchanged
+ *   w             slot-major [k][count] like the upload's, each in (0, 1), or NULL = unchanged.  The library normalises weights no more
+ *                 than the upload does: a pool's weights summing to 1 is the caller's duty
+ * The contract is that of cfmm_update_pools*:
+ *   - everything is checked before anything is written: a position outside [0, m) or named twice, a fee or weight the upload refuses
+ *     (the same predicates), both value pointers NULL with count > 0 -> CFMM_E_ARG and the pools are left bit for bit as they were;
+ *     count > 0 on an empty bucket -> CFMM_E_STATE, a k without a bucket -> CFMM_E_ARG; count == 0 is legal;
+ *   - shared with every cfmm_clone, ordered behind all work enqueued on every context of the set, complete on return, CFMM_E_STATE while
+ *     another context of the set is inside a solve, evaluation, batch or read-back; every context notices on its next call and drops
+ *     what it drops after a reserve update (cached solution, kink tenders, barrier warm start, the extrema, captured launches) but keeps
+ *     its prices, utility, ties and tie flags.  Price ties the CALLER formed from an old fee (cfmm_set_ties with an offset of
+ *     +- log gamma of a constant-sum pool) are the caller's to refresh;
+ *   - pool-sharded contexts: positions local to the rank's shard, and EVERY rank makes the call (count = 0 where it has nothing). */
+int cfmm_update_terms2(cfmm_ctx *ctx, int kind, int64_t count, const int32_t *pos,
+                       const double *fee /* [count] or NULL = unchanged */, const double *wa /* [count] or NULL; CFMM_POOL_W2 only */);
+int cfmm_update_termsN(cfmm_ctx *ctx, int k, int64_t count, const int32_t *pos,
+                       const double *fee /* [count] or NULL */, const double *w /* [k][count] slot-major or NULL */);
+int cfmm_update_termsG(cfmm_ctx *ctx, int kind, int k, int64_t count, const int32_t *pos, const double *fee /* [count] */);
 /* The router's own trades applied to the resident pools, on the device (docs/apply_trades.md): commits exactly the tenders
  * cfmm_get_trades2 / N / G would return at the moment of the call -- every bucket, at the context's accepted prices: the exact pool
  * solutions after a first-order solve or cfmm_set_nu, the gross smoothed tenders after a second-order solve (a leg may both receive and
