@@ -1412,7 +1412,7 @@ int hess_nr(int n) { return (n + 2 * CH_NB - 1) / (2 * CH_NB) * (2 * CH_NB); }  
 int hess_ld(int n) { return hess_nr(n) + CH_NB; }                   // + the block row that carries the right-hand side
 
 // in-place Cholesky of the lower triangle of ctx->H with the right-hand side in row nr (chol.hpp), then the back
-// substitution into `x`; *sm_info (device) = 0 or 1 + the first block column with a non-positive pivot
+// substitution into `x`; *sm_info (device) = 0, or non-zero: not positive definite (a pivot <= 0, NaN or +inf) -- NOT a position: the kernels take atomicMax(column + 1) and a failed pivot makes NaN of everything behind it
 int launch_factor(cfmm_ctx *ctx, int n, bool info_zeroed = false)
 {
     const int nr = hess_nr(n), ld = hess_ld(n), nrows = nr + 1, nbk = nr / CH_NB;

@@ -333,7 +333,10 @@ int cfmm_eval_dual(cfmm_ctx *ctx, const double *nu, double *arb_sum, double *psi
 int cfmm_eval_smooth(cfmm_ctx *ctx, const double *nu, double mu, double *value, double *trade, double *psi, double *H);
 
 /* test hook: the dense Cholesky solve of the second-order method on a caller-supplied SPD system (A: n x n
- * column-major, lower triangle read; n must equal the context's token count); *info != 0 flags a non-positive pivot */
+ * column-major, ONLY the lower triangle read: what lies above may be zero, the mirror image or anything else; n must
+ * equal the context's token count).  *info = 0, or non-zero: A is not positive definite (a pivot <= 0, NaN or +inf met);
+ * the value is not a position (everything behind a failed pivot is NaN and flags too), and x is then meaningless.  A
+ * failed call leaves the context fit for the next one. */
 int cfmm_debug_cholesky(cfmm_ctx *ctx, int n, const double *A, const double *b, double *x, int32_t *info);
 /* test hook: x = A^-1 b for a NEW right-hand side through the factor and inverse factor the last cfmm_debug_cholesky left
  * (the two matrix-vector products of the second-order iteration's chord steps) */

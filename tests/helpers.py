@@ -90,6 +90,26 @@ def normalise_with_params(inst):
     return out
 
 
+def mixed_network(seed=0, n=60, m=1500):
+    """every two-asset family (m pools each), constant-sum pools between equal-priced tokens of a peg group"""
+    net = _syn.make_network(n, m_cp2=m, m_w2=m, m_curve2=m, seed=seed)
+    rng = np.random.default_rng(seed + 99)
+    ms = m // 2
+    ia = rng.integers(0, n, ms); ib = (ia // 4) * 4 + (ia % 4 + rng.integers(1, 4, ms)) % 4
+    ib = np.minimum(ib, n - 1); ib = np.where(ib == ia, (ia // 4) * 4, ib)
+    keep = ia != ib
+    ia, ib = ia[keep].astype(np.int32), ib[keep].astype(np.int32)
+    L = np.exp(rng.normal(np.log(1e3), 1.0, len(ia)))
+    net["sum2"] = dict(Ra=L / net["prices"][ia], Rb=L / net["prices"][ia] * np.exp(rng.normal(0, 0.05, len(ia))),
+                       fee=np.full(len(ia), 0.999), ia=ia, ib=ib)
+    return net
+
+
+def smoothed_hessian_point(net, seed=5):
+    """the prices at which the dense-solve tests take a smoothed Hessian of `net` (3 % off the market)"""
+    return net["prices"] * np.exp(np.random.default_rng(seed).normal(0, 0.03, net["n_tokens"]))
+
+
 def table_instance(seed):
     """small instance with K-asset table pools (n-asset stableswap over 2..5 tokens; 40 %: an n-asset constant-sum pool over tokens of
     clearly different value) among constant-product pools, one of the reference's three utilities by seed: tools/fuzz_table.py's generator"""
