@@ -69,6 +69,36 @@ class Audit(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+BUCKET_SLOTS = 32                      # include/cfmm.h: CFMM_BUCKET_SLOTS
+
+
+def bucket_slot(key):
+    """the slot of a bucket in cfmm_select_info's per-slot arrays (include/cfmm.h): key = a two-asset kind (int), ("gn", k) for the
+    geo-mean bucket of k assets, or ("table", kind, k) for the K-asset table's bucket"""
+    if isinstance(key, tuple) and key[0] == "gn":
+        return 5 + int(key[1])
+    if isinstance(key, tuple) and key[0] == "table":
+        return 5 + (MAX_POOL_SIZE + 1) * (1 + int(key[1])) + int(key[2])
+    return int(key)
+
+
+class SelectInfo(C.Structure):
+    """cfmm_select_info: what cfmm_select_pools selected, per bucket slot and in total (docs/subnetwork.md)"""
+    _fields_ = [("pools", C.c_int64), ("selected", C.c_int64), ("non_finite", C.c_int64),
+                ("value_in_total", C.c_double), ("value_in_selected", C.c_double),
+                ("slot_pools", C.c_int64 * BUCKET_SLOTS), ("slot_selected", C.c_int64 * BUCKET_SLOTS)]
+
+    def asdict(self):
+        out = {k: getattr(self, k) for k, _ in self._fields_[:5]}
+        out["slot_pools"], out["slot_selected"] = list(self.slot_pools), list(self.slot_selected)
+        return out
+
+
+class PoolLists(C.Structure):
+    """cfmm_pool_lists: per bucket slot the upload-order positions cfmm_subnetwork takes"""
+    _fields_ = [("pos", C.POINTER(C.c_int32) * BUCKET_SLOTS), ("count", C.c_int64 * BUCKET_SLOTS)]
+
+
 class Stats(C.Structure):
     _fields_ = [("evals", C.c_int32), ("iters", C.c_int32), ("status", C.c_int32), ("n_ranks", C.c_int32),
                 ("dual_value", C.c_double), ("primal_value", C.c_double), ("gap", C.c_double),
@@ -88,7 +118,7 @@ assert _STATS_STRUCT.size == C.sizeof(Stats)
 
 def build(force=False):
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp", "update.hpp", "apply.hpp", "audit.hpp", "solve_plan.hpp", "newton_rules.hpp", "sweep_rules.hpp", "route_rules.hpp", "update_rules.hpp", "tiny_limits.hpp", "fixedpoint.hpp")]
+    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp", "update.hpp", "apply.hpp", "audit.hpp", "solve_plan.hpp", "newton_rules.hpp", "sweep_rules.hpp", "route_rules.hpp", "update_rules.hpp", "subset.hpp", "subset_rules.hpp", "tiny_limits.hpp", "fixedpoint.hpp")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "cfmm.h"))
     if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _CSRC, "-s"])
@@ -100,7 +130,7 @@ _lib = None
 SYMBOLS = ["cfmm_create", "cfmm_clone", "cfmm_destroy", "cfmm_last_error", "cfmm_backend", "cfmm_default_opts",
            "cfmm_upload_pools2", "cfmm_upload_poolsN", "cfmm_upload_poolsG", "cfmm_update_pools2", "cfmm_update_poolsN", "cfmm_update_poolsG",
            "cfmm_update_terms2", "cfmm_update_termsN", "cfmm_update_termsG",
-           "cfmm_apply_trades", "cfmm_get_reserves2", "cfmm_get_reservesN", "cfmm_get_reservesG", "cfmm_apply_timers", "cfmm_audit_trades", "cfmm_debug_audit_launch", "cfmm_set_pool_flags", "cfmm_set_pool_flagsG", "cfmm_set_utility",
+           "cfmm_apply_trades", "cfmm_get_reserves2", "cfmm_get_reservesN", "cfmm_get_reservesG", "cfmm_apply_timers", "cfmm_audit_trades", "cfmm_debug_audit_launch", "cfmm_select_pools", "cfmm_get_selected2", "cfmm_get_selectedN", "cfmm_get_selectedG", "cfmm_subnetwork", "cfmm_set_pool_flags", "cfmm_set_pool_flagsG", "cfmm_set_utility",
            "cfmm_set_ties", "cfmm_set_deterministic", "cfmm_debug_eval_limbs", "cfmm_debug_scatter_limbs", "cfmm_eval_dual", "cfmm_eval_smooth", "cfmm_debug_cholesky", "cfmm_debug_cholesky_apply", "cfmm_time_xcd_handoff", "cfmm_solve", "cfmm_solve_batch", "cfmm_eval_dual_batch", "cfmm_batch_capacity", "cfmm_solve_sweep", "cfmm_get_nu", "cfmm_set_nu", "cfmm_get_psi",
            "cfmm_get_solution", "cfmm_get_trades2", "cfmm_get_tradesN", "cfmm_get_tradesG", "cfmm_comm_unique_id", "cfmm_comm_init",
            "cfmm_oneshot_export", "cfmm_oneshot_import", "cfmm_oneshot_attach", "cfmm_oneshot_mailbox", "cfmm_oneshot_enable",
@@ -139,6 +169,11 @@ def lib():
     L.cfmm_apply_timers.argtypes = [vp, C.c_int, dp]
     L.cfmm_audit_trades.argtypes = [vp, C.POINTER(AuditTenders), C.c_double, C.POINTER(Audit), dp, C.POINTER(C.c_uint64)]
     L.cfmm_debug_audit_launch.argtypes = [vp, C.c_int, C.c_int, dp]
+    L.cfmm_select_pools.argtypes = [vp, C.c_double, C.POINTER(SelectInfo)]
+    L.cfmm_get_selected2.argtypes = [vp, C.c_int, ip, C.c_int64, C.POINTER(C.c_int64)]
+    L.cfmm_get_selectedN.argtypes = [vp, C.c_int, ip, C.c_int64, C.POINTER(C.c_int64)]
+    L.cfmm_get_selectedG.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int64, C.POINTER(C.c_int64)]
+    L.cfmm_subnetwork.argtypes = [vp, C.POINTER(PoolLists), C.POINTER(vp)]
     L.cfmm_set_pool_flags.argtypes = [vp, C.c_int, ip]
     L.cfmm_set_pool_flagsG.argtypes = [vp, C.c_int, ip]
     L.cfmm_set_utility.argtypes = [vp, dp, dp, ip]
@@ -362,6 +397,58 @@ class Context:
             return int(rc), out
         self._chk(rc)
         return out
+
+    def select_pools(self, min_value_in=0.0, check=True):
+        """cfmm_select_pools: select the pools whose value taken in at the accepted prices, v = sum_j nu_j Delta_j on the tenders
+        get_trades* would return now, exceeds min_value_in (docs/subnetwork.md).  Returns the info record as a dict; check=False:
+        (return code, dict) instead of raising on a refusal"""
+        info = SelectInfo()
+        rc = self.L.cfmm_select_pools(self.h, float(min_value_in), C.byref(info))
+        if not check:
+            return int(rc), info.asdict()
+        self._chk(rc)
+        return info.asdict()
+
+    def _selected(self, call, cap):
+        cnt = C.c_int64(0)
+        if cap is None:                                  # the count first, then exactly that many
+            self._chk(call(None, 0, C.byref(cnt)))
+            cap = cnt.value
+        idx = np.zeros(max(int(cap), 0), dtype=np.int32)
+        self._chk(call(_i(idx) if len(idx) else None, len(idx), C.byref(cnt)))
+        return idx[:min(cnt.value, len(idx))], int(cnt.value)
+
+    def get_selected2(self, kind, cap=None):
+        """(ascending upload-order positions of the selected pools of a two-asset bucket -- the first `cap` of them, None = all --,
+        how many the bucket has)"""
+        return self._selected(lambda p, c, n: self.L.cfmm_get_selected2(self.h, int(kind), p, c, n), cap)
+
+    def get_selectedN(self, k, cap=None):
+        """... of the geo-mean bucket of k assets"""
+        return self._selected(lambda p, c, n: self.L.cfmm_get_selectedN(self.h, int(k), p, c, n), cap)
+
+    def get_selectedG(self, kind, k, cap=None):
+        """... of the K-asset table's bucket (kind, k)"""
+        return self._selected(lambda p, c, n: self.L.cfmm_get_selectedG(self.h, int(kind), int(k), p, c, n), cap)
+
+    def subnetwork(self, lists=None):
+        """cfmm_subnetwork: a new context on this device whose own pool store holds the chosen pools, gathered device to device
+        (docs/subnetwork.md).  lists: {bucket slot (bucket_slot): strictly ascending upload-order positions}, or None = the current
+        selection (select_pools).  Carries the utility, the accepted prices and the reproducible mode; independent afterwards"""
+        pl, keep = None, []
+        if lists is not None:
+            pl = PoolLists()
+            for q, pos in lists.items():
+                if not 0 <= int(q) < BUCKET_SLOTS:
+                    raise CfmmError(f"subnetwork: no bucket slot {q!r}")
+                pos = np.ascontiguousarray(pos, dtype=np.int32).reshape(-1)
+                keep.append(pos)
+                pl.count[int(q)] = len(pos)
+                if len(pos):
+                    pl.pos[int(q)] = pos.ctypes.data_as(C.POINTER(C.c_int32))
+        h = C.c_void_p()
+        self._chk(self.L.cfmm_subnetwork(self.h, C.byref(pl) if pl is not None else None, C.byref(h)))
+        return Context(self.n, _handle=h)
 
     def debug_audit_launch(self, timed=False, grid=0):
         """(seconds of the last audit's launches by HIP events, buckets the last audit found stored reordered); switches the events

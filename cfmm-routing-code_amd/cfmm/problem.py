@@ -508,6 +508,35 @@ def _bucket_param(net, key):
     return b["param"] if fam == "gk" and key[0] == "stable" else None
 
 
+def subset_network(net, positions_by_key):
+    """The host network of a choice of pools: {bucket key: strictly ascending positions} (keys as bucket_trades takes them; a bucket
+    not named, or named with no position, is left out) -> a network holding copies of those pools' columns in that order, equal array
+    for array to what pack makes of the same pool sub-list.  Everything that is not a bucket (n_tokens, c, prices) is carried over."""
+    out = {k: v for k, v in net.items() if not str(k).startswith("_") and k not in KIND2 and k not in ("gn", "gk")}
+    for key, pos in positions_by_key.items():
+        b, fam = _bucket_of(net, key)
+        m = len(b["Ra"]) if fam == "two" else b["R"].shape[1]
+        p = np.asarray(pos, dtype=np.int64).reshape(-1)
+        if len(p) and (p[0] < 0 or p[-1] >= m or np.any(np.diff(p) <= 0)):
+            raise ValueError(f"bucket {key!r}: positions must be strictly ascending and in [0, {m})")
+        if len(p) == 0:
+            continue
+        sub = {name: (col[p].copy() if col.ndim == 1 else np.ascontiguousarray(col[:, p])) for name, col in b.items() if isinstance(col, np.ndarray)}
+        if fam == "two":
+            out[key] = sub
+        else:
+            out.setdefault(fam, {})[key if fam == "gk" else int(key)] = sub
+    # (bucket order as pack and the uploads have it: the two-asset kinds, then the sizes in the parent's order)
+    ordered = {k: v for k, v in out.items() if k not in KIND2 and k not in ("gn", "gk")}
+    for key in KIND2:
+        if key in out:
+            ordered[key] = out[key]
+    for fam in ("gn", "gk"):
+        if fam in out:
+            ordered[fam] = {k: out[fam][k] for k in net[fam] if k in out[fam]}
+    return ordered
+
+
 def network_pool_count(net):
     m = sum(len(net[k]["Ra"]) for k in KIND2 if k in net)
     m += sum(b["R"].shape[1] for b in net.get("gn", {}).values())
@@ -1469,6 +1498,107 @@ class Problem:
         dv = getattr(self, "dual_value", None)
         rep["gap"] = abs(dv - rep["value"]) / max(1.0, abs(dv)) if dv is not None else float("nan")
         return rep
+
+    def select(self, min_value=0.0):
+        """Which pools of the route are worth executing?  Every pool is measured on the device by the value it takes in at the accepted
+        prices, v = sum_j nu_j delta_j on the tenders deltas / lambdas / bucket_trades hand out now, and selected iff v > min_value
+        (strict: 0 selects the pools that trade; docs/subnetwork.md).  Only the selected positions cross to the host.  Returns the
+        report of cfmm_select_pools as a dict (pools, selected, non_finite, value_in_total, value_in_selected, per-slot counts), plus
+          positions   {bucket key: ascending upload-order positions of the bucket's selected pools} (keys as bucket_trades takes them)
+          pools       the selected pools' indices in the pool lists this Problem was built from, ascending (None without lists)
+        Refused (CfmmError) while fills are held on the host, ties sit on the device or the pools are sharded, as apply_trades'
+        device path is: the selection is of the device's own tenders."""
+        ctx = self._ensure_ctx()
+        self._pools_seen()
+        if self._apply_path() != "device":
+            raise CfmmError("select: fills held on the host, device ties or sharded pools -- the device's tenders are not the route")
+        net = self._net
+        out = ctx.select_pools(min_value)
+        pos = {}
+        cap = lambda key: out["slot_selected"][self._slot_of(key)]      # (the count is known: one compaction per bucket, none where it is 0)
+        for key, kind in KIND2.items():
+            if key in net:
+                pos[key] = ctx.get_selected2(kind, cap(key))[0] if cap(key) else np.zeros(0, dtype=np.int32)
+        for k in net.get("gn", {}):
+            pos[k] = ctx.get_selectedN(k, cap(k))[0] if cap(k) else np.zeros(0, dtype=np.int32)
+        for (kind, k) in net.get("gk", {}):
+            pos[(kind, k)] = ctx.get_selectedG(_lib.POOLK[kind], k, cap((kind, k)))[0] if cap((kind, k)) else np.zeros(0, dtype=np.int32)
+        out["positions"] = pos
+        out["pools"] = None
+        if self.where is not None:
+            chosen = {key: set(p.tolist()) for key, p in pos.items()}
+            out["pools"] = np.array([i for i, (key, p) in enumerate(self.where) if int(p) in chosen.get(key, ())], dtype=np.int64)
+        return out
+
+    @staticmethod
+    def _slot_of(key):
+        if isinstance(key, str):
+            return _lib.bucket_slot(KIND2[key])
+        return _lib.bucket_slot(("table", _lib.POOLK[key[0]], key[1])) if isinstance(key, tuple) else _lib.bucket_slot(("gn", int(key)))
+
+    def subproblem(self, pools=None, buckets=None):
+        """A Problem over a choice of this one's pools, built on the device (cfmm_subnetwork, docs/subnetwork.md): the chosen pools'
+        resident columns -- as in-place updates and applied trades left them -- are gathered device to device into a pool store of
+        its own; nothing is uploaded.  The choice: `pools` (indices of the pool lists this Problem was built from, no duplicates),
+        or `buckets` ({bucket key: strictly ascending upload-order positions}), or neither = the current selection (select()).
+        The new Problem has this one's utility and, as its warm start, this one's prices (solve(warm_start=True)); its net / where are
+        the subset of this one's host copy (refreshed first if the device has moved it), and it carries
+          parent_positions   {bucket key: positions in this Problem's buckets}
+          parent_pools       this Problem's pool-list indices, ascending: sub.deltas[i] belongs to pool parent_pools[i] (None without lists)
+        Afterwards the two are independent: updates through one do not reach the other, either may be closed."""
+        if pools is not None and buckets is not None:
+            raise ValueError("subproblem: pools or buckets, not both")
+        if self._host is not None or self._comm is not None:
+            raise CfmmError("subproblem: pool-sharded problems are not served")
+        ctx = self._ensure_ctx()
+        self._pools_seen()
+        net = self.net                                   # (refreshed when an apply left it behind the device)
+        if pools is not None:
+            if self.where is None:
+                raise CfmmError("subproblem(pools=...) needs a Problem built from pool lists; use buckets=")
+            pp = np.sort(np.asarray(pools, dtype=np.int64).reshape(-1))
+            if len(pp) and (pp[0] < 0 or pp[-1] >= len(self.where) or np.any(np.diff(pp) == 0)):
+                raise ValueError(f"subproblem: pools must be distinct and in [0, {len(self.where)})")
+            positions = {}
+            for i in pp:
+                positions.setdefault(self.where[i][0], []).append(self.where[i][1])
+        elif buckets is not None:
+            positions = dict(buckets)
+        else:
+            positions = {}
+            for key in [k for k in KIND2 if k in net] + list(net.get("gn", {})) + list(net.get("gk", {})):
+                got = (ctx.get_selected2(KIND2[key]) if isinstance(key, str) else
+                       ctx.get_selectedG(_lib.POOLK[key[0]], key[1]) if isinstance(key, tuple) else ctx.get_selectedN(key))[0]
+                if len(got):
+                    positions[key] = got
+        positions = {key: np.asarray(p, dtype=np.int64).reshape(-1) for key, p in positions.items()}
+        sub_net = subset_network(net, positions)         # (checks the lists as the library does: ValueError)
+        lists = {self._slot_of(key): p for key, p in positions.items() if len(p)}
+        q = Problem(self.n, utility=self.utility, device=self.device, network=sub_net, deterministic=self.deterministic)
+        q.ctx = ctx.subnetwork(lists)
+        q._uploaded = True
+        q._dev_utility = self._dev_utility               # (what the library carried over: the utility last sent)
+        q.nu = None if self.nu is None else np.array(self.nu, dtype=np.float64)
+        q.parent_positions = positions
+        q.parent_pools = None
+        if self.where is not None:
+            rank = {key: {int(p): r for r, p in enumerate(pos)} for key, pos in positions.items()}
+            keep = [(i, key, rank[key][int(p)]) for i, (key, p) in enumerate(self.where) if int(p) in rank.get(key, ())]
+            q.parent_pools = np.array([i for i, _, _ in keep], dtype=np.int64)
+            q.where = [(key, r) for _, key, r in keep]
+        return q
+
+    def sparsify(self, min_value=0.0, solve=True, **solve_kw):
+        """Drop the dust and route again: select(min_value), the selected pools as a subproblem() built on the device, and (solve=True)
+        its solve, warm from this Problem's prices -- the fixed-cost heuristic's second pass, so that the smaller route is itself
+        optimal and feasible over the pools it uses.  Returns the new Problem, with the selection's report as .selection"""
+        rep = self.select(min_value)
+        q = self.subproblem(buckets={key: p for key, p in rep["positions"].items() if len(p)})      # (the lists select() read: no second read)
+        q.selection = rep
+        if solve:
+            solve_kw.setdefault("warm_start", True)
+            q.solve(**solve_kw)
+        return q
 
     def _solve(self, tol=1e-6, nu0=None, max_evals=2000, memory=0, iters_per_graph=8, kink_tol=1e-3,
                max_rounds=6, warm_start=False, method="auto"):

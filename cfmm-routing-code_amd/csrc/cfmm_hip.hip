@@ -41,12 +41,14 @@
 #include "update.hpp"
 #include "apply.hpp"
 #include "audit.hpp"
+#include "subset.hpp"
 #include "handoff.hpp"
 #include "solve_plan.hpp"
 #include "newton_rules.hpp"
 #include "sweep_rules.hpp"
 #include "route_rules.hpp"
 #include "update_rules.hpp"
+#include "subset_rules.hpp"
 
 using namespace cfmm;
 
@@ -183,6 +185,7 @@ struct Point {
     bool slo_active = false;           // sm_slo holds that solve's low-order log-prices (smooth.hpp); read only while mu_last > 0
     std::vector<double> tr_ovr;        // tenders the library's kink loop left (solve_tiny_kinks; cfmm_solve_sweep's `trades` layout):
     bool tr_ovr_valid = false;         // what cfmm_get_trades2 returns while set
+    bool sel_valid = false;            // the selection arena holds the masks of these tenders' pools (cfmm_select_pools)
 };
 
 struct cfmm_ctx {
@@ -220,6 +223,11 @@ struct cfmm_ctx {
     double audit_sec = 0.0;
     int audit_reordered = 0;           // buckets the last audit found stored reordered (perm non-null)
     double apply_sec[2] = {0.0, 0.0};  // ... of the last apply: the pass that checks, the pass that writes
+    // cfmm_select_pools (subset.hpp), made at the first selection and grown with the buckets: the arena of subset_rules.hpp's layout
+    // (records | partials | mask words | the compaction's counts); pinned: the records read back | the compaction's total
+    char *sel_dev = nullptr; size_t sel_cap = 0;
+    char *sel_host = nullptr;
+    route::Counts sel_counts = {};     // the buckets the masks were laid out for (read only while pt.sel_valid)
 
     // tokens / state (device)
     double *c = nullptr, *h = nullptr, *off = nullptr, *glo = nullptr, *ghi = nullptr;
@@ -806,17 +814,18 @@ void local_extrema(cfmm_ctx *ctx)
 void point_from_caller(cfmm_ctx *ctx)
 {
     Point &p = ctx->pt;
-    p.have_nu = true; p.hsol_valid = false; p.mu_last = 0.0; p.slo_active = false; p.tr_ovr_valid = false;
+    p.have_nu = true; p.hsol_valid = false; p.mu_last = 0.0; p.slo_active = false; p.tr_ovr_valid = false; p.sel_valid = false;
 }
 // a solve left nu | psi in nu_acc / psi_acc and hsol, at barrier weight mu (0: first order), sm_slo in use or not, and the kink loop its tenders
 void point_published(cfmm_ctx *ctx, double mu, bool slo, std::vector<double> *tenders = nullptr)
 {
     Point &p = ctx->pt;
-    p.have_nu = true; p.hsol_valid = true; p.mu_last = mu; p.slo_active = slo; p.tr_ovr_valid = tenders != nullptr;
+    p.have_nu = true; p.hsol_valid = true; p.mu_last = mu; p.slo_active = slo; p.tr_ovr_valid = tenders != nullptr; p.sel_valid = false;
     if (tenders) p.tr_ovr.swap(*tenders);
 }
-// the tie rules changed (cfmm_set_pool_flags / G, cfmm_set_ties), or a solve is about to move the point: the kink loop's tenders go
-void drop_tenders(cfmm_ctx *ctx) { ctx->pt.tr_ovr_valid = false; }
+// the tie rules changed (cfmm_set_pool_flags / G, cfmm_set_ties), or a solve is about to move the point: the kink loop's tenders go,
+// and the selection made of the old tenders with them
+void drop_tenders(cfmm_ctx *ctx) { ctx->pt.tr_ovr_valid = false; ctx->pt.sel_valid = false; }
 // a first-order solve is about to move the point, or the smoothed state of its barrier weight was overwritten (cfmm_time_newton_kernels)
 void drop_barrier(cfmm_ctx *ctx) { ctx->pt.mu_last = 0.0; ctx->pt.slo_active = false; }
 // the point whose tenders the read-backs hand out, the apply moves and the audit checks (route_rules.hpp: point_view): the accepted
@@ -834,7 +843,7 @@ void reserves_moved(cfmm_ctx *ctx)
     local_extrema(ctx);
     ctx->g_valid = false; ctx->g_counts_valid = false;
     Point &p = ctx->pt;
-    p.hsol_valid = false; p.mu_last = 0.0; p.slo_active = false; p.tr_ovr_valid = false;
+    p.hsol_valid = false; p.mu_last = 0.0; p.slo_active = false; p.tr_ovr_valid = false; p.sel_valid = false;
 }
 
 // a successful (re-)upload through this context
@@ -2434,6 +2443,8 @@ int cfmm_destroy(cfmm_ctx *ctx)
     if (ctx->tender_dev) (void)hipFree(ctx->tender_dev);
     if (ctx->audit_dev) (void)hipFree(ctx->audit_dev);
     if (ctx->audit_host) (void)hipHostFree(ctx->audit_host);
+    if (ctx->sel_dev) (void)hipFree(ctx->sel_dev);
+    if (ctx->sel_host) (void)hipHostFree(ctx->sel_host);
     if (ctx->sweep.dev) (void)hipFree(ctx->sweep.dev);
     if (ctx->sweep.host) (void)hipHostFree(ctx->sweep.host);
     if (ctx->sweep.tr_dev) (void)hipFree(ctx->sweep.tr_dev);
@@ -4834,12 +4845,12 @@ struct ApplyRun {
 };
 
 // what the context must hold: prices, and no ties of the caller's
-int apply_refusals(cfmm_ctx *ctx)
+int apply_refusals(cfmm_ctx *ctx, const char *who = "apply_trades")
 {
-    if (!ctx->pt.have_nu) return fail(ctx, CFMM_E_STATE, "apply_trades: no prices yet (cfmm_set_nu or a solve first)");
+    if (!ctx->pt.have_nu) return fail(ctx, CFMM_E_STATE, "%s: no prices yet (cfmm_set_nu or a solve first)", who);
     bool tied = ctx->flags2 != nullptr || ctx->ng != ctx->n;
     for (int *q : ctx->flagsG) tied |= q != nullptr;
-    if (tied) return fail(ctx, CFMM_E_UNSUPPORTED, "apply_trades: tie flags or price ties are set by the caller, who then holds the tied pools' fills");
+    if (tied) return fail(ctx, CFMM_E_UNSUPPORTED, "%s: tie flags or price ties are set by the caller, who then holds the tied pools' fills", who);
     return CFMM_OK;
 }
 
@@ -4950,6 +4961,334 @@ int cfmm_apply_timers(cfmm_ctx *ctx, int on, double *out2)
     if (!ctx) return CFMM_E_ARG;
     ctx->apply_timed = on != 0;
     if (out2) { out2[0] = ctx->apply_sec[0]; out2[1] = ctx->apply_sec[1]; }
+    return CFMM_OK;
+}
+
+// ---- pools of the route selected on the device (subset.hpp; the layout and the folds: subset_rules.hpp; docs/subnetwork.md) ----------
+// One pass over every bucket on this context's stream, as a reader of the store like the read-backs: every workgroup leaves one partial,
+// one launch folds them per bucket slot, ONE copy (the records) and ONE synchronisation.  The masks stay in the context's selection
+// arena; nothing of the store and nothing else of the context is written.
+namespace {
+struct SelectRun {
+    cfmm_ctx *ctx;
+    PoolStore &ps;
+    double thr;
+    route::Counts counts;
+    TradeLayout tl;
+    subset::Layout lay;
+    const double *ovr;                 // the kink loop's tenders on the device (NULL: every pool's own)
+};
+
+// the selection arena (grow-only; the stream is drained wherever a selection is read, so the old one is idle) and its pinned records
+int select_reserve(SelectRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    if (!ctx->sel_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->sel_host, route::SLOTS * sizeof(SelRec) + 256));
+    if (R.lay.total <= ctx->sel_cap) return CFMM_OK;
+    if (ctx->sel_dev) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->sel_dev); ctx->sel_dev = nullptr; ctx->sel_cap = 0; }
+    HIP_TRY(ctx, hipMalloc((void **)&ctx->sel_dev, R.lay.total));
+    ctx->sel_cap = R.lay.total;
+    return CFMM_OK;
+}
+
+// the kink loop's own tenders (two-asset buckets, partial fills included) travel to the device once, as the apply stages them
+int select_stage(SelectRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    if (!ctx->pt.tr_ovr_valid) return CFMM_OK;
+    const size_t len = R.tl.two_asset();
+    if (ctx->pt.tr_ovr.size() < len) return fail(ctx, CFMM_E_STATE, "select_pools: the kink loop's tenders do not match the resident buckets");
+    { int rc = tender_room(ctx, len); if (rc) return rc; }
+    if (len) HIP_TRY(ctx, hipMemcpyAsync(ctx->tender_dev, ctx->pt.tr_ovr.data(), len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    R.ovr = ctx->tender_dev;
+    return CFMM_OK;
+}
+
+int select_pass(SelectRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    const subset::Layout &lay = R.lay;
+    SelRec *recs = (SelRec *)(ctx->sel_dev + lay.recs), *parts = (SelRec *)(ctx->sel_dev + lay.parts);
+    unsigned long long *words = (unsigned long long *)(ctx->sel_dev + lay.words);
+    HIP_TRY(ctx, hipMemsetAsync(words, 0, lay.scan - lay.words, ctx->stream));       // (reordered buckets set their bits one by one)
+    const TenderPoint p = tender_point(ctx);
+    const dim3 blk(SEL_THREADS);
+    SelFold fold;
+    for (int q = 0; q <= route::SLOTS; ++q) fold.off[q] = lay.part_off[q];
+    each_bucket(R.ps, [&](auto &r, int q, auto FAMILY, auto KIND, auto K) {
+        const auto b = r.b;                             // (no tie flags: the call refuses while any are set)
+        const dim3 grid((unsigned)subset::select_groups(b.m));
+        const SelArgs a{words + lay.word_off[q], parts + lay.part_off[q], R.thr};
+        if constexpr (FAMILY == 0) {
+            const double *ov = R.ovr ? R.ovr + R.tl.off2[KIND] : nullptr;
+            hipLaunchKernelGGL(select2_kernel<KIND>, grid, blk, 0, ctx->stream, b, p.nu, p.slo, p.mu, ov, a);
+        } else if constexpr (FAMILY == 1) hipLaunchKernelGGL(selectN_kernel<K>, grid, blk, 0, ctx->stream, b, p.nu, p.slo, a);
+        else hipLaunchKernelGGL((selectG_kernel<KIND, K>), grid, blk, 0, ctx->stream, b, p.nu, p.slo, p.mu, a);
+    });
+    hipLaunchKernelGGL(select_fold_kernel, dim3(route::SLOTS), blk, 0, ctx->stream, parts, fold, recs);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->sel_host, recs, route::SLOTS * sizeof(SelRec), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CFMM_OK;
+}
+
+// one bucket's selected positions: count, scan, write (subset.hpp), the total read back first and then only the positions there are
+int selected_back(cfmm_ctx *ctx, const char *who, int q, int32_t *idx, int64_t cap, int64_t *count)
+{
+    if (!count || cap < 0 || (cap > 0 && !idx)) return fail(ctx, CFMM_E_ARG, "%s: count is NULL, cap is negative, or idx is NULL with cap > 0", who);
+    *count = 0;
+    if (sharded(ctx)) return fail(ctx, CFMM_E_UNSUPPORTED, "%s: pool-sharded contexts are not served", who);
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
+    if (!ctx->pt.sel_valid) return fail(ctx, CFMM_E_STATE, "%s: no selection (cfmm_select_pools first; a solve, new prices or ties, an upload or an update drop it)", who);
+    const int64_t m = ctx->sel_counts.m[q];
+    if (m == 0) return CFMM_OK;
+    const subset::Layout lay = subset::layout(ctx->sel_counts);
+    const unsigned long long *words = (const unsigned long long *)(ctx->sel_dev + lay.words) + lay.word_off[q];
+    unsigned *cnt = (unsigned *)(ctx->sel_dev + lay.scan);
+    const long long nwords = subset::mask_words(m), groups = subset::scan_groups(m);
+    const int64_t room = std::min(cap, m);
+    double *d0 = nullptr, *d1 = nullptr;
+    { int rc = trade_scratch(ctx, ((size_t)room + 3) / 4 + 1, &d0, &d1); if (rc) return rc; }      // (room int32 in 2 x that many doubles)
+    int *out = reinterpret_cast<int *>(d0);
+    const dim3 grid((unsigned)groups), blk(SCAN_THREADS);
+    hipLaunchKernelGGL(selected_count_kernel, grid, blk, 0, ctx->stream, words, nwords, cnt);
+    hipLaunchKernelGGL(selected_scan_kernel, dim3(1), blk, 0, ctx->stream, cnt, groups);
+    hipLaunchKernelGGL(selected_write_kernel, grid, blk, 0, ctx->stream, words, nwords, (const unsigned *)cnt, out, (long long)room);
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned *total = reinterpret_cast<unsigned *>(ctx->sel_host + route::SLOTS * sizeof(SelRec));
+    HIP_TRY(ctx, hipMemcpyAsync(total, cnt + groups, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *count = (int64_t)*total;
+    const int64_t n = subset::listed(*count, cap);
+    if (n > 0) {
+        { int rc = download_staged(ctx, idx, out, (size_t)n * sizeof(int32_t)); if (rc) return rc; }
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return CFMM_OK;
+}
+}  // namespace
+
+int cfmm_select_pools(cfmm_ctx *ctx, double min_value_in, cfmm_select_info *info)
+{
+    const char *who = "select_pools";
+    if (!ctx) return CFMM_E_ARG;
+    if (info) std::memset(info, 0, sizeof *info);
+    if (min_value_in != min_value_in) return fail(ctx, CFMM_E_ARG, "%s: the threshold is NaN", who);
+    if (sharded(ctx)) return fail(ctx, CFMM_E_UNSUPPORTED, "%s: pool-sharded contexts are not served", who);
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
+    { int rc = apply_refusals(ctx, who); if (rc) return rc; }
+    ctx->pt.sel_valid = false;                             // (a pass that fails half way leaves no selection)
+    const route::Counts counts = bucket_counts(entry.ps);
+    SelectRun R{ctx, entry.ps, min_value_in, counts, route::trade_layout(counts), subset::layout(counts), nullptr};
+    { int rc = select_reserve(R); if (rc) return rc; }
+    { int rc = select_stage(R); if (rc) return rc; }
+    { int rc = select_pass(R); if (rc) return rc; }
+    ctx->sel_counts = counts;
+    ctx->pt.sel_valid = true;
+    if (info) subset::fold_select((const SelRec *)ctx->sel_host, counts, info);
+    return CFMM_OK;
+}
+
+int cfmm_get_selected2(cfmm_ctx *ctx, int kind, int32_t *idx, int64_t cap, int64_t *count)
+{
+    if (!ctx) return CFMM_E_ARG;
+    if (kind < 0 || kind >= CFMM_POOL_KINDS2) return fail(ctx, CFMM_E_ARG, "get_selected2: kind %d", kind);
+    return selected_back(ctx, "get_selected2", route::slot2(kind), idx, cap, count);
+}
+
+int cfmm_get_selectedN(cfmm_ctx *ctx, int k, int32_t *idx, int64_t cap, int64_t *count)
+{
+    if (!ctx) return CFMM_E_ARG;
+    if (k < 3 || k > CFMM_MAX_POOL_SIZE) return fail(ctx, CFMM_E_ARG, "get_selectedN: %d assets", k);
+    return selected_back(ctx, "get_selectedN", route::slotN(k), idx, cap, count);
+}
+
+int cfmm_get_selectedG(cfmm_ctx *ctx, int kind, int k, int32_t *idx, int64_t cap, int64_t *count)
+{
+    if (!ctx) return CFMM_E_ARG;
+    if (kind < 0 || kind >= CFMM_POOLK_KINDS || k < 2 || k > CFMM_MAX_POOL_SIZE) return fail(ctx, CFMM_E_ARG, "get_selectedG: kind %d, %d assets", kind, k);
+    return selected_back(ctx, "get_selectedG", route::slotG(kind, k), idx, cap, count);
+}
+
+// ---- a sub-network gathered on the device (subset.hpp; the lists and the arenas: subset_rules.hpp; docs/subnetwork.md) -----------------
+// The lists are checked on the host before anything is allocated and travel as ONE staged copy (behind a zeroed header that takes the
+// reduced extrema); per chosen bucket one arena laid out as an upload's, one gather launch and two reductions on the PARENT's stream
+// (behind everything it has enqueued), ONE copy back and ONE synchronisation.  Then the new context owns the arenas.
+namespace {
+constexpr size_t SUB_HDR = 2 * route::SLOTS * sizeof(unsigned long long);       // per slot: largest reserve | smallest fee, as the updates reduce them
+
+struct SubnetRun {
+    cfmm_ctx *src, *sub;
+    PoolStore &ps;
+    const cfmm_pool_lists *lists;
+    route::Counts counts;
+    std::vector<size_t> offs;          // device offset of every staged part: the header, then the chosen slots' lists in bucket order
+    int part_of[route::SLOTS];         // a slot's part (0: not chosen)
+};
+
+int subnet_stage(SubnetRun &R)
+{
+    static const std::vector<char> zeros(SUB_HDR, 0);
+    std::vector<UpdPart> parts = {{zeros.data(), SUB_HDR}};
+    route::each_slot([&](int q, int, int, int) {
+        R.part_of[q] = 0;
+        if (R.lists->count[q] > 0) { R.part_of[q] = (int)parts.size(); parts.push_back({R.lists->pos[q], (size_t)R.lists->count[q] * sizeof(int32_t)}); }
+    });
+    return update_stage(R.src, parts, R.offs);
+}
+
+// one chosen bucket: the parent's inverse permutation where it is stored reordered (built once per bucket, as the updates build it), the
+// arena, the gather, the reductions.  The new record is filled in but for its extrema
+extern "C++" template <class Rec, class FAMILY, class KIND, class KK> int subnet_bucket(SubnetRun &R, Rec &r, int q, FAMILY, KIND, KK)
+{
+    cfmm_ctx *ctx = R.src;
+    const int64_t cnt = R.lists->count[q];
+    if (cnt == 0) return CFMM_OK;
+    constexpr int K = KK::value;
+    (void)K;
+    const auto b = r.b;
+    const int *list = (const int *)(ctx->upd_dev + R.offs[R.part_of[q]]);
+    unsigned long long *mx = (unsigned long long *)(ctx->upd_dev + R.offs[0]) + q, *mn = mx + route::SLOTS;
+    const dim3 grid((unsigned)((cnt + SUB_THREADS - 1) / SUB_THREADS)), blk(SUB_THREADS);
+    char *arena = nullptr;
+    if constexpr (FAMILY::value != 2) {
+        if (b.perm && !r.inv) {
+            HIP_TRY(ctx, hipMalloc((void **)&r.inv, (size_t)b.m * sizeof(int) + 16));
+            hipLaunchKernelGGL(upd_inverse_kernel, dim3((unsigned)std::min<int64_t>((b.m + UP_THREADS - 1) / UP_THREADS, 4096)), dim3(UP_THREADS), 0, ctx->stream, b.perm, (long long)b.m, r.inv);
+        }
+    }
+    if constexpr (FAMILY::value == 0) {
+        const subset::Arena a = subset::arena2(cnt, b.param != nullptr);
+        HIP_TRY(ctx, hipMalloc((void **)&arena, a.total + 256));
+        Bucket2 d = {};
+        d.m = cnt;
+        int c = 0;
+        d.Ra = (double *)(arena + a.off[c++]); d.Rb = (double *)(arena + a.off[c++]); d.fee = (double *)(arena + a.off[c++]);
+        if (b.param) d.param = (double *)(arena + a.off[c++]);
+        d.ia = (int *)(arena + a.off[c++]); d.ib = (int *)(arena + a.off[c++]);
+        hipLaunchKernelGGL(subnet2_kernel, grid, blk, 0, ctx->stream, b, b.perm ? r.inv : nullptr, list, (long long)cnt, d);
+        hipLaunchKernelGGL(upd_max_kernel, dim3(max_grid(2 * cnt)), dim3(UP_THREADS), 0, ctx->stream, d.Ra, (long long)cnt, d.Rb, (long long)cnt, mx);
+        hipLaunchKernelGGL(upd_min_kernel, dim3(max_grid(cnt)), dim3(UP_THREADS), 0, ctx->stream, d.fee, (long long)cnt, mn);
+        Resident2 &n = R.sub->pools->r2[KIND::value];
+        n.b = d; n.mem = arena; n.ro = reorder_applies(R.sub, KIND::value, cnt) ? a.total : 0;
+    } else if constexpr (FAMILY::value == 1) {
+        const subset::Arena a = subset::arenaN(K, cnt);
+        HIP_TRY(ctx, hipMalloc((void **)&arena, a.total + 256));
+        BucketN d = {};
+        d.m = cnt;
+        d.idx = (int *)(arena + a.off[0]); d.R = (double *)(arena + a.off[1]); d.w = (double *)(arena + a.off[2]);
+        d.fee = (double *)(arena + a.off[3]); d.lfee = (double *)(arena + a.off[4]); d.lrw = (double *)(arena + a.off[5]);
+        hipLaunchKernelGGL(subnetN_kernel<K>, grid, blk, 0, ctx->stream, b, b.perm ? r.inv : nullptr, list, (long long)cnt, d);
+        hipLaunchKernelGGL(upd_max_kernel, dim3(max_grid(K * cnt)), dim3(UP_THREADS), 0, ctx->stream, d.R, (long long)K * cnt, (const double *)nullptr, 0ll, mx);
+        hipLaunchKernelGGL(upd_min_kernel, dim3(max_grid(cnt)), dim3(UP_THREADS), 0, ctx->stream, d.fee, (long long)cnt, mn);
+        Resident<BucketN> &n = R.sub->pools->rn[K];
+        n.b = d; n.mem = arena; n.ro = reorder_applies(R.sub, K, cnt) ? a.total : 0;
+    } else {
+        const subset::Arena a = subset::arenaG(K, cnt, b.param != nullptr);
+        HIP_TRY(ctx, hipMalloc((void **)&arena, a.total + 256));
+        BucketG d = {};
+        d.m = cnt;
+        int c = 0;
+        d.idx = (int *)(arena + a.off[c++]); d.R = (double *)(arena + a.off[c++]); d.fee = (double *)(arena + a.off[c++]);
+        if (b.param) d.param = (double *)(arena + a.off[c++]);
+        d.ifee = (double *)(arena + a.off[c++]); d.sR = (double *)(arena + a.off[c++]); d.ws = (double *)(arena + a.off[c++]);
+        hipLaunchKernelGGL(subnetG_kernel<K>, grid, blk, 0, ctx->stream, b, list, (long long)cnt, d);
+        hipLaunchKernelGGL(upd_max_kernel, dim3(max_grid(K * cnt)), dim3(UP_THREADS), 0, ctx->stream, d.R, (long long)K * cnt, (const double *)nullptr, 0ll, mx);
+        hipLaunchKernelGGL(upd_min_kernel, dim3(max_grid(cnt)), dim3(UP_THREADS), 0, ctx->stream, d.fee, (long long)cnt, mn);
+        Resident<BucketG> &n = R.sub->pools->rg[KIND::value][K];
+        n.b = d; n.mem = arena; n.ro = 0;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return CFMM_OK;
+}
+
+// the host copy of a small constant-sum bucket (PoolStore::hs_*), gathered from the parent's
+void subnet_host_copy(SubnetRun &R)
+{
+    const int q = route::slot2(CFMM_POOL_SUM2);
+    const int64_t cnt = R.lists->count[q];
+    PoolStore &p = R.ps, &s = *R.sub->pools;
+    if (cnt == 0 || cnt > 65536 || (int64_t)p.hs_Ra.size() != R.counts.m[q]) return;
+    const int32_t *pos = R.lists->pos[q];
+    for (int64_t i = 0; i < cnt; ++i) {
+        s.hs_ia.push_back(p.hs_ia[pos[i]]); s.hs_ib.push_back(p.hs_ib[pos[i]]); s.hs_fee.push_back(p.hs_fee[pos[i]]);
+        s.hs_Ra.push_back(p.hs_Ra[pos[i]]); s.hs_Rb.push_back(p.hs_Rb[pos[i]]);
+    }
+}
+
+// behind its checks: the gather under the store's lock, the extrema, what is carried over
+int subnet_build(cfmm_ctx *src, const cfmm_pool_lists *lists, const route::Counts &counts, PoolStore &ps, cfmm_ctx *sub)
+{
+    SubnetRun R{src, sub, ps, lists, counts, {}, {}};
+    { int rc = subnet_stage(R); if (rc) return rc; }
+    int rc = CFMM_OK;
+    each_bucket(ps, [&](auto &r, int q, auto FAMILY, auto KIND, auto K) { if (rc == CFMM_OK) rc = subnet_bucket(R, r, q, FAMILY, KIND, K); });
+    if (rc) return rc;
+    std::vector<unsigned long long> ext(2 * route::SLOTS);
+    std::vector<double> nu((size_t)src->n);
+    HIP_TRY(src, hipMemcpyAsync(ext.data(), src->upd_dev + R.offs[0], SUB_HDR, hipMemcpyDeviceToHost, src->stream));
+    if (src->pt.have_nu) HIP_TRY(src, hipMemcpyAsync(nu.data(), src->nu_acc, nu.size() * sizeof(double), hipMemcpyDeviceToHost, src->stream));
+    HIP_TRY(src, hipStreamSynchronize(src->stream));
+    each_bucket(*sub->pools, [&](auto &r, int q, auto, auto, auto) {
+        std::memcpy(&r.mxr, &ext[q], sizeof(double));
+        r.mnf = terms::fee_from_reduced(ext[route::SLOTS + q]);
+    });
+    subnet_host_copy(R);
+    pools_changed(sub);
+    sub->det = src->det;
+    if (src->have_utility) {
+        const int rcu = cfmm_set_utility(sub, src->hc.data(), src->hh.data(), src->hctype.data());
+        if (rcu) return fail(src, rcu, "subnetwork: the utility did not carry over: %s", sub->err.c_str());
+    }
+    if (src->pt.have_nu) {
+        const int rcn = cfmm_set_nu(sub, nu.data());
+        if (rcn) return fail(src, rcn, "subnetwork: the prices did not carry over: %s", sub->err.c_str());
+    }
+    return CFMM_OK;
+}
+}  // namespace
+
+int cfmm_subnetwork(cfmm_ctx *src, const cfmm_pool_lists *lists, cfmm_ctx **out)
+{
+    const char *who = "subnetwork";
+    if (!src) return CFMM_E_ARG;
+    if (!out) return fail(src, CFMM_E_ARG, "%s: out is NULL", who);
+    *out = nullptr;
+    if (sharded(src)) return fail(src, CFMM_E_UNSUPPORTED, "%s: pool-sharded contexts are not served", who);
+    PoolEntry entry(src); HIP_TRY(src, entry.device);      // (first: an update through a sharer since the selection was made drops it here)
+    PoolStore &ps = entry.ps;
+    // the current selection: its positions come back compacted (positions, not pool columns) and travel down again with the lists
+    cfmm_pool_lists own = {};
+    std::vector<std::vector<int32_t>> held(route::SLOTS);
+    if (!lists) {
+        if (!src->pt.sel_valid) return fail(src, CFMM_E_STATE, "%s: lists is NULL and the context holds no selection (cfmm_select_pools first)", who);
+        const SelRec *rec = (const SelRec *)src->sel_host;
+        for (int q = 0; q < route::SLOTS; ++q) {
+            if (src->sel_counts.m[q] == 0 || rec[q].selected == 0) continue;
+            held[q].resize((size_t)rec[q].selected);
+            int64_t n = 0;
+            { int rc = selected_back(src, who, q, held[q].data(), (int64_t)held[q].size(), &n); if (rc) return rc; }
+            if (n != (int64_t)held[q].size()) return fail(src, CFMM_E_STATE, "%s: the selection changed under the call", who);
+            own.pos[q] = held[q].data(); own.count[q] = n;
+        }
+        lists = &own;
+    }
+    const route::Counts counts = bucket_counts(ps);
+    const subset::ListVerdict v = subset::check_lists(lists, counts);
+    if (v.slot >= 0) {
+        const route::SlotName s = route::slot_name(v.slot);
+        return fail(src, CFMM_E_ARG, "%s: the list of the bucket (family %d, kind %d, %d assets) of %lld pools breaks the rule at entry %lld: positions are strictly ascending and in range",
+                    who, s.family, s.kind, s.k, (long long)counts.m[v.slot], (long long)v.entry);
+    }
+    for (int q = 0; q < route::SLOTS; ++q)          // (a slot no bucket has: each_slot does not visit it)
+        if (lists->count[q] != 0 && counts.m[q] == 0) return fail(src, CFMM_E_ARG, "%s: slot %d holds no pools and its list names %lld", who, q, (long long)lists->count[q]);
+    std::unique_lock<std::mutex> lock(ps.mu);
+    if (ps.readers > 1) return fail(src, CFMM_E_STATE, "%s: a context sharing these pools is inside a solve, evaluation or read-back", who);
+    cfmm_ctx *sub = nullptr;
+    { int rc = cfmm_create(src->device, src->n, &sub); if (rc) { src->err = g_create_error; return rc; } }
+    const int rc = subnet_build(src, lists, counts, ps, sub);
+    if (rc) { (void)hipStreamSynchronize(src->stream); cfmm_destroy(sub); return rc; }
+    *out = sub;
     return CFMM_OK;
 }
 

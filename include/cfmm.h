@@ -306,6 +306,64 @@ int cfmm_audit_trades(cfmm_ctx *ctx, const cfmm_audit_tenders *own /* or NULL */
  * (1 .. 2048; 0: leave as it is -- the audited result does not depend on it); out2 (or NULL) receives {seconds of the last audit's
  * launches, number of buckets the last audit found stored reordered (positions mapped through the upload's permutation)} */
 int cfmm_debug_audit_launch(cfmm_ctx *ctx, int timed, int grid, double *out2);
+/* Selecting pools of the route on the device (docs/subnetwork.md): every resident pool is measured by the value it takes in at the
+ * context's accepted prices,
+ *      v_i = sum_j nu_j Delta_ij     over the pool's legs in slot order, every product and every sum rounded on its own,
+ * on exactly the tenders cfmm_get_trades2 / N / G would return at the moment of the call (the exact pool solutions after a first-order
+ * solve or cfmm_set_nu, the gross smoothed tenders after a second-order solve, the tenders with their partial fills after
+ * CFMM_METHOD_AUTO's own kink loop): NumPy on the read-back tenders and cfmm_get_nu's prices reproduces v_i bit for bit.  A pool is
+ * selected iff v_i is finite and v_i > min_value_in (strict: 0 selects exactly the pools that take something in).  v_i is what the pool
+ * receives, not its surplus nu'(Lambda - Delta): a constant-sum pool filled on its kink has no surplus and a real fill.
+ *   - the selection stays with the context, one bit per pool per bucket in upload order, until the tenders it was made of go: a solve,
+ *     cfmm_set_nu, new tie flags or price ties, an upload, or an in-place update or apply through any context sharing the pools.
+ *     It changes nothing else a later call can see, and counts as a reader of the pools like cfmm_get_trades*;
+ *   - info: counts per bucket slot and in total; value_in_total / value_in_selected are plain double sums (per workgroup, then per
+ *     bucket, then over the slots, each in a fixed order: the same on every run, but not the sum NumPy forms in its own order -- compare
+ *     to a relative 1e-12, not bitwise).  Pools with a non-finite v_i are counted in non_finite and enter neither sum;
+ *   - refusals, as cfmm_apply_trades': no prices yet -> CFMM_E_STATE; tie flags or price ties set by the caller or a pool-sharded
+ *     context -> CFMM_E_UNSUPPORTED; a NaN threshold -> CFMM_E_ARG.
+ * A bucket slot: two-asset kind `kind` -> kind; the geo-mean bucket of k assets -> CFMM_POOL_KINDS2 + k; the K-asset table's bucket
+ * (kind, k) -> CFMM_POOL_KINDS2 + (CFMM_MAX_POOL_SIZE + 1) * (1 + kind) + k -- the bucket order of cfmm_apply_info and cfmm_audit. */
+#define CFMM_BUCKET_SLOTS 32    /* CFMM_POOL_KINDS2 + (CFMM_MAX_POOL_SIZE + 1) * (1 + CFMM_POOLK_KINDS) */
+typedef struct {
+    int64_t pools, selected, non_finite;
+    double  value_in_total, value_in_selected;
+    int64_t slot_pools[CFMM_BUCKET_SLOTS], slot_selected[CFMM_BUCKET_SLOTS];
+} cfmm_select_info;
+
+int cfmm_select_pools(cfmm_ctx *ctx, double min_value_in, cfmm_select_info *info /* or NULL */);
+/* the selected pools of one bucket as ascending upload-order positions: *count receives how many the bucket has, idx the first
+ * min(*count, cap) of them (idx may be NULL with cap 0: the count alone).  An empty bucket: CFMM_OK, *count = 0.  CFMM_E_STATE without a
+ * selection (cfmm_select_pools first, and nothing since that dropped it); count == NULL, cap < 0, a kind or k without a bucket -> CFMM_E_ARG */
+int cfmm_get_selected2(cfmm_ctx *ctx, int kind, int32_t *idx, int64_t cap, int64_t *count);
+int cfmm_get_selectedN(cfmm_ctx *ctx, int k, int32_t *idx, int64_t cap, int64_t *count);
+int cfmm_get_selectedG(cfmm_ctx *ctx, int kind, int k, int32_t *idx, int64_t cap, int64_t *count);
+/* A sub-network on the device (docs/subnetwork.md): a NEW context on src's device, with src's n_tokens (token ids are unchanged, so prices
+ * and utilities carry over one to one) and a pool store of its OWN, whose buckets hold the chosen pools of src in ascending upload order.
+ * Every column is gathered device to device from src's resident columns as they are NOW (in-place updates and applied trades included):
+ * no pool column crosses the host.  The new context is bit for bit the one a caller would get by uploading the same pools' current
+ * values: the same columns, the derived columns, every bucket's largest reserve and smallest fee reduced on the device, the token-block
+ * ordering left pending exactly where a fresh upload of that many pools would have it, the host copy of a small constant-sum bucket.
+ *   lists       per bucket slot (see cfmm_select_info) `count` upload-order positions, strictly ascending and in range; a slot with
+ *               count 0 takes no pool of that bucket.  Checked on the host before anything is allocated: a list that breaks the rule,
+ *               or names a bucket src does not hold -> CFMM_E_ARG, *out stays NULL and nothing is created.  NULL: src's current
+ *               selection (cfmm_select_pools; CFMM_E_STATE without one).  An empty choice gives a context with no pools.
+ *   carried     src's utility (as last set), its accepted prices (cfmm_solve(sub, NULL, ..) then starts warm from them) and the
+ *               reproducible mode.  NOT carried: tie flags, price ties, the solution and anything derived from it.
+ * Afterwards the two contexts are independent: either may be destroyed, updates through one do not reach the other.  The call reads
+ * src's pools like cfmm_get_trades* and changes nothing of src a later call can see; CFMM_E_STATE while another context sharing src's
+ * pools is inside a solve, evaluation or read-back.  An in-place update or apply through a sharer holds the store's lock from its
+ * first check to its last write, so a call that meets one WAITS for it (it is not refused) and gathers the updated pools.  A
+ * pool-sharded src -> CFMM_E_UNSUPPORTED.
+ * Bit for bit: the columns, the derived columns, the extrema, the reproducible mode's results, and every tender of a sub-bucket that
+ * keeps the caller's order.  A sub-bucket large enough for the token-block ordering (16 384 two-asset, 65 536 geo-mean pools) is stored
+ * in an order atomics settle, which differs between any two uploads of the same pools; the one tender that depends on a pool's wave
+ * neighbours -- CFMM_POOL_W2's, through a wave-uniform choice of series -- then agrees to 1e-14 of the reserve, as between two uploads. */
+typedef struct {
+    const int32_t *pos[CFMM_BUCKET_SLOTS];    /* [count] each, or NULL with count 0 */
+    int64_t count[CFMM_BUCKET_SLOTS];
+} cfmm_pool_lists;
+int cfmm_subnetwork(cfmm_ctx *src, const cfmm_pool_lists *lists /* or NULL */, cfmm_ctx **out);
 /* constant-sum pools sitting on their kink are `tied` (flag 1): they are skipped by the
  * kernels and their fill fraction is assigned by the host's primal recovery */
 int cfmm_set_pool_flags(cfmm_ctx *ctx, int kind, const int32_t *flags /* [m] or NULL */);
