@@ -94,6 +94,15 @@ class SelectInfo(C.Structure):
         return out
 
 
+class PricesInfo(C.Structure):
+    """cfmm_prices_info: the report of cfmm_pool_prices (docs/pool_prices.md)"""
+    _fields_ = [("relations", C.c_int64), ("components", C.c_int32), ("components_anchored", C.c_int32), ("tokens_unlisted", C.c_int32),
+                ("iterations", C.c_int32), ("status", C.c_int32), ("residual", C.c_double), ("misfit_max", C.c_double), ("misfit_ss", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PoolLists(C.Structure):
     """cfmm_pool_lists: per bucket slot the upload-order positions cfmm_subnetwork takes"""
     _fields_ = [("pos", C.POINTER(C.c_int32) * BUCKET_SLOTS), ("count", C.c_int64 * BUCKET_SLOTS)]
@@ -118,7 +127,7 @@ assert _STATS_STRUCT.size == C.sizeof(Stats)
 
 def build(force=False):
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp", "update.hpp", "apply.hpp", "audit.hpp", "solve_plan.hpp", "newton_rules.hpp", "sweep_rules.hpp", "route_rules.hpp", "update_rules.hpp", "subset.hpp", "subset_rules.hpp", "tiny_limits.hpp", "fixedpoint.hpp")]
+    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp", "update.hpp", "apply.hpp", "audit.hpp", "solve_plan.hpp", "newton_rules.hpp", "sweep_rules.hpp", "route_rules.hpp", "update_rules.hpp", "subset.hpp", "subset_rules.hpp", "prices.hpp", "prices_rules.hpp", "tiny_limits.hpp", "fixedpoint.hpp")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "cfmm.h"))
     if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _CSRC, "-s"])
@@ -130,7 +139,7 @@ _lib = None
 SYMBOLS = ["cfmm_create", "cfmm_clone", "cfmm_destroy", "cfmm_last_error", "cfmm_backend", "cfmm_default_opts",
            "cfmm_upload_pools2", "cfmm_upload_poolsN", "cfmm_upload_poolsG", "cfmm_update_pools2", "cfmm_update_poolsN", "cfmm_update_poolsG",
            "cfmm_update_terms2", "cfmm_update_termsN", "cfmm_update_termsG",
-           "cfmm_apply_trades", "cfmm_get_reserves2", "cfmm_get_reservesN", "cfmm_get_reservesG", "cfmm_apply_timers", "cfmm_audit_trades", "cfmm_debug_audit_launch", "cfmm_select_pools", "cfmm_get_selected2", "cfmm_get_selectedN", "cfmm_get_selectedG", "cfmm_subnetwork", "cfmm_set_pool_flags", "cfmm_set_pool_flagsG", "cfmm_set_utility",
+           "cfmm_apply_trades", "cfmm_get_reserves2", "cfmm_get_reservesN", "cfmm_get_reservesG", "cfmm_apply_timers", "cfmm_audit_trades", "cfmm_debug_audit_launch", "cfmm_select_pools", "cfmm_get_selected2", "cfmm_get_selectedN", "cfmm_get_selectedG", "cfmm_subnetwork", "cfmm_pool_prices", "cfmm_debug_prices_launch", "cfmm_set_pool_flags", "cfmm_set_pool_flagsG", "cfmm_set_utility",
            "cfmm_set_ties", "cfmm_set_deterministic", "cfmm_debug_eval_limbs", "cfmm_debug_scatter_limbs", "cfmm_eval_dual", "cfmm_eval_smooth", "cfmm_debug_cholesky", "cfmm_debug_cholesky_apply", "cfmm_time_xcd_handoff", "cfmm_solve", "cfmm_solve_batch", "cfmm_eval_dual_batch", "cfmm_batch_capacity", "cfmm_solve_sweep", "cfmm_get_nu", "cfmm_set_nu", "cfmm_get_psi",
            "cfmm_get_solution", "cfmm_get_trades2", "cfmm_get_tradesN", "cfmm_get_tradesG", "cfmm_comm_unique_id", "cfmm_comm_init",
            "cfmm_oneshot_export", "cfmm_oneshot_import", "cfmm_oneshot_attach", "cfmm_oneshot_mailbox", "cfmm_oneshot_enable",
@@ -174,6 +183,8 @@ def lib():
     L.cfmm_get_selectedN.argtypes = [vp, C.c_int, ip, C.c_int64, C.POINTER(C.c_int64)]
     L.cfmm_get_selectedG.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int64, C.POINTER(C.c_int64)]
     L.cfmm_subnetwork.argtypes = [vp, C.POINTER(PoolLists), C.POINTER(vp)]
+    L.cfmm_pool_prices.argtypes = [vp, dp, dp, dp, ip, C.POINTER(PricesInfo)]
+    L.cfmm_debug_prices_launch.argtypes = [vp, C.c_int, dp]
     L.cfmm_set_pool_flags.argtypes = [vp, C.c_int, ip]
     L.cfmm_set_pool_flagsG.argtypes = [vp, C.c_int, ip]
     L.cfmm_set_utility.argtypes = [vp, dp, dp, ip]
@@ -449,6 +460,32 @@ class Context:
         h = C.c_void_p()
         self._chk(self.L.cfmm_subnetwork(self.h, C.byref(pl) if pl is not None else None, C.byref(h)))
         return Context(self.n, _handle=h)
+
+    def pool_prices(self, anchor=None, want_potential=False):
+        """cfmm_pool_prices: the prices the resident pools imply at their current reserves, fees and weights (docs/pool_prices.md).
+        anchor: [n] known prices, 0 = unknown (None: none known).  Returns (prices, info); with want_potential, info also carries
+        "phi" (the gauged log-potentials) and "comp" (component labels 0.., numbered by first token)"""
+        n = self.n
+        if anchor is not None:
+            anchor = f64(anchor)
+            if anchor.shape != (n,):
+                raise CfmmError(f"pool_prices: anchor has shape {anchor.shape}, not ({n},)")
+        prices = np.empty(n)
+        phi = np.empty(n) if want_potential else None
+        comp = np.empty(n, np.int32) if want_potential else None
+        rep = PricesInfo()
+        self._chk(self.L.cfmm_pool_prices(self.h, _d(anchor), _d(prices), _d(phi), _i(comp), C.byref(rep)))
+        info = rep.asdict()
+        if want_potential:
+            info["phi"], info["comp"] = phi, comp
+        return prices, info
+
+    def debug_prices_launch(self, timed=False):
+        """seconds of the last timed pool_prices' {clear, relation pass, components, iteration, misfit pass} by HIP events; switches
+        the events on or off for the calls that follow (tools/prices_timing.py)"""
+        out = np.zeros(5)
+        self._chk(self.L.cfmm_debug_prices_launch(self.h, 1 if timed else 0, _d(out)))
+        return out
 
     def debug_audit_launch(self, timed=False, grid=0):
         """(seconds of the last audit's launches by HIP events, buckets the last audit found stored reordered); switches the events

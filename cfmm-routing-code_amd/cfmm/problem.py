@@ -775,6 +775,128 @@ def _propagate_prices(net, c, known):
     return np.where(known, c, np.exp(logp))
 
 
+# ------------------------------------------------------------------------------- the prices the pools imply
+def start_anchor(util):
+    """the prices a utility names, 0 where it names none: start_prices' `c` (entries of the utility table start at the price at which
+    they would not trade, u'(0)) -- the anchors of pool_prices for solve(nu0="pools")"""
+    c = util.c
+    if _is_general(util):
+        c = c.copy()
+        lg, qd = util.ctype == ULOG, util.ctype == UQUAD
+        with np.errstate(divide="ignore"):
+            c[lg] = np.where(util.h[lg] > 0, util.c[lg] / np.where(util.h[lg] > 0, util.h[lg], 1.0), 0.0)
+        c[qd] = util.c[qd]
+    return np.where(c > 0, c, 0.0)
+
+
+def pool_relations(net):
+    """(eu, ev, lr) of EVERY pool at the network's current reserves, fees and weights: log p_eu - log p_ev = lr, one relation per
+    two-asset pool (ia, ib), k - 1 per k-asset pool (leg j against leg 0), in bucket order.  _price_relations' formulas at stride 1;
+    reads and writes none of its caches"""
+    eu, ev, elr = [], [], []
+    for key in KIND2:
+        if key not in net:
+            continue
+        b = net[key]
+        Ra, Rb = b["Ra"], b["Rb"]
+        if key == "cp2":
+            lr = np.log(Rb / Ra)
+        elif key == "w2":
+            lr = np.log(b["wa"] * Rb / ((1 - b["wa"]) * Ra))
+        elif key == "sum2":
+            lr = np.zeros(len(Ra))
+        elif key == "pow2":
+            lr = b["t"] * np.log(Rb / Ra)
+        else:
+            lr = np.log((1 + b["alpha"] / (Ra * Ra * Rb)) / (1 + b["alpha"] / (Ra * Rb * Rb)))
+        eu.append(b["ia"]); ev.append(b["ib"]); elr.append(lr)
+    for k, b in net.get("gn", {}).items():
+        for j in range(1, k):
+            eu.append(b["idx"][j]); ev.append(b["idx"][0])
+            elr.append(np.log(b["w"][j] * b["R"][0] / (b["w"][0] * b["R"][j])))
+    for (kind, k), b in net.get("gk", {}).items():
+        R = b["R"]
+        lm = np.log1p((b["param"] / np.prod(R, axis=0))[None, :] / R) if kind == "stable" else np.zeros_like(R)
+        for j in range(1, k):
+            eu.append(b["idx"][j]); ev.append(b["idx"][0]); elr.append(lm[j] - lm[0])
+    if not eu:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0)
+    return np.concatenate(eu).astype(np.int64), np.concatenate(ev).astype(np.int64), np.concatenate(elr).astype(np.float64)
+
+
+def pool_prices(net, anchor=None):
+    """The prices the pools imply (docs/pool_prices.md; the pure NumPy twin of cfmm_pool_prices).  phi minimises
+    sum (phi_u - phi_v - lr)^2 over every pool's relations (unit weights, no thinning): L phi = rhs on the multigraph Laplacian by
+    Jacobi-preconditioned conjugate gradients from zero, stopped at max |r| <= 1e-12 max |rhs| or after 4 n + 100 iterations, then
+    zero mean per connected component.  anchor[j] > 0: a known price.  A component with anchored tokens gets log p = phi + off, off
+    the mean of log anchor - phi over them in token order, and its anchored tokens come back as given; one without returns exp(phi).
+    Returns (prices, info): info has cfmm_prices_info's fields, and phi (gauged) and comp (labels 0.., numbered by first token)."""
+    n = int(net["n_tokens"])
+    eu, ev, lr = pool_relations(net)
+    if anchor is not None:
+        anchor = np.asarray(anchor, dtype=np.float64)
+        if anchor.shape != (n,) or not np.all(np.isfinite(anchor) & (anchor >= 0)):
+            raise ValueError("pool_prices: anchor holds n entries, each 0 (unknown) or a positive finite price")
+    deg = (np.bincount(eu, minlength=n) + np.bincount(ev, minlength=n)).astype(np.float64)
+    label = np.arange(n)
+    while len(eu):                                            # min-label propagation with pointer jumping
+        new = label.copy()
+        np.minimum.at(new, eu, label[ev])
+        np.minimum.at(new, ev, label[eu])
+        new = new[new]
+        if np.array_equal(new, label):
+            break
+        label = new
+    comp = np.unique(label, return_inverse=True)[1].astype(np.int32)       # (labels are first tokens: ascending labels = by first token)
+    nc = int(comp.max()) + 1 if n else 0
+
+    def adj(x):
+        return np.bincount(eu, weights=x[ev], minlength=n) + np.bincount(ev, weights=x[eu], minlength=n)
+    rhs = np.bincount(eu, weights=lr, minlength=n) - np.bincount(ev, weights=lr, minlength=n)
+    dinv = 1.0 / np.maximum(deg, 1.0)
+    phi = np.zeros(n)
+    r = rhs.copy()
+    pdir = dinv * r
+    rz = float(r @ pdir)
+    rhs_max = float(np.abs(rhs).max()) if n else 0.0
+    stop = 1e-12 * max(rhs_max, 1e-300)
+    it, status = 0, 0
+    rmax = rhs_max
+    while rmax > stop:
+        if it >= 4 * n + 100:
+            status = 1
+            break
+        q = deg * pdir - adj(pdir)
+        pq = float(pdir @ q)
+        if not pq > 0.0:
+            status = 1
+            break
+        alpha = rz / pq
+        phi += alpha * pdir
+        r -= alpha * q
+        z = dinv * r
+        rz_new = float(r @ z)
+        rmax = float(np.abs(r).max())
+        pdir = z + (rz_new / rz) * pdir
+        rz = rz_new
+        it += 1
+    cnt = np.bincount(comp, minlength=nc)
+    phi = phi - (np.bincount(comp, weights=phi, minlength=nc) / cnt)[comp]
+    known = anchor > 0 if anchor is not None else np.zeros(n, dtype=bool)
+    ka = np.bincount(comp[known], minlength=nc)
+    off = np.zeros(nc)
+    if known.any():
+        off = np.bincount(comp[known], weights=(np.log(anchor[known]) - phi[known]), minlength=nc) / np.maximum(ka, 1)
+    prices = np.exp(phi + off[comp])
+    if known.any():
+        prices[known] = anchor[known]
+    mis = phi[eu] - phi[ev] - lr
+    info = dict(relations=int(len(eu)), components=nc, components_anchored=int((ka > 0).sum()), tokens_unlisted=int((deg == 0).sum()),
+                iterations=it, status=status, residual=(rmax / rhs_max if rhs_max > 0 else 0.0),
+                misfit_max=float(np.abs(mis).max()) if len(mis) else 0.0, misfit_ss=float(mis @ mis), phi=phi, comp=comp)
+    return prices, info
+
+
 # ------------------------------------------------------------------------------- ties (kinks)
 class _Ties:
     """Weighted union-find over tokens: log nu_j = s[group(j)] + off[j]."""
@@ -1352,9 +1474,11 @@ class Problem:
     def net(self):
         """the packed network; a host copy that apply_trades(sync_host=False) left behind the device is refreshed on first use"""
         n = self._net
-        if n.get("_stale") and self.ctx is not None and self._uploaded:
+        if n.get("_stale") and self.ctx is not None and self._uploaded and not self._hold_refresh:
             self._refresh_net()
         return n
+
+    _hold_refresh = False          # inside solve(nu0="pools"): the solve reads the network's shape alone, the reserves stay on the device
 
     @net.setter
     def net(self, network):
@@ -1412,6 +1536,7 @@ class Problem:
             ctx._chk(rc)
             self._net["_stale"] = True
             self._reserves_changed()
+            self._rmax = float(info["max_reserve"])      # (the network's largest new reserve, exact: what _max_reserve would read back)
             if sync_host:
                 self._refresh_net()
             return int(info["pools_moved"])
@@ -1451,7 +1576,18 @@ class Problem:
         `audit`: audit the route the solve ends on (Problem.audit, docs/audit.md) and keep the report as self.audit_report; a status of
         "optimal" becomes "inaccurate" when a pool refuses its tenders, a contribution falls outside the fixed point, or the audited
         psi disagrees with the reported one -- or misses the certificates -- beyond the solve's tolerance."""
-        value = self._solve(tol, nu0, max_evals, memory, iters_per_graph, kink_tol, max_rounds, warm_start, method)
+        if isinstance(nu0, str) and nu0 != "pools":
+            raise ValueError(f"nu0 {nu0!r}: start prices, None, or \"pools\" (fitted on the device to the resident pools, pool_prices)")
+        # nu0="pools" on a host copy an apply left behind the device: nothing the solve reads of it but its shape, unless constant-sum
+        # pools (whose kink loop reads the host's reserves) are present or the largest reserve is not known -- then it is refreshed as ever
+        self._pools_seen()
+        self._hold_refresh = (isinstance(nu0, str) and self._host is None and self._comm is None and bool(self._net.get("_stale"))
+                              and getattr(self, "_rmax", None) is not None and "sum2" not in self._net
+                              and not any(kd == "sum" for kd, _ in self._net.get("gk", {})))
+        try:
+            value = self._solve(tol, nu0, max_evals, memory, iters_per_graph, kink_tol, max_rounds, warm_start, method)
+        finally:
+            self._hold_refresh = False
         self.audit_report = None
         if audit and self.psi is not None and np.all(np.isfinite(self.psi)):
             rep = self.audit_report = self.audit()
@@ -1498,6 +1634,15 @@ class Problem:
         dv = getattr(self, "dual_value", None)
         rep["gap"] = abs(dv - rep["value"]) / max(1.0, abs(dv)) if dv is not None else float("nan")
         return rep
+
+    def pool_prices(self, anchor=None):
+        """What is every token worth according to the resident pools, and how far do the pools disagree?  cfmm_pool_prices on the
+        device (docs/pool_prices.md), at the reserves, fees and weights the pools hold NOW -- after update_* and
+        apply_trades(sync_host=False) included; self.net is not read.  anchor: [n] known prices, 0 = unknown.  Returns (prices, info)
+        as the NumPy twin cfmm.problem.pool_prices does, info carrying phi and comp.  Needs no utility and no solve."""
+        if self._host is not None or self._comm is not None:
+            raise ValueError("pool_prices: pool-sharded problems are not served (cfmm.problem.pool_prices on the gathered network)")
+        return self._ensure_ctx().pool_prices(anchor, want_potential=True)
 
     def select(self, min_value=0.0):
         """Which pools of the route are worth executing?  Every pool is measured on the device by the value it takes in at the accepted
@@ -1624,6 +1769,11 @@ class Problem:
                 cnt = host.allreduce_sum(cnt)
             self._global_counts = cnt
         n_stable, n_sum = int(cnt[0]), int(cnt[1])
+        if isinstance(nu0, str):                      # "pools": fitted on the device to the resident pools; pool-sharded: the host path
+            anchor = start_anchor(u)
+            nu0 = None if host or self._comm is not None else (anchor.copy() if np.all(anchor > 0) else ctx.pool_prices(anchor)[0])
+            nu0_given = nu0
+            warm_start = False
         if nu0 is None:
             if warm_start and self.nu is not None and np.all(np.isfinite(self.nu)) and np.all(np.asarray(self.nu) > 0.0):
                 nu0 = self.nu                     # (a previous solve that ended on collapsed / non-finite prices is no warm start: cold instead)

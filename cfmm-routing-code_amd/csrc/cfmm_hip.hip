@@ -41,6 +41,7 @@
 #include "update.hpp"
 #include "apply.hpp"
 #include "audit.hpp"
+#include "prices.hpp"
 #include "subset.hpp"
 #include "handoff.hpp"
 #include "solve_plan.hpp"
@@ -228,6 +229,9 @@ struct cfmm_ctx {
     char *sel_dev = nullptr; size_t sel_cap = 0;
     char *sel_host = nullptr;
     route::Counts sel_counts = {};     // the buckets the masks were laid out for (read only while pt.sel_valid)
+    // cfmm_pool_prices (prices.hpp), made at the first call and grown with n and the buckets: the scratch of prices_rules.hpp's layout;
+    // pinned: its first `back` bytes read back.  timed (cfmm_debug_prices_launch): HIP events around the phases, made at the first timed call
+    struct { char *dev = nullptr, *host = nullptr; size_t cap = 0, host_cap = 0; bool timed = false; hipEvent_t ev[6] = {}; double sec[5] = {}; } prices;
 
     // tokens / state (device)
     double *c = nullptr, *h = nullptr, *off = nullptr, *glo = nullptr, *ghi = nullptr;
@@ -2445,6 +2449,9 @@ int cfmm_destroy(cfmm_ctx *ctx)
     if (ctx->audit_host) (void)hipHostFree(ctx->audit_host);
     if (ctx->sel_dev) (void)hipFree(ctx->sel_dev);
     if (ctx->sel_host) (void)hipHostFree(ctx->sel_host);
+    if (ctx->prices.dev) (void)hipFree(ctx->prices.dev);
+    if (ctx->prices.host) (void)hipHostFree(ctx->prices.host);
+    for (hipEvent_t e : ctx->prices.ev) if (e) (void)hipEventDestroy(e);
     if (ctx->sweep.dev) (void)hipFree(ctx->sweep.dev);
     if (ctx->sweep.host) (void)hipHostFree(ctx->sweep.host);
     if (ctx->sweep.tr_dev) (void)hipFree(ctx->sweep.tr_dev);
@@ -5453,6 +5460,141 @@ int cfmm_debug_audit_launch(cfmm_ctx *ctx, int timed, int grid, double *out2)
     ctx->audit_timed = timed != 0;
     if (grid > 0) ctx->audit_grid = grid;
     if (out2) { out2[0] = ctx->audit_sec; out2[1] = (double)ctx->audit_reordered; }
+    return CFMM_OK;
+}
+
+// ---- the prices the resident pools imply (prices.hpp; docs/pool_prices.md) -----------------------------------------------------------
+// On this context's stream, as a reader of the store like the read-backs: the scratch cleared, the relation pass, the components, the
+// iteration, the misfit pass, ONE copy (phi | degrees | labels | the iteration's record | the misfit partials, contiguous) and ONE
+// synchronisation; the gauge, the renumbering, the anchoring and the report are prices_rules.hpp's, on the host.  Nothing of the context
+// or the store is written: the scratch below is the call's own.
+namespace {
+struct PricesRun {
+    cfmm_ctx *ctx;
+    PoolStore &ps;
+    route::Counts counts;
+    prices::Layout l;
+};
+
+// the call's own scratch, grow-only
+int prices_reserve(PricesRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    auto &s = ctx->prices;
+    if (R.l.total > s.cap) {
+        if (s.dev) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(s.dev); s.dev = nullptr; s.cap = 0; }
+        HIP_TRY(ctx, hipMalloc((void **)&s.dev, R.l.total));
+        s.cap = R.l.total;
+    }
+    if (R.l.back > s.host_cap) {
+        if (s.host) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipHostFree(s.host); s.host = nullptr; s.host_cap = 0; }
+        HIP_TRY(ctx, hipHostMalloc((void **)&s.host, R.l.back));
+        s.host_cap = R.l.back;
+    }
+    if (s.timed) for (hipEvent_t &e : s.ev) if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    return CFMM_OK;
+}
+
+// one relation pass over every bucket: SINK 0 assembles rhs and the count matrix, SINK 1 measures the misfit of phi
+extern "C++" template <int SINK> int prices_pass(PricesRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    char *dev = ctx->prices.dev;
+    PricesArgs a;
+    a.n = ctx->n; a.ld = R.l.ld;
+    a.rhs = (double *)(dev + R.l.rhs); a.mat = (unsigned *)(dev + R.l.mat); a.phi = (const double *)(dev + R.l.phi);
+    const size_t lds = (size_t)ctx->n * sizeof(double);
+    const dim3 blk(PR_THREADS);
+    each_bucket(R.ps, [&](auto &r, int q, auto FAMILY, auto KIND, auto K) {
+        const auto &b = r.b;
+        const dim3 grid((unsigned)prices::rel_grid(b.m));
+        a.part = (double *)(dev + R.l.parts) + 2 * R.l.part_off[q];
+        if constexpr (FAMILY == 0) hipLaunchKernelGGL((prices2_kernel<KIND, SINK>), grid, blk, lds, ctx->stream, b, a);
+        else if constexpr (FAMILY == 1) hipLaunchKernelGGL((pricesN_kernel<K, SINK>), grid, blk, lds, ctx->stream, b, a);
+        else hipLaunchKernelGGL((pricesG_kernel<KIND, K, SINK>), grid, blk, lds, ctx->stream, b, a);
+    });
+    HIP_TRY(ctx, hipGetLastError());
+    return CFMM_OK;
+}
+
+// everything the device does, behind prices_reserve
+int prices_device(PricesRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    auto &s = ctx->prices;
+    const prices::Layout &l = R.l;
+    const int n = ctx->n;
+    int mark = 0;
+    auto stamp = [&]() { return s.timed ? hipEventRecord(s.ev[mark++], ctx->stream) : hipSuccess; };
+    HIP_TRY(ctx, stamp());
+    HIP_TRY(ctx, hipMemsetAsync(s.dev + l.clear_from, 0, l.total - l.clear_from, ctx->stream));
+    HIP_TRY(ctx, stamp());
+    { int rc = prices_pass<0>(R); if (rc) return rc; }
+    HIP_TRY(ctx, stamp());
+    PricesCg *cg = (PricesCg *)(s.dev + l.cg);
+    const unsigned *mat = (const unsigned *)(s.dev + l.mat);
+    hipLaunchKernelGGL(prices_components_kernel, dim3(1), dim3(PR_ONE), 2 * (size_t)l.ld * sizeof(int), ctx->stream, mat, n, l.ld, (int *)(s.dev + l.label), cg);
+    HIP_TRY(ctx, stamp());
+    hipLaunchKernelGGL(prices_cg_kernel, dim3(1), dim3(PR_ONE), (size_t)l.ld * sizeof(double), ctx->stream, mat, (const double *)(s.dev + l.rhs), n, l.ld,
+                       prices::iteration_cap(n), (double *)(s.dev + l.phi), (double *)(s.dev + l.r), (double *)(s.dev + l.q), (unsigned *)(s.dev + l.deg), cg);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, stamp());
+    { int rc = prices_pass<1>(R); if (rc) return rc; }
+    HIP_TRY(ctx, stamp());
+    HIP_TRY(ctx, hipMemcpyAsync(s.host, s.dev, l.back, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (s.timed)
+        for (int q = 0; q < 5; ++q) { float ms = 0.f; HIP_TRY(ctx, hipEventElapsedTime(&ms, s.ev[q], s.ev[q + 1])); s.sec[q] = ms * 1e-3; }
+    return CFMM_OK;
+}
+}  // namespace
+
+int cfmm_pool_prices(cfmm_ctx *ctx, const double *anchor, double *prices_out, double *log_potential, int32_t *component, cfmm_prices_info *info)
+{
+    const char *who = "pool_prices";
+    if (!ctx) return CFMM_E_ARG;
+    if (!prices_out) return fail(ctx, CFMM_E_ARG, "%s: prices is NULL", who);
+    const int n = ctx->n;
+    { const int j = prices::anchor_offender(anchor, n); if (j >= 0) return fail(ctx, CFMM_E_ARG, "%s: anchor[%d] = %g is neither 0 (unknown) nor a positive finite price", who, j, anchor[j]); }
+    if (sharded(ctx)) return fail(ctx, CFMM_E_UNSUPPORTED, "%s: pool-sharded contexts are not served (fit the shards' relations on the host)", who);
+    if (n > prices::MAX_TOKENS) return fail(ctx, CFMM_E_LIMIT, "%s: %d tokens exceed the iteration's LDS tile of n doubles (n <= %d)", who, n, prices::MAX_TOKENS);
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
+    PricesRun R{ctx, entry.ps, bucket_counts(entry.ps), {}};
+    const int64_t rel = prices::relations(R.counts);
+    if (rel >= (1ll << 32)) return fail(ctx, CFMM_E_LIMIT, "%s: %lld relations exceed the count matrix's 32-bit entries (< 2^32)", who, (long long)rel);
+    R.l = prices::layout(n, R.counts);
+    std::vector<double> phi((size_t)n, 0.0), sum((size_t)n);
+    std::vector<uint32_t> deg((size_t)n, 0u);
+    std::vector<int32_t> label((size_t)n), comp((size_t)n), cnt((size_t)n);
+    PricesCg cg = {};
+    prices::Misfit mf = {0.0, 0.0};
+    if (rel > 0) {
+        { int rc = prices_reserve(R); if (rc) return rc; }
+        { int rc = prices_device(R); if (rc) return rc; }
+        const char *h = ctx->prices.host;
+        std::memcpy(phi.data(), h + R.l.phi, (size_t)n * sizeof(double));
+        std::memcpy(deg.data(), h + R.l.deg, (size_t)n * sizeof(uint32_t));
+        std::memcpy(label.data(), h + R.l.label, (size_t)n * sizeof(int32_t));
+        std::memcpy(&cg, h + R.l.cg, sizeof cg);
+        mf = prices::fold_misfit((const double *)(h + R.l.parts), R.l, R.counts);
+    } else {
+        for (int j = 0; j < n; ++j) label[j] = j;              // no pools: every token is its own component
+    }
+    const int nc = prices::renumber(label.data(), n, comp.data());
+    if (nc < 0) return fail(ctx, CFMM_E_NUMERIC, "%s: the component labels came back inconsistent", who);
+    prices::gauge(phi.data(), comp.data(), n, nc, sum.data(), cnt.data());
+    const int anchored = prices::anchor_prices(phi.data(), comp.data(), n, nc, anchor, prices_out, sum.data(), cnt.data());
+    if (log_potential) std::memcpy(log_potential, phi.data(), (size_t)n * sizeof(double));
+    if (component) std::memcpy(component, comp.data(), (size_t)n * sizeof(int32_t));
+    if (info) prices::fold_info(R.counts, deg.data(), n, nc, anchored, cg, mf, info);
+    return CFMM_OK;
+}
+
+int cfmm_debug_prices_launch(cfmm_ctx *ctx, int timed, double *out5)
+{
+    if (!ctx) return CFMM_E_ARG;
+    ctx->prices.timed = timed != 0;
+    if (out5) for (int q = 0; q < 5; ++q) out5[q] = ctx->prices.sec[q];
     return CFMM_OK;
 }
 

@@ -364,6 +364,47 @@ typedef struct {
     int64_t count[CFMM_BUCKET_SLOTS];
 } cfmm_pool_lists;
 int cfmm_subnetwork(cfmm_ctx *src, const cfmm_pool_lists *lists /* or NULL */, cfmm_ctx **out);
+/* The prices the resident pools imply (docs/pool_prices.md).  Every pool contributes relations  log p_u - log p_v = lr  at its CURRENT
+ * resident reserves, fees and weights: a two-asset pool one, (ia, ib); a k-asset pool k - 1, leg j against leg 0.  lr is the pool's
+ * marginal log-price ratio at zero trade: log(Rb / Ra) (constant product), log(wa Rb / ((1 - wa) Ra)) (weighted), 0 (constant sum, two
+ * assets or k), t log(Rb / Ra) (power sum), log((1 + alpha / (Ra Ra Rb)) / (1 + alpha / (Ra Rb Rb))) (two-asset stableswap),
+ * log(w_j R_0 / (w_0 R_j)) (geo-mean), log1p(s / R_j) - log1p(s / R_0) with s = alpha / prod R (k-asset stableswap).  Every pool
+ * counts, with unit weight, tie flags or not (flags describe a solve, not the reserves).
+ *   phi       minimises sum (phi_u - phi_v - lr)^2: L phi = rhs on the multigraph Laplacian, zero mean on every connected component
+ *             of the token graph; a token no pool lists is a component of its own with phi = 0.  Solved on the device by
+ *             Jacobi-preconditioned conjugate gradients from zero, stopped at max |r| <= 1e-12 max |rhs| or after 4 n + 100 iterations
+ *             (status 1; the prices are still returned).
+ *   anchor    anchor[j] > 0 and finite: the price of token j is known; 0 (or anchor == NULL): unknown.  On a component with anchored
+ *             tokens log p = phi + off, off the mean of log anchor - phi over its anchored tokens summed in token order, and anchored
+ *             tokens are returned bit for bit as given; a component without one returns exp(phi) (geometric-mean price 1).
+ *   prices    [n], required.  log_potential: the gauged phi.  component: labels 0.., numbered by each component's first token.
+ * Needs uploaded pools only -- no utility, no prices, no solve; a context without pools is served (every token its own component).
+ * The call reads the pools like cfmm_get_trades* and changes nothing a later call can see: no pool column, no warm start of the table's
+ * root search, no generation, no accepted prices, no cached solution, no barrier warm start, no Cholesky factor, no captured launch;
+ * its scratch is its own (grow-only, made at the first call, freed by cfmm_destroy).  An in-place update through a context sharing the
+ * pools is refused meanwhile; a call made after an update sees the updated pools.  One synchronisation, one staged copy back.
+ * Refusals: prices == NULL, or an anchor entry that is negative, NaN or infinite -> CFMM_E_ARG; a pool-sharded context ->
+ * CFMM_E_UNSUPPORTED; more than 6144 tokens (the workgroup's tile of the direction vector) or 2^32 relations -> CFMM_E_LIMIT. */
+typedef struct {
+    int64_t relations;            /* 1 per two-asset pool, k - 1 per k-asset pool */
+    int32_t components;           /* unlisted tokens count one each */
+    int32_t components_anchored;
+    int32_t tokens_unlisted;
+    int32_t iterations;           /* of the iterative solve (0 if direct) */
+    int32_t status;               /* 0 converged; 1 iteration cap reached */
+    double residual;              /* max |L phi - rhs| / max |rhs| at return (the iteration's own residual); 0 when rhs == 0 */
+    double misfit_max, misfit_ss; /* max and sum of squares of phi_u - phi_v - lr over all relations */
+} cfmm_prices_info;
+
+int cfmm_pool_prices(cfmm_ctx *ctx, const double *anchor /* [n] or NULL */,
+                     double *prices /* [n] */,
+                     double *log_potential /* [n] or NULL */,
+                     int32_t *component /* [n] or NULL: labels 0.., numbered by first token */,
+                     cfmm_prices_info *info /* or NULL */);
+/* measurement hook of the call's launches (tools/prices_timing.py), not part of the product's interface: with `timed`, every
+ * cfmm_pool_prices brackets its phases with HIP events; out5 (or NULL) receives the seconds of the last timed call's {clear, relation
+ * pass, components, iteration, misfit pass} */
+int cfmm_debug_prices_launch(cfmm_ctx *ctx, int timed, double *out5);
 /* constant-sum pools sitting on their kink are `tied` (flag 1): they are skipped by the
  * kernels and their fill fraction is assigned by the host's primal recovery */
 int cfmm_set_pool_flags(cfmm_ctx *ctx, int kind, const int32_t *flags /* [m] or NULL */);
