@@ -69,6 +69,25 @@ class Audit(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RouteInfo(C.Structure):
+    """cfmm_route_info: what cfmm_hold_route holds (docs/requote.md)"""
+    _fields_ = [("pools", C.c_int64), ("pools_trading", C.c_int64), ("bytes", C.c_int64)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Requote(C.Structure):
+    """cfmm_requote: the report of cfmm_requote_route (docs/requote.md)"""
+    _fields_ = [("pools", C.c_int64), ("pools_trading", C.c_int64), ("pools_short", C.c_int64), ("pools_long", C.c_int64),
+                ("pools_capped", C.c_int64), ("pools_failed", C.c_int64), ("legs_out_of_range", C.c_int64),
+                ("min_family", C.c_int32), ("min_kind", C.c_int32), ("min_k", C.c_int32), ("fixed_exponent", C.c_int32),
+                ("min_pos", C.c_int64), ("min_scale", C.c_double), ("value", C.c_double), ("infeas", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 BUCKET_SLOTS = 32                      # include/cfmm.h: CFMM_BUCKET_SLOTS
 
 
@@ -127,7 +146,7 @@ assert _STATS_STRUCT.size == C.sizeof(Stats)
 
 def build(force=False):
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp", "update.hpp", "apply.hpp", "audit.hpp", "solve_plan.hpp", "newton_rules.hpp", "sweep_rules.hpp", "route_rules.hpp", "update_rules.hpp", "subset.hpp", "subset_rules.hpp", "prices.hpp", "prices_rules.hpp", "tiny_limits.hpp", "fixedpoint.hpp")]
+    srcs = [os.path.join(_CSRC, f) for f in ("cfmm_hip.hip", "kernels.hpp", "iterate.hpp", "tiny.hpp", "onewave.hpp", "reorder.hpp", "oneshot.hpp", "pool_math.hpp", "phi2.hpp", "lbfgs_rules.hpp", "smooth.hpp", "chol.hpp", "chol2.hpp", "phik.hpp", "handoff.hpp", "update.hpp", "apply.hpp", "audit.hpp", "requote.hpp", "requote_rules.hpp", "solve_plan.hpp", "newton_rules.hpp", "sweep_rules.hpp", "route_rules.hpp", "update_rules.hpp", "subset.hpp", "subset_rules.hpp", "prices.hpp", "prices_rules.hpp", "tiny_limits.hpp", "fixedpoint.hpp")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "cfmm.h"))
     if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _CSRC, "-s"])
@@ -139,7 +158,7 @@ _lib = None
 SYMBOLS = ["cfmm_create", "cfmm_clone", "cfmm_destroy", "cfmm_last_error", "cfmm_backend", "cfmm_default_opts",
            "cfmm_upload_pools2", "cfmm_upload_poolsN", "cfmm_upload_poolsG", "cfmm_update_pools2", "cfmm_update_poolsN", "cfmm_update_poolsG",
            "cfmm_update_terms2", "cfmm_update_termsN", "cfmm_update_termsG",
-           "cfmm_apply_trades", "cfmm_get_reserves2", "cfmm_get_reservesN", "cfmm_get_reservesG", "cfmm_apply_timers", "cfmm_audit_trades", "cfmm_debug_audit_launch", "cfmm_select_pools", "cfmm_get_selected2", "cfmm_get_selectedN", "cfmm_get_selectedG", "cfmm_subnetwork", "cfmm_pool_prices", "cfmm_debug_prices_launch", "cfmm_set_pool_flags", "cfmm_set_pool_flagsG", "cfmm_set_utility",
+           "cfmm_apply_trades", "cfmm_get_reserves2", "cfmm_get_reservesN", "cfmm_get_reservesG", "cfmm_apply_timers", "cfmm_audit_trades", "cfmm_debug_audit_launch", "cfmm_hold_route", "cfmm_release_route", "cfmm_get_held2", "cfmm_get_heldN", "cfmm_get_heldG", "cfmm_requote_route", "cfmm_get_route_scale2", "cfmm_get_route_scaleN", "cfmm_get_route_scaleG", "cfmm_debug_requote_launch", "cfmm_select_pools", "cfmm_get_selected2", "cfmm_get_selectedN", "cfmm_get_selectedG", "cfmm_subnetwork", "cfmm_pool_prices", "cfmm_debug_prices_launch", "cfmm_set_pool_flags", "cfmm_set_pool_flagsG", "cfmm_set_utility",
            "cfmm_set_ties", "cfmm_set_deterministic", "cfmm_debug_eval_limbs", "cfmm_debug_scatter_limbs", "cfmm_eval_dual", "cfmm_eval_smooth", "cfmm_debug_cholesky", "cfmm_debug_cholesky_apply", "cfmm_time_xcd_handoff", "cfmm_solve", "cfmm_solve_batch", "cfmm_eval_dual_batch", "cfmm_batch_capacity", "cfmm_solve_sweep", "cfmm_get_nu", "cfmm_set_nu", "cfmm_get_psi",
            "cfmm_get_solution", "cfmm_get_trades2", "cfmm_get_tradesN", "cfmm_get_tradesG", "cfmm_comm_unique_id", "cfmm_comm_init",
            "cfmm_oneshot_export", "cfmm_oneshot_import", "cfmm_oneshot_attach", "cfmm_oneshot_mailbox", "cfmm_oneshot_enable",
@@ -178,6 +197,16 @@ def lib():
     L.cfmm_apply_timers.argtypes = [vp, C.c_int, dp]
     L.cfmm_audit_trades.argtypes = [vp, C.POINTER(AuditTenders), C.c_double, C.POINTER(Audit), dp, C.POINTER(C.c_uint64)]
     L.cfmm_debug_audit_launch.argtypes = [vp, C.c_int, C.c_int, dp]
+    L.cfmm_hold_route.argtypes = [vp, C.POINTER(RouteInfo)]
+    L.cfmm_release_route.argtypes = [vp]
+    L.cfmm_get_held2.argtypes = [vp, C.c_int, dp, dp]
+    L.cfmm_get_heldN.argtypes = [vp, C.c_int, dp, dp]
+    L.cfmm_get_heldG.argtypes = [vp, C.c_int, C.c_int, dp, dp]
+    L.cfmm_requote_route.argtypes = [vp, C.c_double, C.POINTER(Requote), dp, C.POINTER(C.c_uint64)]
+    L.cfmm_get_route_scale2.argtypes = [vp, C.c_int, dp]
+    L.cfmm_get_route_scaleN.argtypes = [vp, C.c_int, dp]
+    L.cfmm_get_route_scaleG.argtypes = [vp, C.c_int, C.c_int, dp]
+    L.cfmm_debug_requote_launch.argtypes = [vp, C.c_int, C.c_int, dp]
     L.cfmm_select_pools.argtypes = [vp, C.c_double, C.POINTER(SelectInfo)]
     L.cfmm_get_selected2.argtypes = [vp, C.c_int, ip, C.c_int64, C.POINTER(C.c_int64)]
     L.cfmm_get_selectedN.argtypes = [vp, C.c_int, ip, C.c_int64, C.POINTER(C.c_int64)]
@@ -493,6 +522,75 @@ class Context:
         out = np.zeros(2)
         self._chk(self.L.cfmm_debug_audit_launch(self.h, 1 if timed else 0, int(grid), _d(out)))
         return float(out[0]), int(out[1])
+
+    def hold_route(self, check=True):
+        """cfmm_hold_route: keep the tenders get_trades* would return now on the device, through every later update, apply and solve
+        (docs/requote.md).  Returns the info record as a dict; check=False: (return code, dict) instead of raising on a refusal"""
+        info = RouteInfo()
+        rc = self.L.cfmm_hold_route(self.h, C.byref(info))
+        if not check:
+            return int(rc), info.asdict()
+        self._chk(rc)
+        return info.asdict()
+
+    def release_route(self):
+        self._chk(self.L.cfmm_release_route(self.h))
+
+    def requote(self, tol_scale=0.0, want_limbs=False, check=True):
+        """cfmm_requote_route: the held route with its inputs fixed and every pool's outputs scaled onto its curve at the reserves, fees
+        and weights resident NOW (docs/requote.md).  Returns the report as a dict with "psi" [n] (and "limbs" [3][n] uint64 with
+        want_limbs); check=False: (return code, dict) instead of raising"""
+        rep = Requote()
+        psi = np.zeros(self.n)
+        limbs = np.zeros((3, self.n), dtype=np.uint64) if want_limbs else None
+        rc = self.L.cfmm_requote_route(self.h, float(tol_scale), C.byref(rep), _d(psi),
+                                       limbs.ctypes.data_as(C.POINTER(C.c_uint64)) if want_limbs else None)
+        out = rep.asdict()
+        out["psi"] = psi
+        if want_limbs:
+            out["limbs"] = limbs
+        if not check:
+            return int(rc), out
+        self._chk(rc)
+        return out
+
+    def debug_requote_launch(self, timed=False, grid=0):
+        """(seconds of the last re-quote's launches by HIP events, buckets it found stored reordered); switches the events on / off;
+        grid > 0: workgroups per pass from now on (test and measurement hook)"""
+        out = np.zeros(2)
+        self._chk(self.L.cfmm_debug_requote_launch(self.h, 1 if timed else 0, int(grid), _d(out)))
+        return float(out[0]), int(out[1])
+
+    def _pair(self, call, k, m):
+        d = np.zeros((k, m)); l = np.zeros((k, m))
+        self._chk(call(_d(d), _d(l)))          # (an empty bucket writes nothing; a missing hold is refused either way)
+        return d, l
+
+    def held2(self, kind, m):
+        """the held tenders (delta, lambda) [2][m] of a two-asset bucket, in the shapes of get_trades2"""
+        return self._pair(lambda d, l: self.L.cfmm_get_held2(self.h, int(kind), d, l), 2, m)
+
+    def heldN(self, k, m):
+        return self._pair(lambda d, l: self.L.cfmm_get_heldN(self.h, int(k), d, l), k, m)
+
+    def heldG(self, kind, k, m):
+        return self._pair(lambda d, l: self.L.cfmm_get_heldG(self.h, int(kind), int(k), d, l), k, m)
+
+    def route_scale2(self, kind, m):
+        """the scales [m] of the last re-quote for a two-asset bucket, upload order: 1 = not trading, NaN = failed"""
+        s = np.ones(m)
+        self._chk(self.L.cfmm_get_route_scale2(self.h, int(kind), _d(s)))
+        return s
+
+    def route_scaleN(self, k, m):
+        s = np.ones(m)
+        self._chk(self.L.cfmm_get_route_scaleN(self.h, int(k), _d(s)))
+        return s
+
+    def route_scaleG(self, kind, k, m):
+        s = np.ones(m)
+        self._chk(self.L.cfmm_get_route_scaleG(self.h, int(kind), int(k), _d(s)))
+        return s
 
     def get_reserves2(self, kind, m, with_param=False):
         """resident reserves (Ra, Rb[, param]) of a two-asset bucket of m pools, in upload order"""

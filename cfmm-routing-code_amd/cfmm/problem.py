@@ -480,6 +480,176 @@ def audit_trades(net, trades, utility=None, tol_pool=AUDIT_TOL_POOL, exponent=No
     return rep
 
 
+# ------------------------------------------------------------------------------- a held route re-quoted (docs/requote.md)
+REQUOTE_TOL_SCALE = 1e-9   # the default tol_scale: the audit's tol_pool
+
+
+def requote_slack(b, up, L, s):
+    """the slack of every pool of one bucket (a record of audit_buckets) at the scales s [m]: the audit's expression per class on
+    x = up - s L with up = R + gamma Delta already formed, every operation rounded on its own, sums and products in leg order"""
+    R, k = b["R"], b["k"]
+    m = R.shape[1]
+    with np.errstate(all="ignore"):
+        x = up - s * L
+        Sx = np.zeros(m); SR = np.zeros(m)
+        for j in range(k):
+            Sx = Sx + x[j]; SR = SR + R[j]
+        if b["cls"] == "log":
+            F = np.zeros(m)
+            for j in range(k):
+                F = F + b["w"][j] * np.log(x[j] / R[j])
+        elif b["cls"] == "sum":
+            F = (Sx - SR) / SR
+        elif b["cls"] == "stable":
+            Px = np.ones(m); PR = np.ones(m)
+            for j in range(k):
+                Px = Px * x[j]; PR = PR * R[j]
+            cx, cR = b["alpha"] / Px, b["alpha"] / PR
+            F = ((Sx - cx) - (SR - cR)) / (SR + cR)
+        else:
+            fx = np.zeros(m); fR = np.zeros(m)
+            for j in range(k):
+                fx = fx + np.power(x[j], b["e"]); fR = fR + np.power(R[j], b["e"])
+            F = (fx - fR) / fR
+    return F
+
+
+def _take(b, sel):
+    """the pools `sel` of a bucket record"""
+    out = dict(b)
+    for key in ("R", "w", "idx"):
+        if key in b:
+            out[key] = b[key][:, sel]
+    for key in ("fee", "alpha", "e"):
+        if key in b:
+            out[key] = b[key][sel]
+    return out
+
+
+def requote_bucket(b, D, L, scales=None):
+    """one bucket of requote_route: (s [m], trading, capped, failed -- boolean [m]).  The cap, the special cases and the verdicts are the
+    device's (csrc/requote.hpp); the root, with scales=None, is found by bisection on the bracket [0, s_cap] down to adjacent doubles
+    and is the lower one: the last s whose own slack evaluation is >= 0"""
+    R, g = b["R"], b["fee"]
+    m = R.shape[1]
+    fin = lambda a: np.isfinite(a) & (a >= 0.0)
+    with np.errstate(all="ignore"):
+        up = R + g * D
+        trading = ((D != 0.0) | (L != 0.0)).any(axis=0)
+        ok = (fin(D) & fin(L) & fin(up)).all(axis=0)
+        SD = np.zeros(m); SL = np.zeros(m)
+        for j in range(b["k"]):
+            SD = SD + D[j]; SL = SL + L[j]
+        c = up / L
+        for _ in range(6):
+            over = (c * L > up) if b["cls"] == "sum" else (c * L >= up)          # (only a constant-sum leg may be drained to zero)
+            c = np.where((L > 0.0) & (c > 0.0) & over, np.nextafter(c, 0.0), c)
+        cap = np.where(L > 0.0, c, np.inf).min(axis=0)
+        failed = trading & (~ok | ((SL > 0.0) & ~fin(cap)))
+        live = trading & ~failed
+        s = np.ones(m)
+        s[live & (SL > 0.0) & ~(SD > 0.0)] = 0.0
+        act = live & (SL > 0.0) & (SD > 0.0)
+        capped = np.zeros(m, dtype=bool)
+        if b["cls"] == "sum":
+            sv = (g * SD) / SL
+            bad = act & ~fin(sv)
+            capped = act & ~bad & (sv > cap)
+            s = np.where(act, np.where(capped, cap, sv), s)
+            failed |= bad
+        else:
+            bad = act & ~(requote_slack(b, up, L, np.zeros(m)) >= 0.0)
+            capped = act & ~bad & (requote_slack(b, up, L, np.where(act, cap, 0.0)) >= 0.0)
+            s = np.where(capped, cap, s)
+            failed |= bad
+            idx = np.flatnonzero(act & ~bad & ~capped)
+            if scales is None and len(idx):
+                bb, ub, Lb = _take(b, idx), up[:, idx], L[:, idx]
+                lo, hi = np.zeros(len(idx)), cap[idx].copy()
+                for _ in range(2400):
+                    mid = lo + 0.5 * (hi - lo)
+                    inside = (mid > lo) & (mid < hi)
+                    if not inside.any():
+                        break
+                    above = requote_slack(bb, ub, Lb, mid) >= 0.0
+                    lo = np.where(inside & above, mid, lo); hi = np.where(inside & ~above, mid, hi)
+                s[idx] = lo
+        s = np.where(failed, np.nan, s)
+        if scales is not None:
+            s = np.asarray(scales, dtype=np.float64).copy()
+    return s, trading, capped, failed
+
+
+def psi_worth(net, psi, utility):
+    """(value, infeas) of a net trade under a utility: the host expression of cfmm_audit / cfmm_requote (csrc/route_rules.hpp: psi_worth)"""
+    n = len(psi)
+    c, h, ct = utility.c, utility.h, utility.ctype
+    r = psi + h
+    lin = ct <= FREE
+    with np.errstate(all="ignore"):
+        terms = np.where(ct == ULOG, c * np.log(np.where(ct == ULOG, r, 1.0)),
+                         np.where(ct == UQUAD, c * psi - psi * psi / (2.0 * np.where(ct == UQUAD, h, 1.0)), c * psi))
+    value = 0.0
+    for t in terms.tolist():
+        value += t
+    viol = float(np.where(ct == GE, np.maximum(-r, 0.0), np.where(ct == EQ, np.abs(r), 0.0)).max()) if n else 0.0
+    scale = max(float(np.abs(psi).max()) if n else 0.0, float(np.abs(h[lin]).max()) if lin.any() else 0.0)
+    mr = max((float(b["R"].max()) for b in audit_buckets(net)), default=0.0)
+    return value, viol / max(scale, 1e-12 * mr, 1e-300)
+
+
+def requote_route(net, held, utility=None, scales=None, tol_scale=REQUOTE_TOL_SCALE, exponent=None):
+    """What does a held route pay on the pools as they are now?  The NumPy twin of cfmm_requote_route (include/cfmm.h, docs/requote.md),
+    the host path of Problem.requote and the reference of the tests.  net: the packed network at its CURRENT reserves, fees and weights;
+    held: {bucket key: (delta, lambda)}, slot-major [k][m] in upload order, as Problem._trades builds it.  Per trading pool the inputs
+    stay and the outputs are scaled onto the curve: x_j(s) = (R_j + gamma Delta_j) - s Lambda_j with s the root of the audit's slack,
+    Lambda'_j = fl(s Lambda_j).  scales=None: every root is found here in fp64 by bisection to the last bit that changes the slack's
+    sign; scales = {key: s [m]} (the device's): they are used as they are and only the tenders, the integers, limbs, psi and the report
+    are formed -- bit for bit the device's.  exponent: F of the fixed point (None: audit_exponent(net)).
+    Returns the fields of cfmm_requote plus psi [n], psi_int, limbs [3][n] uint64, scale {key: [m]} and lambdas {key: [k][m]}."""
+    import math
+    n = int(net["n_tokens"])
+    tol = float(tol_scale) if tol_scale is not None and tol_scale > 0 else REQUOTE_TOL_SCALE
+    F = audit_exponent(net) if exponent is None else int(exponent)
+    L0 = np.zeros(n, dtype=np.uint64); L1 = np.zeros(n, dtype=np.uint64); L2 = np.zeros(n, dtype=np.int64)
+    rep = dict(pools=0, pools_trading=0, pools_short=0, pools_long=0, pools_capped=0, pools_failed=0, legs_out_of_range=0,
+               min_family=-1, min_kind=-1, min_k=-1, fixed_exponent=F, min_pos=-1, min_scale=np.inf, value=np.nan, infeas=np.nan)
+    scale, lambdas = {}, {}
+    with np.errstate(all="ignore"):
+        for b in audit_buckets(net):
+            key = b["key"]
+            D, L = (np.asarray(a, dtype=np.float64) for a in held[key])
+            s, trading, capped, failed = requote_bucket(b, D, L, None if scales is None else scales[key])
+            live = trading & ~failed
+            Lp = s * L
+            scale[key], lambdas[key] = s, Lp
+            rep["pools"] += len(s)
+            rep["pools_trading"] += int(trading.sum())
+            rep["pools_short"] += int((live & (s < 1.0 - tol)).sum())
+            rep["pools_long"] += int((live & (s > 1.0 + tol)).sum())
+            rep["pools_capped"] += int(capped.sum())
+            rep["pools_failed"] += int(failed.sum())
+            if live.any():
+                sl = np.where(live, s, np.inf)
+                i = int(np.argmin(sl))                                         # (the first of equals: the lowest upload position)
+                if sl[i] < rep["min_scale"]:                                   # (strictly: ties go to the first bucket)
+                    rep.update(min_scale=float(sl[i]), min_family=b["family"], min_kind=b["kind"], min_k=b["k"], min_pos=i)
+            for y, sign in ((Lp, 1.0), (D, -1.0)):
+                sel = (y != 0.0) & live[None, :]
+                yv, tok = sign * y[sel], b["idx"][sel]
+                ok = np.abs(np.ldexp(yv, F)) < 2.0 ** 94
+                rep["legs_out_of_range"] += int((~ok).sum())
+                a0, a1, a2 = _fixed_limbs(yv[ok], F)
+                np.add.at(L0, tok[ok], a0); np.add.at(L1, tok[ok], a1); np.add.at(L2, tok[ok], a2)
+    limbs = np.stack([L0, L1, L2.view(np.uint64)])
+    psi_int = [(int(L2[j]) << 64) + (int(L1[j]) << 32) + int(L0[j]) for j in range(n)]
+    psi = np.array([math.ldexp(float(v), -F) for v in psi_int], dtype=np.float64).reshape(n)
+    rep.update(psi=psi, psi_int=psi_int, limbs=limbs, scale=scale, lambdas=lambdas)
+    if utility is not None:
+        rep["value"], rep["infeas"] = psi_worth(net, psi, utility)
+    return rep
+
+
 def apply_path(theta, dev_ties, sharded):
     """where Problem.apply_trades forms the new reserves: "device" (cfmm_apply_trades: no host leg) unless fills are held on the
     host (`theta`: the Python kink loop's), price ties / tie flags sit on the device, or the pools are sharded -- then "host\""""
@@ -1013,6 +1183,7 @@ class Problem:
         self.ctx = None
         self._uploaded = False
         self.value = None; self.status = None; self.psi = None; self.nu = None
+        self._held_route = None            # hold_route: where the held route is kept, with psi and value of that moment
         self.gap = None; self.infeas = None; self.dual_value = None; self.stats = None
         self._theta = {}
         self._trade_cache = None
@@ -1633,6 +1804,111 @@ class Problem:
             rep["psi_mismatch"] = float("nan")
         dv = getattr(self, "dual_value", None)
         rep["gap"] = abs(dv - rep["value"]) / max(1.0, abs(dv)) if dv is not None else float("nan")
+        return rep
+
+    # -- the pools moved before the route landed (include/cfmm.h: cfmm_hold_route, cfmm_requote_route; docs/requote.md) -----------
+    def _bucket_keys(self):
+        net = self._net
+        return [k for k in KIND2 if k in net] + list(net.get("gn", {})) + list(net.get("gk", {}))
+
+    def hold_route(self):
+        """Keep the route this object hands out now (deltas / lambdas / bucket_trades) through whatever happens to the pools next --
+        update_reserves / update_fees / update_weights, apply_trades, another solve, through this Problem or a clone -- together with
+        self.psi and self.value of this moment.  On the device (cfmm_hold_route: no tender crosses the host) unless fills are held in
+        Python, ties sit on the device or the pools are sharded: then the tenders are kept here.  Returns the info record."""
+        ctx = self._ensure_ctx()
+        self._pools_seen()
+        kept = dict(psi=None if self.psi is None else np.array(self.psi, copy=True), value=self.value)
+        if self._apply_path() == "device":
+            info = ctx.hold_route()
+            kept["path"] = "device"
+        else:
+            tr = {key: (d.copy(), l.copy()) for key, (d, l) in self._trades().items()}
+            kept.update(path="host", trades=tr)
+            info = dict(pools=int(sum(d.shape[1] for d, _ in tr.values())),
+                        pools_trading=int(sum(((d != 0) | (l != 0)).any(axis=0).sum() for d, l in tr.values())),
+                        bytes=int(sum(d.nbytes + l.nbytes for d, l in tr.values())))
+        self._held_route = kept
+        return info
+
+    def release_route(self):
+        """let the held route go (a no-op without one)"""
+        if self._held_route is not None and self._held_route["path"] == "device" and self.ctx is not None:
+            self.ctx.release_route()
+        self._held_route = None
+
+    def held_trades(self):
+        """{bucket key: (delta, lambda)} of the held route, read back from where it is kept"""
+        kept = self._held_route
+        if kept is None:
+            raise CfmmError("no route is held (hold_route first)", code=_lib.E_STATE)
+        if kept["path"] == "host":
+            return kept["trades"]
+        ctx, out = self._ensure_ctx(), {}
+        for key in self._bucket_keys():
+            b, fam = _bucket_of(self._net, key)
+            if fam == "two":
+                out[key] = ctx.held2(KIND2[key], len(b["Ra"]))
+            elif fam == "gn":
+                out[key] = ctx.heldN(int(key), b["R"].shape[1])
+            else:
+                out[key] = ctx.heldG(_lib.POOLK[key[0]], key[1], b["R"].shape[1])
+        return out
+
+    def requote(self, tol_scale=REQUOTE_TOL_SCALE):
+        """What does the held route pay on the pools as they are NOW, which pools fall short, and is it still worth sending?  The
+        report of cfmm_requote_route (docs/requote.md) as a dict with psi, plus
+          shortfall    psi_held - psi: what the route delivers less (per token) than when it was quoted
+          value_held   self.value at the hold
+          scale        {bucket key: s [m]}: 1 = not trading, NaN = failed
+          lambdas      the re-quoted outputs fl(s Lambda) -- in the order of self.lambdas for a Problem built from pool lists, else
+                       {bucket key: [k][m]}; deltas: the inputs, the held ones unchanged, in the same order (self.deltas itself
+                       follows the pools: once they have moved it hands out another route)
+        On the device unless the route is held here (hold_route): then the NumPy twin (requote_route) on the reserves read back."""
+        kept = self._held_route
+        if kept is None:
+            raise CfmmError("no route is held (hold_route first)", code=_lib.E_STATE)
+        ctx = self._ensure_ctx()
+        self._pools_seen()
+        if self.utility is not None:
+            self._send_utility()
+        if kept["path"] == "host":
+            net = dict(self._net)
+            for key, R in self.reserves().items():
+                b, fam = _bucket_of(self._net, key)
+                nb = dict(b)
+                if fam == "two":
+                    nb["Ra"], nb["Rb"] = R[0], R[1]
+                    net[key] = nb
+                else:
+                    nb["R"] = R
+                    net["gn" if fam == "gn" else "gk"] = dict(net["gn" if fam == "gn" else "gk"])
+                    net["gn" if fam == "gn" else "gk"][int(key) if fam == "gn" else key] = nb
+            rep = requote_route(net, kept["trades"], self.utility, None, tol_scale)
+            rep = {k: v for k, v in rep.items() if k not in ("psi_int", "limbs")}
+            rep["path"] = "host"
+            lam, held = rep["lambdas"], kept["trades"]
+        else:
+            rep = ctx.requote(tol_scale=tol_scale)
+            rep["path"] = "device"
+            held, scale, lam = self.held_trades(), {}, {}
+            for key in self._bucket_keys():
+                b, fam = _bucket_of(self._net, key)
+                if fam == "two":
+                    scale[key] = ctx.route_scale2(KIND2[key], len(b["Ra"]))
+                elif fam == "gn":
+                    scale[key] = ctx.route_scaleN(int(key), b["R"].shape[1])
+                else:
+                    scale[key] = ctx.route_scaleG(_lib.POOLK[key[0]], key[1], b["R"].shape[1])
+                lam[key] = scale[key] * held[key][1]
+            rep["scale"] = scale
+        dlt = {key: d for key, (d, _) in held.items()}
+        if self.where is not None:
+            lam = [lam[key][:, pos].copy() for key, pos in self.where]
+            dlt = [dlt[key][:, pos].copy() for key, pos in self.where]
+        rep["lambdas"], rep["deltas"] = lam, dlt
+        rep["value_held"] = kept["value"]
+        rep["shortfall"] = kept["psi"] - rep["psi"] if kept["psi"] is not None else None
         return rep
 
     def pool_prices(self, anchor=None):

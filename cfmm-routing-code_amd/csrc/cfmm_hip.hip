@@ -41,6 +41,7 @@
 #include "update.hpp"
 #include "apply.hpp"
 #include "audit.hpp"
+#include "requote.hpp"
 #include "prices.hpp"
 #include "subset.hpp"
 #include "handoff.hpp"
@@ -223,6 +224,16 @@ struct cfmm_ctx {
     int audit_grid = AU_GRID;          // ... and the workgroups per pass
     double audit_sec = 0.0;
     int audit_reordered = 0;           // buckets the last audit found stored reordered (perm non-null)
+    // the held route (requote.hpp; cfmm_hold_route): one arena laid out by requote_rules.hpp's hold_layout for the buckets as they were
+    // counted at the hold -- every bucket's tenders, then every bucket's scales.  An upload through this context outdates it
+    // (pools_changed); nothing else does.  The re-quote's scratch and hooks are shaped like the audit's
+    struct {
+        double *dev = nullptr; size_t cap = 0;
+        route::Counts counts = {};
+        bool valid = false, scaled = false;            // a route is held; the scales of a re-quote of it are in place
+        char *rq_dev = nullptr, *rq_host = nullptr;
+        bool timed = false; int grid = RQ_GRID; double sec = 0.0; int reordered = 0;
+    } held;
     double apply_sec[2] = {0.0, 0.0};  // ... of the last apply: the pass that checks, the pass that writes
     // cfmm_select_pools (subset.hpp), made at the first selection and grown with the buckets: the arena of subset_rules.hpp's layout
     // (records | partials | mask words | the compaction's counts); pinned: the records read back | the compaction's total
@@ -854,6 +865,7 @@ void reserves_moved(cfmm_ctx *ctx)
 void pools_changed(cfmm_ctx *ctx)
 {
     reserves_moved(ctx);
+    ctx->held.valid = ctx->held.scaled = false;      // (a held route's positions no longer mean anything)
     ctx->listed_valid = false;             // (a re-upload only: an update moves reserves, never the token ids the list is made of)
     ctx->pool_gen = ctx->pools->gen.load(std::memory_order_acquire);
 }
@@ -2447,6 +2459,9 @@ int cfmm_destroy(cfmm_ctx *ctx)
     if (ctx->tender_dev) (void)hipFree(ctx->tender_dev);
     if (ctx->audit_dev) (void)hipFree(ctx->audit_dev);
     if (ctx->audit_host) (void)hipHostFree(ctx->audit_host);
+    if (ctx->held.dev) (void)hipFree(ctx->held.dev);
+    if (ctx->held.rq_dev) (void)hipFree(ctx->held.rq_dev);
+    if (ctx->held.rq_host) (void)hipHostFree(ctx->held.rq_host);
     if (ctx->sel_dev) (void)hipFree(ctx->sel_dev);
     if (ctx->sel_host) (void)hipHostFree(ctx->sel_host);
     if (ctx->prices.dev) (void)hipFree(ctx->prices.dev);
@@ -5460,6 +5475,250 @@ int cfmm_debug_audit_launch(cfmm_ctx *ctx, int timed, int grid, double *out2)
     ctx->audit_timed = timed != 0;
     if (grid > 0) ctx->audit_grid = grid;
     if (out2) { out2[0] = ctx->audit_sec; out2[1] = (double)ctx->audit_reordered; }
+    return CFMM_OK;
+}
+
+// ---- a held route, re-quoted on the pools as they are now (requote.hpp; requote_rules.hpp; docs/requote.md) ---------------------------
+// The hold: the read-backs' own kernels write every bucket's tenders into the context's arena instead of the read-back scratch (the
+// kink loop's two-asset tenders, which live on the host, are copied up); one count per bucket, ONE copy and ONE synchronisation.  The
+// re-quote: one pass over every bucket on this context's stream, as a reader of the store like the audit, ONE copy (records | limbs)
+// and ONE synchronisation.  Nothing of the store and nothing else of the context is written.
+namespace {
+// a held route that still describes the resident buckets, or the refusal
+int held_route(cfmm_ctx *ctx, const char *who, const route::Counts &counts)
+{
+    if (!ctx->held.valid) return fail(ctx, CFMM_E_STATE, "%s: no route is held (cfmm_hold_route first; an upload into the context's pools drops it)", who);
+    if (!requote::same_counts(ctx->held.counts, counts)) return fail(ctx, CFMM_E_STATE, "%s: the held route does not match the resident buckets", who);
+    return CFMM_OK;
+}
+
+// one bucket's [cnt] doubles at `off` of the held arena back to the caller
+int held_back(cfmm_ctx *ctx, const char *who, int q, int k, bool scales, double *first, double *second)
+{
+    if (sharded(ctx)) return fail(ctx, CFMM_E_UNSUPPORTED, "%s: pool-sharded contexts are not served", who);
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
+    const route::Counts counts = bucket_counts(entry.ps);
+    { int rc = held_route(ctx, who, counts); if (rc) return rc; }
+    if (scales && !ctx->held.scaled) return fail(ctx, CFMM_E_STATE, "%s: the held route has not been re-quoted (cfmm_requote_route first)", who);
+    const size_t m = (size_t)counts.m[q];
+    if (m == 0) return CFMM_OK;
+    const requote::HoldLayout l = requote::hold_layout(counts);
+    if (scales) { if (first) { int rc = download_staged(ctx, first, ctx->held.dev + l.scl[q], m * sizeof(double)); if (rc) return rc; } }
+    else {
+        const size_t cnt = (size_t)k * m;
+        if (first) { int rc = download_staged(ctx, first, ctx->held.dev + l.ten[q], cnt * sizeof(double)); if (rc) return rc; }
+        if (second) { int rc = download_staged(ctx, second, ctx->held.dev + l.ten[q] + cnt, cnt * sizeof(double)); if (rc) return rc; }
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CFMM_OK;
+}
+
+unsigned requote_grid(const cfmm_ctx *ctx, int64_t m)
+{
+    const int64_t chunks = (m + RQ_THREADS - 1) / RQ_THREADS;
+    return (unsigned)std::min<int64_t>(chunks, ctx->held.grid);
+}
+
+struct RequoteRun {
+    cfmm_ctx *ctx;
+    PoolStore &ps;
+    double tol;
+    route::Counts counts;
+    requote::HoldLayout hl;
+    requote::Span sp;
+    double sc;                         // 2^F (det_scales)
+};
+
+int requote_reserve(RequoteRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    if (ctx->held.rq_dev) return CFMM_OK;
+    HIP_TRY(ctx, hipMalloc((void **)&ctx->held.rq_dev, R.sp.total));
+    hipError_t e = hipHostMalloc((void **)&ctx->held.rq_host, R.sp.parts);
+    if (e != hipSuccess) { (void)hipFree(ctx->held.rq_dev); ctx->held.rq_dev = nullptr; ctx->held.rq_host = nullptr; return fail(ctx, CFMM_E_HIP, "requote_route: pinned records -> %s", hipGetErrorString(e)); }
+    return CFMM_OK;
+}
+
+int requote_launches(RequoteRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    RequoteArgs a;
+    a.n = ctx->n; a.sc = R.sc; a.tol = R.tol;
+    a.limbs = (unsigned long long *)(ctx->held.rq_dev + R.sp.limbs);
+    RequoteRec *recs = (RequoteRec *)(ctx->held.rq_dev + R.sp.recs), *parts = (RequoteRec *)(ctx->held.rq_dev + R.sp.parts);
+    const size_t lds = 3 * (size_t)ctx->n * sizeof(unsigned long long);
+    const dim3 blk(RQ_THREADS);
+    ctx->held.reordered = 0;
+    each_bucket(R.ps, [&](auto &r, int q, auto FAMILY, auto KIND, auto K) {
+        const auto b = r.b;
+        const dim3 grid(requote_grid(ctx, b.m));
+        const double *ten = ctx->held.dev + R.hl.ten[q];
+        double *scl = ctx->held.dev + R.hl.scl[q];
+        a.rec = recs + q; a.part = parts + (size_t)q * RQ_GRID_MAX;
+        if constexpr (FAMILY == 0) {
+            ctx->held.reordered += b.perm != nullptr;
+            hipLaunchKernelGGL(requote2_kernel<KIND>, grid, blk, lds, ctx->stream, b, ten, scl, a);
+        } else if constexpr (FAMILY == 1) {
+            ctx->held.reordered += b.perm != nullptr;
+            hipLaunchKernelGGL(requoteN_kernel<K>, grid, blk, lds, ctx->stream, b, ten, scl, a);
+        } else hipLaunchKernelGGL((requoteG_kernel<KIND, K>), grid, blk, lds, ctx->stream, b, ten, scl, a);
+    });
+    HIP_TRY(ctx, hipGetLastError());
+    return CFMM_OK;
+}
+
+int requote_pass(RequoteRun &R)
+{
+    cfmm_ctx *ctx = R.ctx;
+    double scd;
+    det_scales(ctx, R.sc, scd);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->held.rq_dev, 0, R.sp.parts, ctx->stream));
+    return timed_pass(ctx, ctx->held.timed, &ctx->held.sec, [&] { return requote_launches(R); }, [&] {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->held.rq_host, ctx->held.rq_dev, R.sp.parts, hipMemcpyDeviceToHost, ctx->stream));
+        return (int)CFMM_OK;
+    });
+}
+
+void requote_report(RequoteRun &R, cfmm_requote *out, double *psi, uint64_t *limbs)
+{
+    cfmm_ctx *ctx = R.ctx;
+    const int n = ctx->n;
+    const RequoteRec *res = (const RequoteRec *)(ctx->held.rq_host + R.sp.recs);
+    const unsigned long long *hl = (const unsigned long long *)(ctx->held.rq_host + R.sp.limbs);
+    requote::report(requote::fold(res, R.counts), route::fixed_exponent(R.sc), out);
+    if (limbs) std::memcpy(limbs, hl, 3 * (size_t)n * sizeof(uint64_t));
+    std::vector<double> hp((size_t)n);
+    route::psi_from_limbs(hl, n, out->fixed_exponent, hp.data());
+    if (psi) std::memcpy(psi, hp.data(), (size_t)n * sizeof(double));
+    if (!ctx->have_utility) return;
+    const route::PsiWorth w = route::psi_worth(hp.data(), n, ctx->hc.data(), ctx->hh.data(), ctx->hctype.data(), ctx->max_reserve);
+    out->value = w.value; out->infeas = w.infeas;
+}
+}  // namespace
+
+int cfmm_hold_route(cfmm_ctx *ctx, cfmm_route_info *info)
+{
+    const char *who = "hold_route";
+    if (!ctx) return CFMM_E_ARG;
+    if (info) std::memset(info, 0, sizeof *info);
+    if (sharded(ctx)) return fail(ctx, CFMM_E_UNSUPPORTED, "%s: pool-sharded contexts are not served", who);
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
+    { int rc = apply_refusals(ctx, who); if (rc) return rc; }
+    const route::Counts counts = bucket_counts(entry.ps);
+    const TradeLayout tl = route::trade_layout(counts);
+    const requote::HoldLayout l = requote::hold_layout(counts);
+    const bool kink = ctx->pt.tr_ovr_valid;
+    if (kink && ctx->pt.tr_ovr.size() < tl.two_asset()) return fail(ctx, CFMM_E_STATE, "%s: the kink loop's tenders do not match the resident buckets", who);
+    ctx->held.valid = ctx->held.scaled = false;            // (a hold that fails half way leaves no route)
+    if (l.total > ctx->held.cap) {
+        if (ctx->held.dev) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->held.dev); ctx->held.dev = nullptr; ctx->held.cap = 0; }
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->held.dev, std::max<size_t>(l.total, 1) * sizeof(double)));
+        ctx->held.cap = l.total;
+    }
+    // (the trading pools per slot are counted into the read-back scratch, which no kernel of this call uses otherwise)
+    double *d0 = nullptr, *d1 = nullptr;
+    { int rc = trade_scratch(ctx, (size_t)route::SLOTS, &d0, &d1); if (rc) return rc; }
+    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(d0);
+    HIP_TRY(ctx, hipMemsetAsync(cnt, 0, route::SLOTS * sizeof(unsigned long long), ctx->stream));
+    const TenderPoint p = tender_point(ctx);
+    hipError_t copied = hipSuccess;                         // (the first copy of the kink loop's tenders that fails: the hold fails with it)
+    each_bucket(entry.ps, [&](auto &r, int q, auto FAMILY, auto KIND, auto K) {
+        const auto b = r.b;                                 // (no tie flags: the call refuses while any are set)
+        constexpr int k = K;
+        double *dd = ctx->held.dev + l.ten[q], *dl = dd + (size_t)k * b.m;
+        const dim3 grid((unsigned)((b.m + 255) / 256)), blk(256);
+        if constexpr (FAMILY == 0) {
+            if (kink) {
+                const hipError_t e = hipMemcpyAsync(dd, ctx->pt.tr_ovr.data() + tl.off2[KIND], 4 * (size_t)b.m * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+                if (copied == hipSuccess) copied = e;
+            } else if (p.mu > 0.0) hipLaunchKernelGGL(smooth_trades_kernel<KIND>, grid, blk, 0, ctx->stream, b, p.nu, p.slo, p.mu, dd, dl);
+            else hipLaunchKernelGGL(trades2_kernel<KIND>, grid, blk, 0, ctx->stream, b, p.nu, dd, dl);
+        } else if constexpr (FAMILY == 1) hipLaunchKernelGGL(tradesn_kernel<K>, grid, blk, 0, ctx->stream, b, p.nu, p.slo, dd, dl);
+        else hipLaunchKernelGGL((tradesg_kernel<KIND, K>), grid, blk, 0, ctx->stream, b, (const int *)nullptr, p.nu, p.slo, p.mu, dd, dl);
+        hipLaunchKernelGGL(hold_count_kernel, dim3((unsigned)std::min<int64_t>((b.m + RQ_THREADS - 1) / RQ_THREADS, 1024)), dim3(RQ_THREADS), 0, ctx->stream,
+                           (const double *)dd, (long long)b.m, k, cnt + q);
+    });
+    if (copied != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return fail(ctx, CFMM_E_HIP, "%s: the kink loop's tenders -> %s", who, hipGetErrorString(copied)); }
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned long long moved[route::SLOTS];
+    HIP_TRY(ctx, hipMemcpyAsync(moved, cnt, sizeof moved, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->held.counts = counts;
+    ctx->held.valid = true;
+    if (info) {
+        info->pools = l.pools; info->bytes = (int64_t)(l.total * sizeof(double));
+        for (int q = 0; q < route::SLOTS; ++q) if (counts.m[q]) info->pools_trading += (int64_t)moved[q];
+    }
+    return CFMM_OK;
+}
+
+int cfmm_release_route(cfmm_ctx *ctx)
+{
+    if (!ctx) return CFMM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->held.valid = ctx->held.scaled = false;
+    if (ctx->held.dev) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->held.dev); ctx->held.dev = nullptr; ctx->held.cap = 0; }
+    return CFMM_OK;
+}
+
+int cfmm_get_held2(cfmm_ctx *ctx, int kind, double *delta, double *lambda)
+{
+    if (!ctx || kind < 0 || kind >= CFMM_POOL_KINDS2) return CFMM_E_ARG;
+    return held_back(ctx, "get_held2", route::slot2(kind), 2, false, delta, lambda);
+}
+int cfmm_get_heldN(cfmm_ctx *ctx, int k, double *delta, double *lambda)
+{
+    if (!ctx || k < 3 || k > CFMM_MAX_POOL_SIZE) return CFMM_E_ARG;
+    return held_back(ctx, "get_heldN", route::slotN(k), k, false, delta, lambda);
+}
+int cfmm_get_heldG(cfmm_ctx *ctx, int kind, int k, double *delta, double *lambda)
+{
+    if (!ctx || kind < 0 || kind >= CFMM_POOLK_KINDS || k < 2 || k > CFMM_MAX_POOL_SIZE) return CFMM_E_ARG;
+    return held_back(ctx, "get_heldG", route::slotG(kind, k), k, false, delta, lambda);
+}
+int cfmm_get_route_scale2(cfmm_ctx *ctx, int kind, double *s)
+{
+    if (!ctx || kind < 0 || kind >= CFMM_POOL_KINDS2) return CFMM_E_ARG;
+    return held_back(ctx, "get_route_scale2", route::slot2(kind), 2, true, s, nullptr);
+}
+int cfmm_get_route_scaleN(cfmm_ctx *ctx, int k, double *s)
+{
+    if (!ctx || k < 3 || k > CFMM_MAX_POOL_SIZE) return CFMM_E_ARG;
+    return held_back(ctx, "get_route_scaleN", route::slotN(k), k, true, s, nullptr);
+}
+int cfmm_get_route_scaleG(cfmm_ctx *ctx, int kind, int k, double *s)
+{
+    if (!ctx || kind < 0 || kind >= CFMM_POOLK_KINDS || k < 2 || k > CFMM_MAX_POOL_SIZE) return CFMM_E_ARG;
+    return held_back(ctx, "get_route_scaleG", route::slotG(kind, k), k, true, s, nullptr);
+}
+
+int cfmm_requote_route(cfmm_ctx *ctx, double tol_scale, cfmm_requote *out, double *psi, uint64_t *limbs)
+{
+    const char *who = "requote_route";
+    if (!ctx) return CFMM_E_ARG;
+    if (!out) return fail(ctx, CFMM_E_ARG, "%s: out is NULL", who);
+    requote::blank(out);
+    if (sharded(ctx)) return fail(ctx, CFMM_E_UNSUPPORTED, "%s: pool-sharded contexts are not served (re-quote the shards' tenders on the host)", who);
+    if (ctx->n > AU_MAX_TOKENS) return fail(ctx, CFMM_E_LIMIT, "%s: %d tokens exceed the workgroup's tile of 3 n 64-bit limbs (n <= %d)", who, ctx->n, AU_MAX_TOKENS);
+    PoolEntry entry(ctx); HIP_TRY(ctx, entry.device);
+    const route::Counts counts = bucket_counts(entry.ps);
+    { int rc = held_route(ctx, who, counts); if (rc) return rc; }
+    RequoteRun R{ctx, entry.ps, requote::tol_scale(tol_scale), counts, requote::hold_layout(counts), requote::span(ctx->n, RQ_GRID_MAX), 0.0};
+    { int rc = requote_reserve(R); if (rc) return rc; }
+    ctx->held.scaled = false;
+    { int rc = requote_pass(R); if (rc) return rc; }
+    ctx->held.scaled = true;
+    requote_report(R, out, psi, limbs);
+    return CFMM_OK;
+}
+
+int cfmm_debug_requote_launch(cfmm_ctx *ctx, int timed, int grid, double *out2)
+{
+    if (!ctx) return CFMM_E_ARG;
+    if (grid < 0 || grid > RQ_GRID_MAX) return fail(ctx, CFMM_E_ARG, "debug_requote_launch: grid %d is outside 0 (unchanged), 1 .. %d", grid, RQ_GRID_MAX);
+    ctx->held.timed = timed != 0;
+    if (grid > 0) ctx->held.grid = grid;
+    if (out2) { out2[0] = ctx->held.sec; out2[1] = (double)ctx->held.reordered; }
     return CFMM_OK;
 }
 

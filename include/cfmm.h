@@ -306,6 +306,82 @@ int cfmm_audit_trades(cfmm_ctx *ctx, const cfmm_audit_tenders *own /* or NULL */
  * (1 .. 2048; 0: leave as it is -- the audited result does not depend on it); out2 (or NULL) receives {seconds of the last audit's
  * launches, number of buckets the last audit found stored reordered (positions mapped through the upload's permutation)} */
 int cfmm_debug_audit_launch(cfmm_ctx *ctx, int timed, int grid, double *out2);
+/* A held route, re-quoted on the pools as they are now (docs/requote.md).  Between the quote and the execution the pools move; on chain a
+ * route executes with its INPUTS fixed, and each pool pays what its curve gives at the reserves it has by then.
+ *
+ * cfmm_hold_route keeps, in device memory the context owns, exactly the tenders cfmm_get_trades2 / N / G would return at the moment of the
+ * call, for every bucket (cfmm_apply_trades' contract: the exact pool solutions after a first-order solve or cfmm_set_nu, the gross
+ * smoothed tenders after a second-order solve, the library's own kink-loop tenders with their partial fills).  Per bucket
+ * delta [k][m] | lambda [k][m] in upload order, and [m] scales behind them: 16 k m + 8 m bytes per bucket.  No tender crosses the host
+ * but the kink loop's, which live there.
+ *   - refusals, as cfmm_apply_trades': no prices yet -> CFMM_E_STATE; tie flags or price ties set by the caller, or a pool-sharded
+ *     context -> CFMM_E_UNSUPPORTED;
+ *   - a second hold replaces the first.  The held route STAYS through cfmm_update_pools*, cfmm_update_terms*, cfmm_apply_trades,
+ *     cfmm_solve*, cfmm_set_nu and cfmm_set_utility, through this context or any context sharing the pools.  It goes with an upload into
+ *     the context's pool store (the positions no longer mean anything: later route calls return CFMM_E_STATE), cfmm_release_route and
+ *     cfmm_destroy.  cfmm_clone and cfmm_subnetwork do not carry it over;
+ *   - the hold changes nothing a later call can see and counts as a reader of the pools like cfmm_get_trades*.
+ * cfmm_get_held2 / N / G read the held tenders back in the shapes of cfmm_get_trades*: once the pools have moved, nothing else can.
+ *
+ * cfmm_requote_route.  For every pool that trades in the held route, at the CURRENT resident reserves R, fee gamma and weights /
+ * parameter (in-place updates and applied trades included), the inputs stay and the outputs are scaled onto the pool's curve:
+ *      x_j(s) = (R_j + gamma Delta_j) - s Lambda_j,    Lambda'_j = fl(s Lambda_j)       (every operation rounded on its own)
+ * with s >= 0 the root of the pool's slack as cfmm_audit_trades defines it per class: sum_j w_j log(x_j(s) / R_j) = 0 (constant product,
+ * weighted, geo-mean), phi(x(s)) = phi(R) (stableswap, power sum), and the closed form s = gamma sum Delta / sum Lambda for the
+ * constant-sum kinds.  The slack is concave and strictly decreasing in s and >= 0 at s = 0: the root is unique.  With one paying leg s
+ * is the exact-in swap output over the quoted output; with several the outputs keep their proportions.
+ *   cap       s <= s_cap = min over legs with Lambda_j > 0 of (R_j + gamma Delta_j) / Lambda_j, rounded down so that no x_j(s_cap) is
+ *             negative (constant sum) or every x_j(s_cap) stays positive (the other classes); a pool whose slack is still >= 0
+ *             there -- a constant-sum leg too small to pay -- pays s_cap: pools_capped
+ *   special   sum Lambda = 0: s = 1;  sum Delta = 0 with a positive Lambda: s = 0;  a pool without tenders does not trade: s = 1
+ *   failed    a held tender or a reserve that is negative or not finite, a slack that is not >= 0 at s = 0: s = NaN, the pool is left
+ *             out of psi and counted in pools_failed
+ *   search    bracketed in [0, s_cap): a bracket lo < hi with slack(lo) >= 0 and slack(hi) < 0, both evaluated; every trial lies strictly
+ *             inside it (a Newton step while it does, else the midpoint) and replaces the end of its sign.  STOPPING RULE: the search
+ *             ends when lo and hi are adjacent doubles and returns lo -- an s whose own slack evaluation is >= 0, and the last double for
+ *             which it is: the pool accepts what the call says it pays, and nothing is left on the table beyond the slack's rounding.
+ * psi, exactly, as cfmm_audit_trades': every non-zero Lambda'_j adds +Lambda'_j and every non-zero Delta_j adds -Delta_j, each floored on
+ * its own to the 96-bit fixed point floor(y 2^F) (F from the CURRENT largest reserve and smallest fee) and summed with integer atomics;
+ * limbs and psi have the audit's layout and its one conversion.  Given the scales, psi is a function of (held tenders, s) alone: bitwise
+ * the same on every run and for any launch geometry.
+ *   pools_short / pools_long   trading pools with s < 1 - tol_scale / s > 1 + tol_scale (tol_scale <= 0: the default 1e-9)
+ *   min_scale                  the smallest s over the trading pools whose root was found, with the family / kind / k / upload-order
+ *                              position of the pool that holds it (ties: the first bucket in bucket order, then the lowest position;
+ *                              +inf and -1s when no pool qualifies)
+ *   value / infeas             from the re-quoted psi and the utility last set, as cfmm_audit's (NaN without one)
+ * cfmm_get_route_scale2 / N / G return the scales of the last re-quote, [m] in upload order: 1 for pools that do not trade, NaN for failed
+ * ones (CFMM_E_STATE before the first re-quote of the held route).  The re-quoted tenders are (Delta, fl(s Lambda)).
+ * The call touches nothing a later call can see (no pool column, warm start of the table's search, generation, price, cached solution or
+ * captured launch) and counts as a reader of the store; an in-place update through a sharer is refused meanwhile.
+ * Refusals: no held route (or one an upload has outdated) -> CFMM_E_STATE; out == NULL -> CFMM_E_ARG; more than 2560 tokens (the audit's
+ * tile) -> CFMM_E_LIMIT; a pool-sharded context -> CFMM_E_UNSUPPORTED. */
+typedef struct {
+    int64_t pools, pools_trading;         /* resident pools; those with a non-zero held tender */
+    int64_t bytes;                        /* device memory the held route takes                */
+} cfmm_route_info;
+
+typedef struct {
+    int64_t pools, pools_trading, pools_short, pools_long, pools_capped, pools_failed, legs_out_of_range;
+    int32_t min_family, min_kind, min_k, fixed_exponent;          /* family / kind / k as in cfmm_apply_info; F of psi */
+    int64_t min_pos;                                              /* upload order; -1s when no trading pool has a root */
+    double  min_scale;
+    double  value, infeas;                                        /* from the re-quoted psi and the utility last set   */
+} cfmm_requote;
+
+int cfmm_hold_route(cfmm_ctx *ctx, cfmm_route_info *info /* or NULL */);
+int cfmm_release_route(cfmm_ctx *ctx);                            /* CFMM_OK without a held route too */
+int cfmm_get_held2(cfmm_ctx *ctx, int kind, double *delta /* [2][m] or NULL */, double *lambda /* [2][m] or NULL */);
+int cfmm_get_heldN(cfmm_ctx *ctx, int k, double *delta /* [k][m] or NULL */, double *lambda /* [k][m] or NULL */);
+int cfmm_get_heldG(cfmm_ctx *ctx, int kind, int k, double *delta, double *lambda);
+int cfmm_requote_route(cfmm_ctx *ctx, double tol_scale /* <= 0: default */, cfmm_requote *out,
+                       double *psi /* [n] or NULL */, uint64_t *limbs /* [3][n] or NULL */);
+int cfmm_get_route_scale2(cfmm_ctx *ctx, int kind, double *s /* [m], upload order */);
+int cfmm_get_route_scaleN(cfmm_ctx *ctx, int k, double *s /* [m] */);
+int cfmm_get_route_scaleG(cfmm_ctx *ctx, int kind, int k, double *s /* [m] */);
+/* test and measurement hook of the re-quote's launches (tools/requote_timing.py, tests/test_gpu_requote.py), shaped like
+ * cfmm_debug_audit_launch: `timed` brackets the launches with HIP events; grid > 0: workgroups per pass from then on (1 .. 2048; the
+ * result does not depend on it); out2 (or NULL): {seconds of the last re-quote's launches, buckets it found stored reordered} */
+int cfmm_debug_requote_launch(cfmm_ctx *ctx, int timed, int grid, double *out2);
 /* Selecting pools of the route on the device (docs/subnetwork.md): every resident pool is measured by the value it takes in at the
  * context's accepted prices,
  *      v_i = sum_j nu_j Delta_ij     over the pool's legs in slot order, every product and every sum rounded on its own,
